@@ -10,7 +10,11 @@ holds a value of more than 64 limbs (the full factorisation is i
 anyone, so CPU and GPU run the same K).  Inputs (A, q) are resident in HBM before the timed
 region; every step starts from column 0 (device-side reset included in the timing).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, the factors of the last step (what download() hands a caller: pinv, Lp, Li,
+Llen, Llimbs, Up, Ui, Ulen, Ulimbs, rholen, rholimbs) are written as DIR/<name>.npy in float64 (see dump_outputs), so
+that two builds can be compared output for output; the inputs are fixed by the seeded generator and the stored order.
 
 N > 1: one rank per GPU under torch.distributed.run (started here as a child process when the
 caller did not).  The path has no exploitable elimination-tree subtrees on this matrix class
@@ -55,7 +59,40 @@ def relaunch_distributed(args):
         cmd.append("--no-secondary")
     if getattr(args, "farm", False):
         cmd.append("--farm")
+    if getattr(args, "dump_outputs", None):
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return cmd
+
+
+DUMP_LIMIT_BYTES = 63 << 20          # array data; with the .npy headers the dump stays under 64 MB
+
+
+def dump_outputs(out_dir, fac):
+    """Write the factor arrays of `fac` (Factorization.download()) as out_dir/<name>.npy, float64.  Index and length arrays
+    are exact in float64; a u64 limb becomes a row [low 32 bits, high 32 bits] (shape (m, 2)), also exact.  If everything
+    together would exceed DUMP_LIMIT_BYTES, every array is replaced by the same fraction of its rows, chosen by a
+    generator seeded from the array's name, and the chosen row numbers are written as <name>_rows.npy."""
+    import zlib
+    import numpy as np
+    arrays = {}
+    for k in ("pinv", "Lp", "Li", "Llen", "Up", "Ui", "Ulen", "rholen"):
+        arrays[k] = np.asarray(fac[k]).astype(np.float64)
+    for k in ("Llimbs", "Ulimbs", "rholimbs"):
+        v = np.asarray(fac[k], dtype=np.uint64)
+        arrays[k] = np.stack([v & np.uint64(0xFFFFFFFF), v >> np.uint64(32)], axis=1).astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if total > DUMP_LIMIT_BYTES:
+        # the row numbers cost 8 bytes per kept row on top of the row itself
+        frac = DUMP_LIMIT_BYTES / sum(a.nbytes + 8 * len(a) for a in arrays.values())
+        for k, a in arrays.items():
+            keep = int(len(a) * frac)
+            rows = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(len(a), size=keep, replace=False))
+            arrays[k] = a[rows]
+            np.save(os.path.join(out_dir, k + "_rows.npy"), rows.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def ref_driver_path():
@@ -319,7 +356,13 @@ def main():
     ap.add_argument("--farm", action="store_true", help="the subtree farm on a block matrix instead of the headline workload")
     ap.add_argument("--no-secondary", action="store_true",
                     help="only the headline workload (used under rocprofv3 so that the kernel statistics are the headline's)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the factors of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.farm and args.dump_outputs:
+        ap.error("--dump-outputs applies to the headline workload, not to --farm")
 
     if os.environ.get("SLIP_HIP_LIBRARY"):
         raise SystemExit("bench.py measures the in-tree HIP library only: unset SLIP_HIP_LIBRARY")
@@ -386,6 +429,8 @@ def main():
     # would otherwise be timed as a pass)
     import slabfile
     fac = f.download()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fac)
     assert slabfile.factor_digest(fac) == idx["digest"], "benchmark run: factor digest differs from the reference's"
     chain = chain_report(fac, K, kernel_ms / args.steps, info)
 

@@ -12,7 +12,7 @@ import pytest
 from conftest import ROOT, load_case
 
 pytestmark = pytest.mark.gpu
-BUILD = os.path.join(ROOT, "tests", "dropin", "_build")
+BUILD = os.path.join(ROOT, "oracle", "_ref", "dropin")
 
 
 def write_triplet(path, fix, n):
@@ -32,12 +32,12 @@ def write_triplet(path, fix, n):
 
 
 def binaries():
-    """The two builds of tests/dropin/dropin_driver.c.  They are compiled by __graft_entry__.build() in the
-    container that has the reference's headers and travel to the GPU box with the snapshot: a missing binary
-    is a broken build, not a reason to skip."""
+    """The two builds of tests/dropin/dropin_driver.c.  They are compiled by __graft_entry__.build() where the
+    reference's headers are, into oracle/_ref/dropin, and travel with oracle/_ref to where the GPU tests run: a
+    missing binary is a broken build, not a reason to skip."""
     hip, ref = os.path.join(BUILD, "dropin_hip"), os.path.join(BUILD, "dropin_ref")
     assert os.path.exists(hip) and os.path.exists(ref), \
-        "drop-in binaries missing: run __graft_entry__.build() where /root/reference exists (make -C tests/dropin)"
+        "drop-in binaries missing: run __graft_entry__.build() where the reference exists (make -C tests/dropin)"
     return hip, ref
 
 

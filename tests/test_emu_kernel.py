@@ -64,13 +64,13 @@ def test_emulated_workers_help_with_update_queues(emu_farm_lib, name, waves, wor
 
 def test_emulated_kernel_under_sanitizers():
     """the kernel source (committer, packages, helpers included) under AddressSanitizer + UBSan on the CPU: a subprocess with
-    libasan preloaded runs small cases against the goldens; any report aborts it (GPU sanitizers are not available)"""
+    the sanitizer runtime preloaded runs small cases against the goldens; any report aborts it (GPU sanitizers are not used)"""
     import sys
     emu_dir = os.path.join(ROOT, "tests", "emu")
     subprocess.check_call(["make", "-s", "-C", emu_dir, "-f", "sanitize.mk", "libslip_emu_san.so"])
-    libasan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
+    libasan = subprocess.check_output(["make", "-s", "-C", emu_dir, "-f", "sanitize.mk", "print-runtime"], text=True).strip()
     if not os.path.isabs(libasan) or not os.path.exists(libasan):
-        pytest.skip("libasan not found")
+        pytest.skip("the sanitizer runtime was not found")
     code = (
         "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
         "from conftest import load_case, check_against_golden\n"

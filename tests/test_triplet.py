@@ -1,14 +1,14 @@
 """Triplet files <-> limb slabs: the host-side reader/writer of the slab ABI against what the reference's
 SLIP_tripread + SLIP_build_sparse_trip_mpz hold (SLIP_LU/Demo/demos.c:245-331, Source/slip_trip_to_mat.c:23-69) -- the A
 arrays of the golden fixtures were dumped from the reference after it had read these very files.  No GPU involved."""
+import gzip
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_case
-
-REF_MATS = "/root/reference/SLIP_LU/ExampleMats"
 
 
 def same(a, b):
@@ -26,11 +26,12 @@ def test_reader_matches_reference_on_fixture():
 
 
 @pytest.mark.parametrize("case,fname", [("10teams", "10teams_mat.txt"), ("prob159", "prob159_mat.txt"), ("NSR8K", "NSR8K_mat.txt")])
-def test_reader_matches_reference_on_example_mats(case, fname):
+def test_reader_matches_reference_on_example_mats(tmp_path, case, fname):
+    """tests/golden/<case>_triplet.txt.gz is the reference's ExampleMats/<fname>, gzipped"""
     import slip_lu_amd as sl
-    path = os.path.join(REF_MATS, fname)
-    if not os.path.exists(path):
-        pytest.skip("the reference's ExampleMats are not on this machine")
+    path = str(tmp_path / fname)
+    with gzip.open(os.path.join(GOLDEN, case + "_triplet.txt.gz"), "rb") as src, open(path, "wb") as dst:
+        shutil.copyfileobj(src, dst)
     entry, fix = load_case(case)
     n, Ap, Ai, Alen, Al = sl.read_triplet(path)
     assert n == entry["n"]
@@ -82,8 +83,7 @@ def test_malformed_input_is_rejected(tmp_path, text):
     with pytest.raises(sl.SlipError) as e:
         sl.read_triplet(p)
     assert e.value.code == -3
-    for bad in ("bad_mat1.txt", "bad_mat2.txt"):
-        path = os.path.join(REF_MATS, bad)
-        if os.path.exists(path):
-            with pytest.raises(sl.SlipError):
-                sl.read_triplet(path)
+    # the reference's ExampleMats/bad_mat1.txt and bad_mat2.txt
+    for bad in ("bad_triplet1.txt", "bad_triplet2.txt"):
+        with pytest.raises(sl.SlipError):
+            sl.read_triplet(os.path.join(GOLDEN, bad))
