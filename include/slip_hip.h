@@ -49,7 +49,7 @@ typedef struct slip_hip_options {
     int64_t unz_hint;     /*   cf. SLIP_LU_analysis.lnz/.unz; both grow on demand      */
     int32_t workers;      /* column workers (workgroups of a launch; each owns a private */
                           /*   dense vector): 0 = as many as can be resident            */
-    int32_t reserved;     /* diagnostics: bit 0 = no early commit, bit 1 = no committer workgroup, bit 2 = no helping with long update queues, bit 3 = no full packages (chain engine off) */
+    int32_t reserved;     /* diagnostics: bit 0 = no early commit, bit 1 = no committer workgroup, bit 2 = no helping with long update queues, bit 3 = no full packages (chain engine off); bits 4-5 = experiment: workers on CUs within this distance of the committer's stand aside (measured: no effect) */
 } slip_hip_options;
 
 typedef struct slip_hip_info {
@@ -193,8 +193,9 @@ void slip_hip_free(void *p);
 int slip_hip_wave_op_test(int32_t op, int32_t nops, int32_t la, int32_t lb, int32_t W,
                           const uint32_t *a, const uint32_t *b, uint32_t *out);
 
-/* Diagnostic builds (-DSLIP_PROFILE_PHASES) only: shader cycles thread 0 of every worker spent per phase of its
- * columns during the last run (summed over the workers); all zero in the product build. */
+/* Diagnostics builds (slip_lu_amd/csrc/Makefile: `make prof`, `make cprof`) only: shader cycles thread 0 of every worker
+ * spent per phase of its columns during the last run (summed over the workers; `cprof`: the committer's phase times);
+ * all zero in the product build. */
 int slip_hip_factor_phase_cycles(const slip_hip_factor *f, unsigned long long *out24);   /* 24 slots */
 
 const char *slip_hip_version(void);

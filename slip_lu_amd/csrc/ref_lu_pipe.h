@@ -72,9 +72,7 @@ typedef struct {
 } SlipPiv;
 
 /* mutable across launches; the words other workers poll sit in 128-byte lines of their own */
-#ifndef SLIP_FARM_HINTS
 #define SLIP_FARM_HINTS 16           /* hint slots (a power of two, at most 32: one line); 8 / 16 / 32 measured: model6 516 / 501 / 494 ms, C4 3.10 / 3.05 / 3.03, rl5934 119.3 / 120.1 / 121.7 */
-#endif
 typedef struct SlipState {
     int32_t F, Fpiv; int32_t padF[30];              /* ONE aligned 64-bit word: the commit frontier (columns < F have published
                                                        their pivot, stage 1) and, next to it, the pivot row of column F-1 */
@@ -91,7 +89,7 @@ typedef struct SlipState {
     int64_t out_used;                               /* solve: limbs of the output slab in use                            */
     unsigned long long c_upd, c_read, c_write, c_src, c_streamed, c_maxdig, c_macs, c_short, c_farm;   /* c_farm: queues opened to helpers (low word), items helpers ran (high word); c_short: columns committed by the short chain (high word: by the committer) */
     unsigned long long c_eng, c_retract;            /* c_eng: columns committed by the committer's chain engine (low word), late sources it applied (high word); c_retract: packages retracted (low), exported again (high) */
-    unsigned long long prof[24];                    /* -DSLIP_PROFILE_PHASES builds only */
+    unsigned long long prof[24];                    /* SLIP_PROFILE builds only */
 } SlipState;
 
 /* immutable during a launch: passed by value, copied to LDS, private fields set per worker there */
@@ -150,16 +148,60 @@ typedef struct SlipSolveArgs {
     int64_t ostride;                                                     /* limbs of output slab reserved per right-hand side        */
 } SlipSolveArgs;
 
-#if defined(SLIP_PROFILE_PHASES) && !defined(SLIP_EMULATE)
-#define SLIP_STAMP(slot) do { if (tid == 0) { unsigned long long now_ = clock64(); prof_[slot] += now_ - t_prev_; t_prev_ = now_; if (hstamp_) hstamp_[slot] = (int32_t) slip_realtime(); } } while (0)
-#define SLIP_PROFILING 1
-#define SLIP_STAMP_INIT() unsigned long long t_prev_ = clock64(); unsigned long long prof_[24] = {0}; int32_t *hstamp_ = (int32_t *) 0
-#define SLIP_STAMP_FLUSH(st) do { if (tid == 0) for (int s_ = 0; s_ < 24; s_++) if (prof_[s_]) slip_agent_add_u64(&(st)->prof[s_], prof_[s_]); } while (0)
-#else
-#define SLIP_STAMP(slot) do { } while (0)
-#define SLIP_STAMP_INIT() do { } while (0)
-#define SLIP_STAMP_FLUSH(st) do { } while (0)
+/* The diagnostics builds (csrc/Makefile: `make prof`, `make cprof`); the product build has neither.
+ *   SLIP_PROFILE=1  the workers: phase stamps (SlipState.prof), the per-column time line and traces of P.dbg (below)
+ *   SLIP_PROFILE=2  the committer's phase clock alone: the workers do not stamp, so the committer's times are not inflated
+ * In the product build SLIP_PROF_* and SLIP_TL expand to nothing and the stamps to an empty statement. */
+#ifndef SLIP_PROFILE
+#define SLIP_PROFILE 0
 #endif
+#if SLIP_PROFILE == 1 && !defined(SLIP_EMULATE)
+#define SLIP_PROF_W(...) __VA_ARGS__                /* code of the workers' profile build only */
+/* shader cycles per phase (thread 0), summed into SlipState.prof at the end of a column */
+#define SLIP_STAMP_INIT() unsigned long long t_prev_ = clock64(); unsigned long long prof_[24] = {0}; int32_t *hstamp_ = (int32_t *) 0
+#define SLIP_STAMP(slot) do { if (tid == 0) { unsigned long long now_ = clock64(); prof_[slot] += now_ - t_prev_; t_prev_ = now_; if (hstamp_) hstamp_[slot] = (int32_t) slip_realtime(); } } while (0)
+#define SLIP_STAMP_FLUSH(st) do { if (tid == 0) for (int s_ = 0; s_ < 24; s_++) if (prof_[s_]) slip_agent_add_u64(&(st)->prof[s_], prof_[s_]); } while (0)
+/* cycles of the sub-steps of the commit chain (the commit-chain words of P.dbg) */
+#define SLIP_TR(i) do { if (tid == 0) { const unsigned long long n_ = slip_clock(); trs_[i] = (int32_t)(n_ - trp_); trp_ = n_; } } while (0)
+#else
+#define SLIP_PROF_W(...)
+#define SLIP_STAMP_INIT() do { } while (0)
+#define SLIP_STAMP(slot) do { } while (0)
+#define SLIP_STAMP_FLUSH(st) do { } while (0)
+#define SLIP_TR(i) do { } while (0)
+#endif
+/* word w of column c's time line, written where cond holds */
+#define SLIP_TL(cond, c, w) SLIP_PROF_W(if (cond) P.dbg[slip_dbg_timeline(P.n) + 6 * (int64_t)(c) + (w)] = (int32_t) slip_realtime())
+#if SLIP_PROFILE == 2 && !defined(SLIP_EMULATE)
+#define SLIP_PROF_C(...) __VA_ARGS__                /* code of the committer's profile build only */
+/* 10 ns ticks per phase of the committer, written to SlipState.prof at the end of the launch */
+#define SLIP_CT(i) do { if (tid == 0) { const unsigned long long n_ = slip_realtime(); tacc_[i] += n_ - tq_; tq_ = n_; } } while (0)
+#else
+#define SLIP_PROF_C(...)
+#define SLIP_CT(i) do { } while (0)
+#endif
+
+/* Emulator tracing (-DSLIP_EMU_TRACE on an emulation build): printf-style lines on stderr, from thread 0 of a workgroup
+ * or from lane 0 of the calling wave (the committer's waves work apart) */
+#if defined(SLIP_EMULATE) && defined(SLIP_EMU_TRACE)
+#define SLIP_TRACE(...) do { if (slip_tid() == 0) fprintf(stderr, __VA_ARGS__); } while (0)
+#define SLIP_TRACE_L0(...) do { if (slip_lane() == 0) fprintf(stderr, __VA_ARGS__); } while (0)
+#else
+#define SLIP_TRACE(...) ((void) 0)
+#define SLIP_TRACE_L0(...) ((void) 0)
+#endif
+
+/* The debug buffer P.dbg (32-bit words; written by the profile builds and the solve launches, read back by the diagnostic
+ * entry points of slip_hip.hip).  Every region is named here once; n is the dimension of the matrix. */
+SLIP_HD constexpr int64_t slip_dbg_trace(int64_t n)     { return 0; }             /* column trace: 8 words per column */
+SLIP_HD constexpr int64_t slip_dbg_seen(int64_t n)      { return 8 * n; }         /* per column: the chip clock when its worker saw its turn */
+SLIP_HD constexpr int64_t slip_dbg_chain(int64_t n)     { return 9 * n; }         /* commit-chain words: 8 sub-step cycles per column */
+SLIP_HD constexpr int64_t slip_dbg_flags(int64_t n)     { return 17 * n; }        /* path flags: 1 word per column */
+SLIP_HD constexpr int64_t slip_dbg_timeline(int64_t n)  { return 18 * n; }        /* wall-clock time line: 6 words per column */
+SLIP_HD constexpr int64_t slip_dbg_heavy(int64_t n)     { return 24 * n; }        /* heavy trace: 64 records of 32 words (column k: record k & 63) */
+SLIP_HD constexpr int64_t slip_dbg_place(int64_t n)     { return 24 * n + 2048; } /* placement: 1 word per workgroup (the first 2048) */
+SLIP_HD constexpr int64_t slip_dbg_solve(int64_t n)     { return 24 * n + 3072; } /* solve time line: 5 words (a solve launch writes no placement) */
+SLIP_HD constexpr int64_t slip_dbg_words(int64_t n)     { return 24 * n + 4096; } /* the whole buffer */
 
 /* LDS layout in 32-bit words */
 #define SLIP_SCRATCH_WAVES 16       /* waves a worker's share of the global scratch is sized for */
@@ -195,9 +237,7 @@ enum { SV_ERR = 0, SV_CNT0 = 1 /* 3 rotating work counters */, SV_MAXDIG = 4, SV
 #define SLIP_PP_WORDS  14
 /* a column's package for the committer (ref_lu_pipe_commit.h), offsets in 32-bit words */
 #define SLIP_PKG_CANDS   16       /* a package lists at most this many candidates ... */
-#ifndef SLIP_PKG_NROWMAX
 #define SLIP_PKG_NROWMAX 256      /* ... of a pattern of at most this many rows (512 measured slower: the committer reads every row) */
-#endif
 #define SLIP_PKG_HDR     0        /* 64-bit {k+1, version}: even = valid, odd = being written or retracted; a column may export again */
 #define SLIP_PKG_STAMP   2
 #define SLIP_PKG_NROWS   3
@@ -593,9 +633,7 @@ template <int D> SLIP_DEV int slip_ensure_inv_reg(const SlipParams &P, int p, in
  * 512 / 526, model6 628 / 627-636 / 644, d18512 550 / 550 / 550: the inverses ARE reused -- the rows of a heavy column share
  * few history levels -- so the Newton extension is paid once per (pivot, width) and a product against the cached inverse
  * (one wr_mul) beats W dependent steps every time after that.  One digit-by-digit division per pivot is the default. */
-#ifndef SLIP_INV_DEMAND
 #define SLIP_INV_DEMAND 1
-#endif
 template <int D> SLIP_DEV int slip_div_piv_reg(const SlipParams &P, WR<D> &Y, int W, int pd, const SlipPiv &d, dig_t *b0)
 {
     const int have = (int) slip_bcast0_u32((uint32_t) slip_piv_invlen(P.piv.at(pd)));
@@ -1001,11 +1039,7 @@ template <int D> SLIP_DEV void slip_mul_row_finish(const SlipParams &P, const Sl
     /* bulk L data: plain (coalesced) stores; the worker's release fence before Lready[k] publishes them (a 4-byte
      * write-through store is one fabric write per lane: 6x the time of these rows).  A candidate of the early commit may
      * become the pivot: its digits are also left in an LDS slot, from where the publishing wave writes them through. */
-#ifdef SLIP_BULK_SC1
-    wr_store_s<D>((dig_t *)(P.Llimbs + off), Y, (len + 1) & ~1);
-#else
     wr_store_g<D>((dig_t *)(P.Llimbs + off), Y, (len + 1) & ~1);
-#endif
     const uint32_t d1 = len ? wr_digit<D>(Y, len - 1) : 0u;
     const int neg = (int)((rec3 >> 2) & 1u) ^ (M.len < 0);
     const int32_t slen = neg ? -len : len;
@@ -1195,21 +1229,10 @@ SLIP_DEVN int slip_tol_compare_out(uint64_t tol_m, int te, const dig_t *num, int
 #ifndef SLIP_FARM_MIN_ITEMS
 #define SLIP_FARM_MIN_ITEMS 16          /* ... and shorter queues neither */
 #endif
-#ifndef SLIP_POLL_NEAR
 #define SLIP_POLL_NEAR 16               /* a worker this close to its turn polls the frontier at the short interval */
-#endif
-#ifndef SLIP_POLL_MAXREPS
 #define SLIP_POLL_MAXREPS 32            /* further away: min(distance, this) long sleeps between two polls */
-#endif
-#ifndef SLIP_FARM_URGENT_DIST
 #define SLIP_FARM_URGENT_DIST 48        /* a waiting worker this close to its own turn only helps with queues the frontier waits for */
-#endif
-#ifndef SLIP_FARM_FEW_LIMBS
 #define SLIP_FARM_FEW_LIMBS 96          /* ... unless every item is at least this long (then two are enough) */
-#endif
-#ifndef SLIP_FARM_KIND2
-#define SLIP_FARM_KIND2     1
-#endif
 #ifndef SLIP_FARM_KIND2_COST
 #define SLIP_FARM_KIND2_COST 16384      /* items * limbs^2: the division queues of committed columns (their readers wait for stage 2);
                                          * measured on the C4 window: 262144 -> 3.63 ms, 65536 -> 3.36, 16384 -> 3.31, 4096 -> 3.38, 1024 -> 3.35 */
@@ -1217,14 +1240,10 @@ SLIP_DEVN int slip_tol_compare_out(uint64_t tol_m, int te, const dig_t *num, int
 #ifndef SLIP_FARM_NEAR_DIV
 #define SLIP_FARM_NEAR_DIV  1125        /* ... and only when the column's turn comes before the worker alone would be done */
 #endif
-#ifndef SLIP_FARM_MAX_HELPERS
 #define SLIP_FARM_MAX_HELPERS 24         /* every helper costs its XCD an L2 invalidate and a write-back */
-#endif
-#ifndef SLIP_FARM_REMOTE_MAX
 #define SLIP_FARM_REMOTE_MAX 4           /* helpers from other dies join only while fewer than this many are inside; the owner's die up to MAX_HELPERS.
                                          * C4 window, (remote, max): (12, 12) 3.40 ms, (0, 12) 3.40, (4, 12) 3.15, (4, 24) 3.05, (2, 24) 3.10, (6, 24) 3.14,
                                          * (4, 32) 3.07, (8, 32) 3.10; (0, x) costs model6 10 %: a few remote helpers are better than none */
-#endif
 #ifndef SLIP_FARM_MIN_COST
 #define SLIP_FARM_MIN_COST  8192        /* items * limbs(rho)^2 below which a queue is not worth publishing */
 #endif
@@ -1350,7 +1369,7 @@ SLIP_DEV void slip_drain(const SlipParams &P, uint32_t *lds, int kind, int j, in
      * and invalidate) */
     /* (a handful of items is worth opening too when each of them is huge: model6's columns have fewer than 16 rows of 200-364
      * limbs, 100+ us per item -- 635 -> 530 ms; the stride tells whether such values exist at all, before the pivot is looked at) */
-    if (P.farm && (kind == 1 || kind == 5 || (kind == 2 && SLIP_FARM_KIND2)) && !sv[SV_ERR] &&
+    if (P.farm && (kind == 1 || kind == 5 || kind == 2) && !sv[SV_ERR] &&
         (nq >= SLIP_FARM_MIN_ITEMS || (nq >= 2 && P.xcap >= 4 * SLIP_FARM_FEW_LIMBS))) {
         /* kind 2: the rows of a committed column that still need their division (its readers wait for its stage 2).  The
          * protocol carries them and a 700-row column of the C4 window then takes 0.35 ms instead of 1.5 -- but the window as a

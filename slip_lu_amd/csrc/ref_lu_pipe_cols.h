@@ -3,29 +3,46 @@
 #ifndef SLIP_REF_LU_PIPE_COLS_H
 #define SLIP_REF_LU_PIPE_COLS_H
 
-#ifdef SLIP_PROFILING
-#define SLIP_TR(i) do { if (tid == 0) { const unsigned long long n_ = slip_clock(); trs_[i] = (int32_t)(n_ - trp_); trp_ = n_; } } while (0)
-#else
-#define SLIP_TR(i) do { } while (0)
-#endif
 #define SLIPDEV_ABORTED 100                 /* internal to the kernel: this worker's column can never commit */
-#if defined(SLIP_EMULATE) && defined(SLIP_EMU_TRACE)
-#define SLIP_WHY(...) do { if (slip_tid() == 0) fprintf(stderr, __VA_ARGS__); } while (0)
-#else
-#define SLIP_WHY(...) do { } while (0)
-#endif
 /* an inconsistency names itself in the state the host prints (site 100 + n, the column, two values) */
 #define SLIP_SITE(n, a, b) do { if (slip_tid() == 0 && !st->dbg_who) { st->dbg_who = 100 + (n); st->dbg_k = k; st->dbg_a = (int32_t)(a); st->dbg_b = (int32_t)(b); } } while (0)
 
 /* the worker's side of the committer protocol (ref_lu_pipe_commit.h) */
 SLIP_DEV void slip_export_package(const SlipParams &P, const int k, uint32_t *lds, const int F0, const int Fl);
 SLIP_DEV void slip_export_full(const SlipParams &P, const int k, uint32_t *lds, const int F0, const int Fl);
-#ifndef SLIP_K1_NEAR
 #define SLIP_K1_NEAR 4                      /* a full package goes out when the frontier is within this many columns of the column */
-#endif
 SLIP_DEV void slip_retract_package(const SlipParams &P, const int k, volatile int32_t *sv);
 
 SLIP_DEV void slip_raise_stop(SlipState *st, int k, int status) { slip_agent_min_i64(&st->stop, ((int64_t) k << 8) | (int64_t) status); }
+
+#if SLIP_PROFILE == 1 && !defined(SLIP_EMULATE)
+/* the workers' profile build: a heavy column's record of the heavy trace (the time of every phase stamp goes there) */
+SLIP_DEV int32_t *slip_prof_heavy(const SlipParams &P, const int k, const int nrows)
+{
+    int32_t *h = P.dbg + slip_dbg_heavy(P.n) + 32 * (int64_t)(k & 63);
+    for (int q_ = 0; q_ < 32; q_++) h[q_] = 0;
+    h[31] = k; h[30] = nrows; h[29] = (int32_t) slip_realtime();
+    return h;
+}
+/* ... and the commit of column k by its worker (one thread): time line 2, phase slot 18 (from the moment this worker learnt
+ * that column k-1 was committed to its own commit), the column trace, the seen clock and (early commits) the commit-chain words */
+SLIP_DEV void slip_prof_commit(const SlipParams &P, const int k, const int early, const int narith, const int nrows,
+                               const unsigned long long t_last, const unsigned long long tr_sweep, const unsigned long long tr_t2,
+                               const unsigned long long t_seen, unsigned long long *prof, const int32_t *trs, const unsigned long long trp)
+{
+    SLIP_TL(true, k, 2);
+    if (t_last) prof[18] += slip_clock() - t_last;
+    int32_t *tr = P.dbg + slip_dbg_trace(P.n) + 8 * (int64_t) k; const unsigned long long nowc = slip_clock();
+    tr[0] = t_last ? (int32_t)(nowc - t_last) : -1; tr[1] = early; tr[2] = narith; tr[3] = nrows;
+    tr[4] = (int32_t) tr_sweep; tr[5] = (int32_t)(nowc - tr_t2); tr[7] = P.worker;
+    tr[6] = (int32_t) slip_realtime(); P.dbg[slip_dbg_seen(P.n) + k] = (int32_t) t_seen;
+    if (trs) {
+        int32_t *ch = P.dbg + slip_dbg_chain(P.n) + 8 * (int64_t) k;
+        for (int q_ = 0; q_ < 8; q_++) ch[q_] = trs[q_];
+        ch[7] = (int32_t)(nowc - trp);                                  /* 7b: drain */
+    }
+}
+#endif
 
 /* Wait until the commit frontier reaches `need` (need <= k).  Called by all threads; returns the frontier, or -1 when
  * column k can never commit (an earlier column stopped the factorisation, or a wait timed out).  once: one look only
@@ -399,9 +416,7 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
         if (jn < 0) {
             if (!GATED || Fl >= k) break;        /* the sweep is complete */
             /* wait for the frontier to move; the rows of the pattern that became pivotal are row_perm[c], c in [Fl, Fn) */
-#ifdef SLIP_PROFILING
-            const unsigned long long tw0_ = slip_clock();
-#endif
+            SLIP_PROF_W(const unsigned long long tw0_ = slip_clock());
             int Fn;
             /* still dry: the exported package holds for every pivot below the frontier this worker knows */
             if (GATED && pp_fresh && tid == 0 && sv[SV_PKGX]) slip_st_u32(P.pkg.at() + (int64_t)(k % P.nworkers) * SLIP_PKG_WORDS + SLIP_PKG_STAMP, (uint32_t) Fl);
@@ -412,9 +427,7 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
                     if (Fn >= 0 && Fn <= Fl) {       /* nothing to do but wait: classify the rows and list the pivot candidates meanwhile */
                         slip_prepass(P, k, tag, lds, Fl, b0);
                         pp_fresh = 1;
-#ifdef SLIP_EMU_TRACE
-                        if (tid == 0) fprintf(stderr, "worker: col %d prepass valid %d ncand %d nonS %d nrows %d full %d committer %d\n", k, (int) sv[SV_PP], (int) sv[SV_PP + 1], (int) sv[SV_PP + 12], (int) sv[SV_NROWS], (int) sv[SV_PPF], P.committer);
-#endif
+                        SLIP_TRACE("worker: col %d prepass valid %d ncand %d nonS %d nrows %d full %d committer %d\n", k, (int) sv[SV_PP], (int) sv[SV_PP + 1], (int) sv[SV_PP + 12], (int) sv[SV_NROWS], (int) sv[SV_PPF], P.committer);
                         Fn = -2;
                     }
                 }
@@ -436,18 +449,14 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
                         if (k - Fl <= SLIP_K1_NEAR) {
                             if (tid == 0) { sv[SV_PKGF] = sv[SV_PPFL]; if (sv[SV_PKGVER]) slip_agent_add_u64(&st->c_retract, 1ull << 32); }
                             slip_export_full(P, k, lds, sv[SV_PPFL], Fl);
-#ifdef SLIP_PROFILING
-                            if (tid == 0) P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 1] = (int32_t) slip_realtime();  /* time line 1: package exported */
-#endif
+                            SLIP_TL(tid == 0, k, 1);                 /* time line 1: package exported */
                             if (cur_io) { *cur_io = cur; return 2; }
                         }
                     } else if (can_pkg && sv[SV_PP] && !sv[SV_PP + 12] && sv[SV_NROWS] <= SLIP_PKG_NROWMAX && sv[SV_PP + 1] <= SLIP_PKG_CANDS) {
                         /* a column whose candidates are all one-limb values is handed to the committer */
                         if (tid == 0) { sv[SV_PKGF] = sv[SV_PPFL]; if (sv[SV_PKGVER]) slip_agent_add_u64(&st->c_retract, 1ull << 32); }
                         slip_export_package(P, k, lds, sv[SV_PPFL], Fl);
-#ifdef SLIP_PROFILING
-                        if (tid == 0) P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 1] = (int32_t) slip_realtime();  /* time line 1: package exported */
-#endif
+                        SLIP_TL(tid == 0, k, 1);                     /* time line 1: package exported */
                     }
                 }
             }
@@ -456,9 +465,7 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
                 Fn = slip_wait_frontier(st, lds, Fl + 1, k, 0, &P);
                 if (Fn <= -2) slip_farm_help(P, st, lds, -Fn - 2, b0, b1, b2);
             }
-#ifdef SLIP_PROFILING
-            *t_last = slip_clock(); t_wait[0] += *t_last - tw0_; t_wait[2] = slip_realtime();
-#endif
+            SLIP_PROF_W(*t_last = slip_clock(); t_wait[0] += *t_last - tw0_; t_wait[2] = slip_realtime());
             if (Fn < 0) return 1;
             const int Fseen = Fn, prow = sv[SV_TMP3];       /* the frontier word carried row_perm[Fseen-1] */
             if (Fn > k) Fn = k;
@@ -525,13 +532,9 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
         }
         if (GATED && jn >= sv[SV_F2]) {
             /* the source is committed but its L column may still be on its way (stage 2 of column jn) */
-#ifdef SLIP_PROFILING
-            const unsigned long long tw0_ = slip_clock();
-#endif
+            SLIP_PROF_W(const unsigned long long tw0_ = slip_clock());
             const int f2 = slip_wait_ready(P, st, lds, jn + 1);
-#ifdef SLIP_PROFILING
-            t_wait[1] += slip_clock() - tw0_;
-#endif
+            SLIP_PROF_W(t_wait[1] += slip_clock() - tw0_);
             if (f2 < 0) return 1;
             if (tid == 0) sv[SV_F2] = f2;
             slip_block_sync();
@@ -785,13 +788,9 @@ SLIP_DEV void slip_takeover_full(const SlipParams &P, const int k, const int tag
         slip_atomic_or_u32(&bm[pos >> 5], 1u << (pos & 31));
     }
     if (tid == 0) sv[SV_NROWS] = nnew;
-#if defined(SLIP_EMULATE) && defined(SLIP_EMU_TRACE)
-    if (tid == 0) {
-        fprintf(stderr, "takeover col %d: stamp %d nold %d nU %d nfin %d:", k, (int) sv[SV_PKGF], nold, nU, nfin);
-        for (int t = 0; t < nnew; t++) fprintf(stderr, " %s%u@%u", t < nU ? "U" : "", t_row[t], t_pos[t]);
-        fprintf(stderr, "\n");
-    }
-#endif
+    SLIP_TRACE("takeover col %d: stamp %d nold %d nU %d nfin %d:", k, (int) sv[SV_PKGF], nold, nU, nfin);
+    for (int t = 0; t < nnew; t++) SLIP_TRACE(" %s%u@%u", t < nU ? "U" : "", t_row[t], t_pos[t]);
+    SLIP_TRACE("\n");
     slip_block_sync();
 }
 
@@ -819,9 +818,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     unsigned long long c_read = 0, c_upd = 0, c_src = 0, c_str = 0, c_mac = 0;
     SLIP_STAMP_INIT();
 
-#ifdef SLIP_PROFILING
-    if (tid == 0) P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k] = (int32_t) slip_realtime();              /* time line 0: the column starts */
-#endif
+    SLIP_TL(tid == 0, k, 0);                                                                         /* time line 0: the column starts */
     /* ---- phase 0: clear the pattern bitmap, take a snapshot of the commit frontier ---- */
     for (int w = tid; w < P.bm_words; w += T) bm[w] = 0;
     if (tid == 0) {
@@ -866,9 +863,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
 
     /* ---- phase 2: ascending sweep over the pivotal part of the pattern, ahead of the frontier ---- */
     unsigned long long t_wait_[3] = {0, 0, 0}, t_last_ = 0;
-#ifdef SLIP_PROFILING
-    int32_t trs_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long trp_ = 0;
-#endif
+    SLIP_PROF_W(int32_t trs_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long trp_ = 0);
     int full_adopt = 0;
     {
         int sweep_at = -1;
@@ -878,9 +873,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             if (sr != 2) break;
             /* parked on a full package: the chain engine commits the column from it, or sends it back */
             const int v = slip_wait_verdict(P, st, lds, k, b0, b1, b2);
-#ifdef SLIP_PROFILING
-            if (tid == 0) P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 3] = (int32_t) slip_realtime();      /* time line 3: verdict seen */
-#endif
+            SLIP_TL(tid == 0, k, 3);                                                                 /* time line 3: verdict seen */
             if (v < 0) return SLIPDEV_ABORTED;
             if (v == 1) { full_adopt = 1; break; }
             if (tid == 0) {
@@ -897,12 +890,11 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     slip_block_sync();
     if (sv[SV_ERR]) { if (sv[SV_ERR] >= 6 && sv[SV_ERR] != SLIPDEV_ABORTED) SLIP_SITE(11, sv[SV_ERR], 0); return sv[SV_ERR] >= 6 ? sv[SV_ERR] : SLIPDEV_GROW_X; }
     SLIP_STAMP(1);
-#ifdef SLIP_PROFILING
-    trp_ = t_last_ ? t_last_ : slip_clock(); SLIP_TR(0);        /* 0: sweep tail */
-    /* slot 1: the sweep's own work; 16/17: waiting for the commit / ready frontier; 19: columns counted */
-    if (tid == 0) { prof_[1] -= t_wait_[0] + t_wait_[1]; prof_[16] += t_wait_[0]; prof_[17] += t_wait_[1]; prof_[19] += 1;
-                    if (t_last_) prof_[20] += t_prev_ - t_last_; }      /* 20: sweep work after the last frontier wait (on the commit chain) */
-#endif
+    SLIP_PROF_W(trp_ = t_last_ ? t_last_ : slip_clock(); SLIP_TR(0));     /* 0: sweep tail */
+    /* slot 1: the sweep's own work; 16/17: waiting for the commit / ready frontier; 19: columns counted;
+     * 20: sweep work after the last frontier wait (on the commit chain) */
+    SLIP_PROF_W(if (tid == 0) { prof_[1] -= t_wait_[0] + t_wait_[1]; prof_[16] += t_wait_[0]; prof_[17] += t_wait_[1]; prof_[19] += 1;
+                                if (t_last_) prof_[20] += t_prev_ - t_last_; });
     /* from here on F == k: columns 0..k-1 are committed, pinv / row_perm are those of the reference at column k */
 
     /* ---- phase 3: snapshot of the rows' positions and states.  F == k, so pinv is the reference's at column k; once
@@ -923,21 +915,15 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     /* a column whose package the committer holds: wait for the verdict (the outcome word of the package: this worker's
      * own line, not the frontier) */
     int adopted = 0;
-#ifdef SLIP_PROFILING
-    if (tid == 0) P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 5] = (int32_t) slip_realtime();          /* time line 5: the sweep has seen F >= k */
-#endif
-#ifdef SLIP_PROFILING
+    SLIP_TL(tid == 0, k, 5);                                                                         /* time line 5: the sweep has seen F >= k */
     /* a heavy column: the wall-clock time of every phase stamp (tools/phase_probe.py prints them) */
-    if (nrows > 400 && tid == 0) { hstamp_ = P.dbg + 24 * (int64_t) P.n + 32 * (int64_t)(k & 63); for (int q_ = 0; q_ < 32; q_++) hstamp_[q_] = 0; hstamp_[31] = k; hstamp_[30] = nrows; hstamp_[29] = (int32_t) slip_realtime(); }
-#endif
+    SLIP_PROF_W(if (nrows > 400 && tid == 0) hstamp_ = slip_prof_heavy(P, k, nrows));
     const int packaged = !full_adopt && P.committer && try_early && sv[SV_PKGX];
     slip_block_sync();                                   /* (thread 0 clears the flag below) */
     if (full_adopt) adopted = 1;
     if (packaged) {
         const int v = slip_wait_verdict(P, st, lds, k, b0, b1, b2);
-#ifdef SLIP_PROFILING
-        if (tid == 0) P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 3] = (int32_t) slip_realtime();      /* time line 3: verdict seen */
-#endif
+        SLIP_TL(tid == 0, k, 3);                                                                     /* time line 3: verdict seen */
         if (v < 0) return SLIPDEV_ABORTED;
         adopted = v;
     }
@@ -976,9 +962,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     dig_t *Ms = SCR_LDS ? lds + SLIP_LDS_BITMAP + (BM_LDS ? P.bm_words : 0) + nw * 3 * wcap : (dig_t *) 0;
     int pc_col = 0;
     int early = 0, e_pivrow = -1, e_pivpos = -1;
-#ifdef SLIP_PROFILING
-    unsigned long long tr_t2_ = slip_clock(), tr_sweep_ = t_last_ ? tr_t2_ - t_last_ : 0;
-#endif
+    SLIP_PROF_W(unsigned long long tr_t2_ = slip_clock(), tr_sweep_ = t_last_ ? tr_t2_ - t_last_ : 0);
     /* where the digits of a row are: its x row (private), or (rows multiplied straight into L: h == -2) the slab (shared) */
     auto row_direct = [&](int r) -> int { return P.xrow[r].h == -2; };
     auto row_digits = [&](int r) -> const dig_t * {
@@ -1122,18 +1106,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
                 slip_vm_drain();                                  /* the digits (all lanes) and the records (lane 0) have left */
                 if (lane == 0) {
                     slip_st_frontier(st, k + 1, e_pivrow);
-#ifdef SLIP_PROFILING
-                    P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 2] = (int32_t) slip_realtime();      /* time line 2: committed (by its worker) */
-                    if (t_last_) prof_[18] += slip_clock() - t_last_;
-                    {
-                        int32_t *tr = P.dbg + 8 * (int64_t) k; const unsigned long long nowc = slip_clock();
-                        tr[0] = t_last_ ? (int32_t)(nowc - t_last_) : -1; tr[1] = 1; tr[2] = A.narith; tr[3] = nrows;
-                        tr[4] = (int32_t) tr_sweep_; tr[5] = (int32_t)(nowc - tr_t2_); tr[7] = P.worker;
-                        tr[6] = (int32_t) slip_realtime(); P.dbg[8 * (int64_t) P.n + k] = (int32_t) t_wait_[2];
-                        for (int q_ = 0; q_ < 8; q_++) P.dbg[9 * (int64_t) P.n + 8 * (int64_t) k + q_] = trs_[q_];
-                        P.dbg[9 * (int64_t) P.n + 8 * (int64_t) k + 7] = (int32_t)(nowc - trp_) + trs_[7] * 0;     /* 7b: drain */
-                    }
-#endif
+                    SLIP_PROF_W(slip_prof_commit(P, k, 1, A.narith, nrows, t_last_, tr_sweep_, tr_t2_, t_wait_[2], prof_, trs_, trp_));
                     /* from now on the pivot row lives in the slab like a class-A row */
                     if (!pdirect) {
                         SlipRow nr = pxr; nr.h = -2; P.xrow[e_pivrow] = nr;
@@ -1217,12 +1190,10 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             if (Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) ok = 0;
             if (Unz_ + (int) nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) ok = 0;
             if (P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ok = 0;
-#ifdef SLIP_PROFILING
-            if (lane == 0) P.dbg[17 * (int64_t) P.n + k] |= 0x100 | (ok ? 0x200 : 0) | ((lm > 2 && !A_ok && nS > 0) ? 0x400 : 0)
+            SLIP_PROF_W(if (lane == 0) P.dbg[slip_dbg_flags(P.n) + k] |= 0x100 | (ok ? 0x200 : 0) | ((lm > 2 && !A_ok && nS > 0) ? 0x400 : 0)
                 | ((Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) ? 0x800 : 0)
                 | ((Unz_ + (int) nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) ? 0x1000 : 0)
-                | ((P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ? 0x2000 : 0);
-#endif
+                | ((P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ? 0x2000 : 0));
             const int diag_cand = (scheme == 1 || scheme == 3 || scheme == 4) && pc_col >= k && P.xrow[col].tag == tag && P.xrow[col].len != 0;
             const int slotw = (lm + 5) & ~1;
             const int nstage = (3 * SLIP_PAT_CAP) / slotw < 30 ? (3 * SLIP_PAT_CAP) / slotw : 30;
@@ -1292,9 +1263,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
                 if (lane == 0) { sv[SV_EST] = ok ? SLIPDEV_INTERNAL : -1; if (ok && !st->dbg_who) { st->dbg_who = 110; st->dbg_k = k; st->dbg_a = sv[SV_ERR]; } }      /* the bounds said this could not happen / the full pass */
             }
             if (lane == 0 && ok && !sv[SV_EST]) slip_agent_add_u64(&st->c_short, 1ull);
-#ifdef SLIP_PROFILING
-            if (lane == 0 && ok) { prof_[23] += 1; prof_[15] += (unsigned long long)(ncA + ncB); }
-#endif
+            SLIP_PROF_W(if (lane == 0 && ok) { prof_[23] += 1; prof_[15] += (unsigned long long)(ncA + ncB); });
         } else {
             /* the position snapshot (pinv as the reference has it at column k) by the other waves, before the swap */
             for (int t = tid - SLIP_WAVE; t < nrows; t += T - SLIP_WAVE) {
@@ -1414,10 +1383,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     slip_block_sync();
     SLIP_TR(2);                                              /* 2: rho staging + barrier */
     pc_col = sv[SV_TMP3];
-#ifdef SLIP_PROFILING
-    tr_t2_ = slip_clock();
-    tr_sweep_ = t_last_ ? tr_t2_ - t_last_ : 0;              /* sweep tail + position snapshot */
-#endif
+    SLIP_PROF_W(tr_t2_ = slip_clock(); tr_sweep_ = t_last_ ? tr_t2_ - t_last_ : 0);     /* sweep tail + position snapshot */
     SLIP_STAMP(2);
 
     /* ---- early commit: choose and publish the pivot BEFORE the column's bulk arithmetic.
@@ -1470,12 +1436,10 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
         if (Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) ok = 0;
         if (Unz_ + (int) nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) ok = 0;
         if (P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ok = 0;  /* the window may end here: decide on exact values */
-#ifdef SLIP_PROFILING
-        if (tid == 0) P.dbg[17 * (int64_t) P.n + k] |= 0x4000 | (ok ? 0x8000 : 0) | (bad_all ? 0x400 : 0)
+        SLIP_PROF_W(if (tid == 0) P.dbg[slip_dbg_flags(P.n) + k] |= 0x4000 | (ok ? 0x8000 : 0) | (bad_all ? 0x400 : 0)
             | ((Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) ? 0x800 : 0)
             | ((Unz_ + (int) nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) ? 0x1000 : 0)
-            | ((P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ? 0x2000 : 0);
-#endif
+            | ((P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ? 0x2000 : 0));
         const int diag_cand = (scheme == 1 || scheme == 3 || scheme == 4) && pc_col >= k && P.xrow[col].tag == tag && P.xrow[col].len != 0;
         /* lists in the work area: class-B candidates (rows), all candidates (table indices), class-A candidates (5-word records) */
         uint32_t *wlB = work, *cl = work + SLIP_CAND_CAP, *wlA = work + 2 * SLIP_CAND_CAP;
@@ -1543,9 +1507,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
                 const CommitArgs ca = { ncand, diag_cand, nA, nLc, ncA + ncB, slotw, 0, nUc_all, U_l, Lb_total, Lnz_, Lnl_, Unz_, Unl_, cl };
                 search_publish(ca);
             }
-#ifdef SLIP_PROFILING
-            if (tid == 0) { prof_[23] += 1; prof_[15] += (unsigned long long)(ncA + ncB); }   /* early commits; their candidates that needed arithmetic */
-#endif
+            SLIP_PROF_W(if (tid == 0) { prof_[23] += 1; prof_[15] += (unsigned long long)(ncA + ncB); });   /* early commits; their candidates that needed arithmetic */
             slip_block_sync();
             return sv[SV_EST];
         }
@@ -1569,7 +1531,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     uint32_t *diroff = lds + SLIP_LDS_DIROFF;
     auto row_at = [&](int t) -> int { return npat <= SLIP_PAT_CAP ? rowl[t] : P.srow[t]; };
     slip_block_sync();
-    if (npat != nrows) { SLIP_SITE(2, npat, nrows | (full_adopt << 16) | (adopted << 17) | (early << 18)); SLIP_WHY("col %d: npat %d != nrows %d (early %d full %d)\n", k, npat, nrows, early, full_adopt); return SLIPDEV_INTERNAL; }      /* every discovered row has exactly one position */
+    if (npat != nrows) { SLIP_SITE(2, npat, nrows | (full_adopt << 16) | (adopted << 17) | (early << 18)); SLIP_TRACE("col %d: npat %d != nrows %d (early %d full %d)\n", k, npat, nrows, early, full_adopt); return SLIPDEV_INTERNAL; }      /* every discovered row has exactly one position */
     for (int t = tid; t < nrows; t += T) {
         const int r = small ? (int) f_row[t] : P.rlist[t];
         const int pos = small ? (int) f_pos[t] : P.rpos[t];
@@ -1695,7 +1657,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             slip_block_sync();
         }
     }
-    if (sv[SV_ERR]) { if (early || sv[SV_ERR] >= 6) SLIP_SITE(3, sv[SV_ERR], early); SLIP_WHY("col %d: error %d in the history phase (early %d)\n", k, (int) sv[SV_ERR], early); return (early || sv[SV_ERR] >= 6) ? SLIPDEV_INTERNAL : SLIPDEV_GROW_X; }    /* after an early commit nothing may fail */
+    if (sv[SV_ERR]) { if (early || sv[SV_ERR] >= 6) SLIP_SITE(3, sv[SV_ERR], early); SLIP_TRACE("col %d: error %d in the history phase (early %d)\n", k, (int) sv[SV_ERR], early); return (early || sv[SV_ERR] >= 6) ? SLIPDEV_INTERNAL : SLIPDEV_GROW_X; }    /* after an early commit nothing may fail */
     SLIP_STAMP(3);
 
     /* ---- phase 5: column-window cap, then the pivot search ---- */
@@ -1755,7 +1717,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
         for (int t = tid; t < nL; t += T) if (ent_row(nU + t) == e_pivrow) sv[SV_TMP] = t;
         slip_block_sync();
         best = sv[SV_TMP];
-        if (best < 0) { SLIP_SITE(4, e_pivrow, nL); SLIP_WHY("col %d: pivot row %d not in the L part\n", k, e_pivrow); return SLIPDEV_INTERNAL; }
+        if (best < 0) { SLIP_SITE(4, e_pivrow, nL); SLIP_TRACE("col %d: pivot row %d not in the L part\n", k, e_pivrow); return SLIPDEV_INTERNAL; }
     } else if (kind != 2 && maxdig < (1 << 18)) {
         /* one pass: (bit length, leading 40 bits) packed into one key; the candidates that share the best key are
          * compared exactly, ties towards the earlier pattern position (slip_get_smallest_pivot.c:79) */
@@ -1881,11 +1843,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             } else {
                 const int64_t at = Lnz + (e - nUe);
                 const int64_t off = direct ? doff : Lnl + (int64_t)(lalloc + baseL + el);
-#ifdef SLIP_BULK_SC1
-                if (at < P.Lcap_nz) { slip_st_i32(&P.Li[at], r); SlipEnt en; en.len = xl; en.bits = xb; en.off = off; slip_st_ent(&P.Le[at], en); }
-#else
                 if (at < P.Lcap_nz) { P.Li[at] = r; SlipEnt en; en.len = xl; en.bits = xb; en.off = off; P.Le[at] = en; }   /* plain: published by the release before Lready[k] */
-#endif
                 if (use_tab && !direct) tab[3 * SLIP_TAB_CAP + pt] = (uint32_t)(off - Lnl);     /* copy destination, flag bit clear */
             }
         }
@@ -1895,7 +1853,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     const uint64_t totLexact = baseL + dirL;
     if (Unz + nUe > P.Ucap_nz || Unl + (int64_t) totU > P.Ucap_nl) { if (early) SLIP_SITE(5, nUe, totU); return early ? SLIPDEV_INTERNAL : SLIPDEV_GROW_U; }
     if (Lnz + nL > P.Lcap_nz || Lnl + (int64_t) totL > P.Lcap_nl) { if (early) SLIP_SITE(6, nL, totL); return early ? SLIPDEV_INTERNAL : SLIPDEV_GROW_L; }
-    if (early && (Lnl + (int64_t) totL > slip_ld_i64(&P.Lo[k + 1]) || Unl + (int64_t) totU != slip_ld_i64(&P.Uo[k + 1]))) { SLIP_SITE(7 + full_adopt, (Lnl + (int64_t) totL) - slip_ld_i64(&P.Lo[k + 1]), (Unl + (int64_t) totU) - slip_ld_i64(&P.Uo[k + 1])); SLIP_WHY("col %d: bounds: L %lld + %lld vs %lld, U %lld + %lld vs %lld (full %d)\n", k, (long long) Lnl, (long long) totL, (long long) slip_ld_i64(&P.Lo[k + 1]), (long long) Unl, (long long) totU, (long long) slip_ld_i64(&P.Uo[k + 1]), full_adopt); return SLIPDEV_INTERNAL; }   /* the published bounds hold */
+    if (early && (Lnl + (int64_t) totL > slip_ld_i64(&P.Lo[k + 1]) || Unl + (int64_t) totU != slip_ld_i64(&P.Uo[k + 1]))) { SLIP_SITE(7 + full_adopt, (Lnl + (int64_t) totL) - slip_ld_i64(&P.Lo[k + 1]), (Unl + (int64_t) totU) - slip_ld_i64(&P.Uo[k + 1])); SLIP_TRACE("col %d: bounds: L %lld + %lld vs %lld, U %lld + %lld vs %lld (full %d)\n", k, (long long) Lnl, (long long) totL, (long long) slip_ld_i64(&P.Lo[k + 1]), (long long) Unl, (long long) totU, (long long) slip_ld_i64(&P.Uo[k + 1]), full_adopt); return SLIPDEV_INTERNAL; }   /* the published bounds hold */
     /* the pivot's record fields, read before the permutation swap below changes what row_perm answers */
     const int32_t plen = ent_len(pividx);
     const int pbits = ent_bits(pividx);
@@ -1930,17 +1888,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             slip_st_i64(&P.Uo[k + 1], Unl + (int64_t) totU); slip_st_i64(&P.Lo[k + 1], Lnl + (int64_t) totL);
             slip_vm_drain();
             slip_st_frontier(st, k + 1, pivrow);
-#ifdef SLIP_PROFILING
-            P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 2] = (int32_t) slip_realtime();              /* time line 2: committed (by its worker) */
-            /* slot 18: from the moment this worker learnt that column k-1 was committed to its own commit */
-            if (t_last_) prof_[18] += slip_clock() - t_last_;
-            {
-                int32_t *tr = P.dbg + 8 * (int64_t) k; const unsigned long long nowc = slip_clock();
-                tr[0] = t_last_ ? (int32_t)(nowc - t_last_) : -1; tr[1] = 0; tr[2] = 0; tr[3] = nrows;
-                tr[4] = (int32_t) tr_sweep_; tr[5] = (int32_t)(nowc - tr_t2_); tr[7] = P.worker;
-                        tr[6] = (int32_t) slip_realtime(); P.dbg[8 * (int64_t) P.n + k] = (int32_t) t_wait_[2];
-            }
-#endif
+            SLIP_PROF_W(slip_prof_commit(P, k, 0, 0, nrows, t_last_, tr_sweep_, tr_t2_, t_wait_[2], prof_, (const int32_t *) 0, 0));
         }
     }
     SLIP_STAMP(6);
@@ -1990,11 +1938,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
         }
         const int lw = (slip_abs(xl) + 1) & ~1;
         if (isU) { for (int c = lane; c < lw; c += SLIP_WAVE) dst[c] = src_shared ? slip_ld_u32(srcx + c) : srcx[c]; }
-#ifdef SLIP_BULK_SC1
-        else     { for (int c = lane; c < lw; c += SLIP_WAVE) slip_st_u32(dst + c, srcx[c]); }
-#else
         else     { for (int c = lane; c < lw; c += SLIP_WAVE) dst[c] = srcx[c]; }
-#endif
     }
     }
     slip_vm_drain();
@@ -2025,10 +1969,8 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             if (t_mac) slip_agent_add_u64(&st->c_macs, t_mac);
         }
     }
-#ifdef SLIP_PROFILING
-    if (tid == 0) P.dbg[18 * (int64_t) P.n + 6 * (int64_t) k + 4] = (int32_t) slip_realtime();          /* time line 4: the column ends */
-    if (tid == 0) P.dbg[17 * (int64_t) P.n + k] |= (packaged ? 1 : 0) | (adopted ? 2 : 0) | (fastc ? 4 : 0) | (early ? 8 : 0) | (sv[SV_PKGVER] << 4) | (nrows << 16);
-#endif
+    SLIP_TL(tid == 0, k, 4);                                                                         /* time line 4: the column ends */
+    SLIP_PROF_W(if (tid == 0) P.dbg[slip_dbg_flags(P.n) + k] |= (packaged ? 1 : 0) | (adopted ? 2 : 0) | (fastc ? 4 : 0) | (early ? 8 : 0) | (sv[SV_PKGVER] << 4) | (nrows << 16));
     SLIP_STAMP(7);
     SLIP_STAMP_FLUSH(st);
     slip_block_sync();
@@ -2083,7 +2025,7 @@ SLIP_DEV int slip_solve_rhs(const SlipParams &P, SlipState *st, const SlipSolveA
     dig_t *b1 = b0 + wcap, *b2 = b1 + wcap;
     unsigned long long c_read = 0, c_upd = 0, c_src = 0, c_str = 0, c_mac = 0;
 
-    if (tid == 0 && c == 0) P.dbg[24 * (int64_t) P.n + 3072 + 0] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
+    if (tid == 0 && c == 0) P.dbg[slip_dbg_solve(P.n) + 0] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
     /* b2[pinv[i]] = b[i]  (SLIP_LU_solve.c:68-75): rows keep their ids, the bitmap is indexed by position */
     for (int w = tid; w < P.bm_words; w += T) bm[w] = 0;
     if (tid == 0) { sv[SV_ERR] = 0; sv[SV_CNT0] = 0; sv[SV_CNT0 + 1] = 0; sv[SV_CNT0 + 2] = 0; sv[SV_NROWS] = 0; sv[SV_F] = n; }
@@ -2108,14 +2050,14 @@ SLIP_DEV int slip_solve_rhs(const SlipParams &P, SlipState *st, const SlipSolveA
     slip_block_sync();
     if (sv[SV_ERR]) return SLIPDEV_GROW_X;
 
-    if (tid == 0 && c == 0) P.dbg[24 * (int64_t) P.n + 3072 + 1] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
+    if (tid == 0 && c == 0) P.dbg[slip_dbg_solve(P.n) + 1] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
     /* forward substitution = the sweep over ALL pivot positions (slip_forward_sub.c:61-158) */
     unsigned long long tw_[3] = {0, 0, 0}, tl_ = 0;
     slip_sweep<FAST, false>(P, st, n, tag, lds, bm, b0, b1, b2, c_read, c_upd, c_src, c_str, c_mac, tw_, &tl_);
     slip_block_sync();
     if (sv[SV_ERR]) return sv[SV_ERR] >= 6 ? sv[SV_ERR] : SLIPDEV_GROW_X;
 
-    if (tid == 0 && c == 0) P.dbg[24 * (int64_t) P.n + 3072 + 2] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
+    if (tid == 0 && c == 0) P.dbg[slip_dbg_solve(P.n) + 2] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
     /* x <- x * det (slip_array_mul.c:19), det = rho[n-1] */
     int npat, nUdummy;
     slip_pattern(P, lds, bm, n, &npat, &nUdummy);
@@ -2158,7 +2100,7 @@ SLIP_DEV int slip_solve_rhs(const SlipParams &P, SlipState *st, const SlipSolveA
     }
     if (sv[SV_ERR]) return sv[SV_ERR] >= 6 ? sv[SV_ERR] : SLIPDEV_GROW_X;
 
-    if (tid == 0 && c == 0) P.dbg[24 * (int64_t) P.n + 3072 + 3] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
+    if (tid == 0 && c == 0) P.dbg[slip_dbg_solve(P.n) + 3] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
     /* back substitution (slip_back_sub.c:36-52): positions descending; x_j /= U_jj (= rho_j, the last entry
      * of U(:,j)), then x_i -= U_ij x_j for the rows above */
     {
@@ -2241,7 +2183,7 @@ SLIP_DEV int slip_solve_rhs(const SlipParams &P, SlipState *st, const SlipSolveA
     slip_block_sync();
     if (sv[SV_ERR]) return sv[SV_ERR] >= 6 ? sv[SV_ERR] : SLIPDEV_GROW_X;
 
-    if (tid == 0 && c == 0) P.dbg[24 * (int64_t) P.n + 3072 + 4] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
+    if (tid == 0 && c == 0) P.dbg[slip_dbg_solve(P.n) + 4] = (int32_t) slip_realtime();      /* solve time line (diagnostic words) */
     /* output: numerators in pivot-position order (the order SLIP_LU_solve returns before SLIP_permute_x); every
      * right-hand side owns a region of the output slab */
     {

@@ -32,9 +32,7 @@
 #ifndef SLIP_REF_LU_PIPE_COMMIT_H
 #define SLIP_REF_LU_PIPE_COMMIT_H
 
-#ifndef SLIP_CB
 #define SLIP_CB          8                  /* columns per batch */
-#endif
 #define SLIP_CB_RING     512                /* swaps and pivots the committer remembers (more than the columns in flight) */
 #define SLIP_CBW         640                /* one batch column in LDS: 32 header words, 96 candidate words, 512 row words */
 #define SLIP_CB_SLOTW    264                /* rho_j: a product of a one-limb value and a pivot of at most 256 digits, whole limbs */
@@ -212,6 +210,32 @@ SLIP_DEV int slip_tol_small(uint64_t tol_m, int te, uint64_t num, uint64_t den)
 struct SlipSmallPiv { uint64_t lo, inv; int ctz, sgn, small, bits; };
 
 /* the kernel body of the committer (block 0 of a launch with P.committer set) */
+#if SLIP_PROFILE == 2 && !defined(SLIP_EMULATE)
+/* the committer's profile build: calibration, in place -- what a dependent LDS read, a dependent VALU op and an s_memrealtime
+ * stamp cost HERE (shader cycles and 10 ns ticks), into slots 20..22 of the phase record (wave 0; misc: 64 LDS words) */
+SLIP_DEV void slip_prof_calibrate(uint32_t *misc, const int wave, const int lane, unsigned long long *tacc)
+{
+    unsigned long long cal_[4] = {0, 0, 0, 0};
+    if (wave == 0) {
+        for (int w = lane; w < 64; w += SLIP_WAVE) misc[w] = (uint32_t)((w * 37 + 11) & 63);
+        slip_wave_sync_lds();
+        uint32_t idx = (uint32_t) lane & 63u;
+        const unsigned long long c0 = slip_clock(), r0 = slip_realtime();
+        for (int r = 0; r < 256; r++) idx = misc[idx];
+        const unsigned long long c1 = slip_clock(), r1 = slip_realtime();
+        uint32_t acc = idx;
+        for (int r = 0; r < 1024; r++) acc = acc * 3u + 1u;
+        const unsigned long long c2 = slip_clock(), r2 = slip_realtime();
+        unsigned long long r3 = r2;
+        for (int r = 0; r < 64; r++) r3 += slip_realtime() & 1ull;
+        const unsigned long long c3 = slip_clock();
+        if (acc == 0x12345u) misc[0] = (uint32_t) r3;
+        cal_[0] = ((c1 - c0) << 32) | (r1 - r0); cal_[1] = ((c2 - c1) << 32) | (r2 - r1); cal_[2] = c3 - c2;
+    }
+    tacc[20] = cal_[0]; tacc[21] = cal_[1]; tacc[22] = cal_[2];
+}
+#endif
+
 template <bool FAST>
 SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
 {
@@ -267,32 +291,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
     if (mirror) for (int i = tid; i < P.n; i += T) { pinvm[i] = (uint16_t) slip_ld_i32(P.pinv.at(i)); slotm[i] = 0; }
     slip_block_sync();
     if (tid == 0) slip_agent_store_i32(&st->committer_up, 1);       /* from now on packages are answered */
-#ifdef SLIP_PROFILE_COMMIT
-    /* calibration, in place: what a dependent LDS read, a dependent VALU op and an s_memrealtime stamp cost HERE (shader
-     * cycles and 10 ns ticks) -- slots 20..23 of the phase record */
-    unsigned long long cal_[4] = {0, 0, 0, 0};
-    if (wave == 0) {
-        for (int w = lane; w < 64; w += SLIP_WAVE) misc[w] = (uint32_t)((w * 37 + 11) & 63);
-        slip_wave_sync_lds();
-        uint32_t idx = (uint32_t) lane & 63u;
-        const unsigned long long c0 = slip_clock(), r0 = slip_realtime();
-        for (int r = 0; r < 256; r++) idx = misc[idx];
-        const unsigned long long c1 = slip_clock(), r1 = slip_realtime();
-        uint32_t acc = idx;
-        for (int r = 0; r < 1024; r++) acc = acc * 3u + 1u;
-        const unsigned long long c2 = slip_clock(), r2 = slip_realtime();
-        unsigned long long r3 = r2;
-        for (int r = 0; r < 64; r++) r3 += slip_realtime() & 1ull;
-        const unsigned long long c3 = slip_clock();
-        if (acc == 0x12345u) misc[0] = (uint32_t) r3;
-        cal_[0] = ((c1 - c0) << 32) | (r1 - r0); cal_[1] = ((c2 - c1) << 32) | (r2 - r1); cal_[2] = c3 - c2;
-    }
-    unsigned long long tq_ = slip_realtime(), tacc_[24] = {0};
-    tacc_[20] = cal_[0]; tacc_[21] = cal_[1]; tacc_[22] = cal_[2];
-#define SLIP_CT(i) do { if (tid == 0) { const unsigned long long n_ = slip_realtime(); tacc_[i] += n_ - tq_; tq_ = n_; } } while (0)
-#else
-#define SLIP_CT(i) do { } while (0)
-#endif
+    SLIP_PROF_C(unsigned long long tacc_[24] = {0}; slip_prof_calibrate(misc, wave, lane, tacc_); unsigned long long tq_ = slip_realtime());
     for (;;) {
         /* (a) the next columns whose packages are there; a column committed by its worker moves the frontier instead */
         if (wave == 0) {
@@ -324,9 +323,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                         if (lo_c > kprev) { for (int i = lane; i < P.n; i += SLIP_WAVE) pinvm[i] = (uint16_t) slip_ld_i32(P.pinv.at(i)); }     /* fell behind the ring: start over from memory (every swap below kc has landed) */
                         else if (lane == 0) for (int c = kprev; c < kc; c++) {
                             const int s_ = c & (SLIP_CB_RING - 1);
-#if defined(SLIP_EMULATE) && defined(SLIP_EMU_TRACE)
-                            fprintf(stderr, "resync col %d: pivot row %u, row %u to pos %u (mirror had %d / %d)\n", c, ring_row[s_], ring_disp[s_], ring_opos[s_], (int) pinvm[ring_row[s_]], (int) pinvm[ring_disp[s_]]);
-#endif
+                            SLIP_TRACE_L0("resync col %d: pivot row %u, row %u to pos %u (mirror had %d / %d)\n", c, ring_row[s_], ring_disp[s_], ring_opos[s_], (int) pinvm[ring_row[s_]], (int) pinvm[ring_disp[s_]]);
                             pinvm[ring_row[s_]] = (uint16_t) c; pinvm[ring_disp[s_]] = (uint16_t) ring_opos[s_];
                         }
                     }
@@ -971,9 +968,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                     if (reject && lane == 0) slip_st_u32(mbx + SLIP_PKG_OUT + 1, (uint32_t) reject);      /* why it goes back (1: try again later) */
                 }
                 slip_wave_sync_lds();
-#if defined(SLIP_EMULATE) && defined(SLIP_EMU_TRACE)
-                if (lane == 0) fprintf(stderr, "committer: col %d kind %d reject %d pre %d (stamp0 %d nfull %d nrows %d nlate %d pr0 %d ring0 %d)\n", j, kindp, reject, (int) cb[18], stamp0, (int) cb[22], nrows, nlate, sv[C_PR0], sv[C_RING0]);
-#endif
+                SLIP_TRACE_L0("committer: col %d kind %d reject %d pre %d (stamp0 %d nfull %d nrows %d nlate %d pr0 %d ring0 %d)\n", j, kindp, reject, (int) cb[18], stamp0, (int) cb[22], nrows, nlate, sv[C_PR0], sv[C_RING0]);
                 if (reject) { rej = j; break; }
                 /* ---- the column is committed: what the next one needs stays in registers; the rings and the publish record in LDS ---- */
                 {
@@ -986,9 +981,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                     const int64_t nUnl = Unl_ + (int64_t)(U_l + plimbs), nLnl = Lnl_ + (int64_t) Lb_total;
                     M = pr; Lnz_ = nLnz; Lnl_ = nLnl; Unz_ = nUnz; Unl_ = nUnl;
                     if (lane == i) { bs_row = (uint32_t) e_pivrow; bs_disp = (uint32_t) intermed2; bs_opos = (uint32_t) e_pivpos; }
-#if defined(SLIP_EMULATE) && defined(SLIP_EMU_TRACE)
-                    if (lane == 0) fprintf(stderr, "commit col %d kind %d: pivot row %d from pos %d, row %d goes there\n", j, kindp, e_pivrow, e_pivpos, intermed2);
-#endif
+                    SLIP_TRACE_L0("commit col %d kind %d: pivot row %d from pos %d, row %d goes there\n", j, kindp, e_pivrow, e_pivpos, intermed2);
                     if (lane == 0) {
                         pring_put(j, pr);
                         ring_row[j & (SLIP_CB_RING - 1)] = (uint32_t) e_pivrow; ring_disp[j & (SLIP_CB_RING - 1)] = (uint32_t) intermed2;
@@ -1119,9 +1112,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
         if (wave == 0) {
             slip_vm_drain();
             if (lane < nbc) slip_st_u32(P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t)(pub + lane * SLIP_PUBW)[20] * SLIP_MBOX_WORDS + SLIP_PKG_OUT, (hver[lane] << 24) | (uint32_t)(kc + lane + 1));
-#ifdef SLIP_PROFILE_PHASES
-            if (lane < nbc) P.dbg[18 * (int64_t) P.n + 6 * (int64_t)(kc + lane) + 2] = (int32_t) slip_realtime();  /* time line 2: committed by the committer */
-#endif
+            SLIP_TL(lane < nbc, kc + lane, 2);   /* time line 2: committed by the committer */
             if (lane == 0) {
                 if (rej >= 0) {
                     const uint32_t rv = hver[rej - kc];
@@ -1137,9 +1128,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
             }
         }
         SLIP_CT(5);                                  /* 5: verdicts + frontier */
-#ifdef SLIP_PROFILE_COMMIT
-        if (tid == 0) { tacc_[6] += 1; tacc_[7] += (unsigned long long) nbc; tacc_[8] += rej >= 0; tacc_[9] += (unsigned long long) nb; }
-#endif
+        SLIP_PROF_C(if (tid == 0) { tacc_[6] += 1; tacc_[7] += (unsigned long long) nbc; tacc_[8] += rej >= 0; tacc_[9] += (unsigned long long) nb; });
         slip_block_sync();
     }
     /* the engine's share of the algorithmic counters: the sources it applied in place of the workers */
@@ -1151,9 +1140,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
         if (eacc[4]) slip_agent_add_u64(&st->c_macs, eacc[4]);
         if (eacc[5] || eacc[6]) slip_agent_add_u64(&st->c_eng, eacc[5] | (eacc[6] << 32));
     }
-#ifdef SLIP_PROFILE_COMMIT
-    if (tid == 0) for (int q = 0; q < 24; q++) st->prof[q] = tacc_[q];      /* (the workers' own slots are added on top: read the committer's with workers that do not stamp) */
-#endif
+    SLIP_PROF_C(if (tid == 0) for (int q = 0; q < 24; q++) st->prof[q] = tacc_[q]);      /* (the workers do not stamp in this build) */
 }
 
 #endif /* SLIP_REF_LU_PIPE_COMMIT_H */

@@ -189,7 +189,7 @@ slip_factor_kernel(SlipParams P, SlipState *st)
      * (P.quiet_neighbours; placement is read, never assumed: a worker that does not see the committer just works) */
     const uint32_t hwid = (uint32_t) __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = (uint32_t) __builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xFu;
     const uint32_t where = ((hwid >> 8) & 0xFFu) | (xcc << 8);          /* cu | sh | se | xcc */
-    if (threadIdx.x == 0 && blockIdx.x < 2048) P.dbg[24 * (int64_t) P.n + 2048 + blockIdx.x] = (int32_t)(where | 0x10000u);
+    if (threadIdx.x == 0 && blockIdx.x < 2048) P.dbg[slip_dbg_place(P.n) + blockIdx.x] = (int32_t)(where | 0x10000u);
     if (sP.committer && blockIdx.x == 0) {
         if (threadIdx.x == 0) slip_st_i32(&st->committer_where, (int32_t)(where | 0x10000u));
         slip_committer<FAST>(sP, st, slip_lds);
@@ -388,6 +388,12 @@ template <class T> static int dev_alloc(T **p, int64_t count)
     if (dev_malloc_bytes(&q, (size_t)(count > 0 ? count : 1) * sizeof(T))) return SLIP_HIP_OUT_OF_MEMORY;
     *p = (T *) q;
     return 0;
+}
+/* the debug buffer P.dbg (its regions: slip_dbg_* in ref_lu_pipe.h), zeroed */
+static int dbg_alloc(int32_t **dbg, int n)
+{
+    if (dev_alloc(dbg, slip_dbg_words(n))) return SLIP_HIP_OUT_OF_MEMORY;
+    return hipMemset(*dbg, 0, (size_t) slip_dbg_words(n) * sizeof(int32_t)) == hipSuccess ? 0 : SLIP_HIP_DEVICE_ERROR;
 }
 template <class T> static int dev_grow(T **p, int64_t old_count, int64_t new_count)
 {
@@ -827,9 +833,8 @@ extern "C" int slip_hip_factor_create(slip_hip_factor **out, int32_t n,
     A_(dev_alloc(&f->dAp, (int64_t) n + 1)); A_(dev_alloc(&f->dAi, onz)); A_(dev_alloc(&f->dAlen, onz));
     A_(dev_alloc(&f->dAoff, onz)); A_(dev_alloc(&f->dAlimbs, ol)); A_(dev_alloc(&f->dq, n));
     A_(dev_alloc(&P->pinv.p_, n)); A_(dev_alloc(&P->row_perm.p_, n));
-    A_(dev_alloc(&P->piv.p_, n)); A_(dev_alloc(&P->Lready.p_, n)); A_(dev_alloc(&P->dbg, 24 * (int64_t) n + 4096)); A_(dev_alloc(&P->sw_row.p_, n)); A_(dev_alloc(&P->sw_pos.p_, n));
+    A_(dev_alloc(&P->piv.p_, n)); A_(dev_alloc(&P->Lready.p_, n)); A_(dbg_alloc(&P->dbg, n)); A_(dev_alloc(&P->sw_row.p_, n)); A_(dev_alloc(&P->sw_pos.p_, n));
     A_(make_ident(f));
-    if (!rc && hipMemset(P->dbg, 0, ((size_t) n * 24 + 4096) * 4) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
     if (!rc && hipMemset(P->piv.p_, 0, (size_t) n * sizeof(SlipPiv)) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
     /* initial sizes: S->lnz/unz only size the first allocation in the reference too */
     P->Lcap_nz = opt.lnz_hint > 0 ? opt.lnz_hint : 4 * onz + n;
@@ -1087,11 +1092,10 @@ extern "C" int slip_hip_factor_from_factors(slip_hip_factor **out, int32_t n,
     int rc = 0;
 #define A_(call) do { if (!rc) rc = (call); } while (0)
     A_(dev_alloc(&P->pinv.p_, n)); A_(dev_alloc(&P->row_perm.p_, n));
-    A_(dev_alloc(&P->piv.p_, n)); A_(dev_alloc(&P->Lready.p_, n)); A_(dev_alloc(&P->dbg, 24 * (int64_t) n + 4096)); A_(dev_alloc(&P->sw_row.p_, n)); A_(dev_alloc(&P->sw_pos.p_, n));
+    A_(dev_alloc(&P->piv.p_, n)); A_(dev_alloc(&P->Lready.p_, n)); A_(dbg_alloc(&P->dbg, n)); A_(dev_alloc(&P->sw_row.p_, n)); A_(dev_alloc(&P->sw_pos.p_, n));
     A_(dev_alloc(&P->Lp, (int64_t) n + 1)); A_(dev_alloc(&P->Lo, (int64_t) n + 1)); A_(dev_alloc(&P->Li, lnz)); A_(dev_alloc(&P->Le, lnz)); A_(dev_alloc(&P->Llimbs, P->Lcap_nl));
     A_(dev_alloc(&P->Up, (int64_t) n + 1)); A_(dev_alloc(&P->Uo, (int64_t) n + 1)); A_(dev_alloc(&P->Ui, unz)); A_(dev_alloc(&P->Ue, unz)); A_(dev_alloc(&P->Ulimbs, P->Ucap_nl));
     A_(dev_alloc(&f->ds, 1));
-    if (!rc && hipMemset(P->dbg, 0, ((size_t) n * 24 + 4096) * 4) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
     if (!rc) rc = alloc_x(f, 2 * maxdig + 8, 0);
 #undef A_
 #define UP_(dst, src, bytes) do { if (!rc && (bytes) > 0 && hipMemcpy((void *)(dst), (src), (size_t)(bytes), hipMemcpyHostToDevice) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR; } while (0)
@@ -1490,7 +1494,7 @@ extern "C" int slip_hip_factor_rescale(slip_hip_factor *f, int32_t nscales, cons
     return rc;
 }
 
-/* diagnostic: per-phase shader cycles of the last run (zeros unless built with -DSLIP_PROFILE_PHASES) */
+/* diagnostic: per-phase shader cycles of the last run (zeros unless built with -DSLIP_PROFILE: csrc/Makefile, `make prof` / `make cprof`) */
 extern "C" int slip_hip_factor_phase_cycles(const slip_hip_factor *f, unsigned long long *out24)
 {
     if (!f || !out24) return SLIP_HIP_INCORRECT_INPUT;
@@ -1503,7 +1507,7 @@ extern "C" int slip_hip_factor_phase_cycles(const slip_hip_factor *f, unsigned l
 extern "C" int slip_hip_factor_heavy_trace(const slip_hip_factor *f, int32_t *out2048)
 {
     if (!f || !out2048) return SLIP_HIP_INCORRECT_INPUT;
-    CK(hipMemcpy(out2048, f->P.dbg + 24 * (int64_t) f->n, 2048 * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(out2048, f->P.dbg + slip_dbg_heavy(f->n), 2048 * 4, hipMemcpyDeviceToHost));
     return SLIP_HIP_OK;
 }
 
@@ -1512,21 +1516,24 @@ extern "C" int slip_hip_factor_heavy_trace(const slip_hip_factor *f, int32_t *ou
 extern "C" int slip_hip_factor_column_trace(const slip_hip_factor *f, int32_t *out, int32_t ncols)
 {
     if (!f || !out || ncols <= 0 || ncols > f->n) return SLIP_HIP_INCORRECT_INPUT;
-    CK(hipMemcpy(out, f->P.dbg, (size_t) ncols * 8 * 4, hipMemcpyDeviceToHost));
-    /* word 8: the 100 MHz chip clock when the column's worker saw its turn (kept behind the n trace records) */
-    CK(hipMemcpy(out + 8 * (int64_t) ncols, f->P.dbg + 8 * (int64_t) f->n, (size_t) ncols * 4, hipMemcpyDeviceToHost));
-    /* words 9..16: cycles of the sub-steps of the commit chain */
-    CK(hipMemcpy(out + 9 * (int64_t) ncols, f->P.dbg + 9 * (int64_t) f->n, (size_t) ncols * 8 * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(out + 17 * (int64_t) ncols, f->P.dbg + 17 * (int64_t) f->n, (size_t) ncols * 4, hipMemcpyDeviceToHost));      /* path flags */
-    CK(hipMemcpy(out + 18 * (int64_t) ncols, f->P.dbg + 18 * (int64_t) f->n, (size_t) ncols * 6 * 4, hipMemcpyDeviceToHost));  /* wall-clock time line, 6 words per column */
+    /* the regions of the debug buffer in their order, each cut to the first ncols columns: the trace records (8 words),
+     * the 100 MHz chip clock when the column's worker saw its turn (1), the cycles of the sub-steps of the commit chain (8),
+     * the path flags (1), the wall-clock time line (6) */
+    const int64_t n = f->n, nc = ncols;
+    const struct { int64_t at, words; } part[5] = { { slip_dbg_trace(n), 8 }, { slip_dbg_seen(n), 1 }, { slip_dbg_chain(n), 8 },
+                                                   { slip_dbg_flags(n), 1 }, { slip_dbg_timeline(n), 6 } };
+    for (int i = 0; i < 5; i++) {
+        CK(hipMemcpy(out, f->P.dbg + part[i].at, (size_t)(nc * part[i].words) * 4, hipMemcpyDeviceToHost));
+        out += nc * part[i].words;
+    }
 
     return SLIP_HIP_OK;
 }
 
-/* diagnostic: raw words of the device debug area (placement of the workgroups of the last launch at 24 n + 2048: cu | sh | se | xcc) */
+/* diagnostic: raw words of the device debug area (ref_lu_pipe.h: slip_dbg_*; e.g. the placement of the workgroups of the last launch: cu | sh | se | xcc) */
 extern "C" int slip_hip_factor_debug_words(const slip_hip_factor *f, int64_t offset, int32_t count, int32_t *out)
 {
-    if (!f || !out || offset < 0 || count <= 0 || offset + count > 24 * (int64_t) f->n + 4096) return SLIP_HIP_INCORRECT_INPUT;
+    if (!f || !out || offset < 0 || count <= 0 || offset + count > slip_dbg_words(f->n)) return SLIP_HIP_INCORRECT_INPUT;
     CK(hipMemcpy(out, f->P.dbg + offset, (size_t) count * 4, hipMemcpyDeviceToHost));
     return SLIP_HIP_OK;
 }

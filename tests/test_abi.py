@@ -61,3 +61,21 @@ def test_shared_arrays_cannot_be_dereferenced_plainly(tmp_path):
         bad = head + "int f(const SlipParams &P) { return (int) (%s); }\n" % expr
         src = tmp_path / "bad.cpp"; src.write_text(bad)
         assert subprocess.run(cmd + [str(src)], capture_output=True).returncode != 0, expr
+
+
+@pytest.mark.parametrize("variant", ["SLIP_PROFILE=1", "SLIP_PROFILE=2", "SLIP_EMU_TRACE"])
+def test_diagnostic_builds_compile(variant):
+    """the diagnostics builds of the kernel source stay compilable: the workers' and the committer's profile builds
+    (csrc/Makefile `prof` / `cprof`, hipcc for gfx950) and the emulator's trace build"""
+    import subprocess
+    csrc = os.path.join(ROOT, "slip_lu_amd", "csrc")
+    src = os.path.join(csrc, "slip_hip.hip")
+    if variant.startswith("SLIP_PROFILE"):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        if not os.path.exists(hipcc):
+            pytest.skip("hipcc not found")
+        cmd = [hipcc, "-fsyntax-only", "--offload-arch=gfx950", "-Wno-unused-value", "-I", csrc, "-D" + variant, src]
+    else:
+        cmd = ["g++", "-fsyntax-only", "-DSLIP_EMULATE", "-D" + variant, "-I", os.path.join(ROOT, "tests", "emu"), "-I", csrc, "-x", "c++", src]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-4000:]

@@ -9,7 +9,10 @@ start, exp, com, ver, end, swe, fl = a.T[:7]
 K = len(com)
 gap = np.diff(com, prepend=com[0])
 adopted = (fl & 2) != 0
-print(f"K {K}: first commit at {us(com[0]):.0f} us, last commit {us(com[-1]):.0f} us, last end {us(end.max()):.0f} us; committed by the committer {int(adopted.sum())}")
+print(f"K {K}: first commit at {us(com[0]):.0f} us, last commit {us(com[-1]):.0f} us, last end {us(end.max()):.0f} us; committed by the committer {int(adopted.sum())}"
+      + (f", the last of them at {us(com[adopted].max()):.0f} us" if adopted.any() else ""))
+bulk = end - swe
+print("longest bulks (sweep end -> column end): " + ", ".join(f"col {k} {us(bulk[k]):.0f} us" for k in np.argsort(-bulk)[:6]))
 edges = [0, 3, 6, 12, 25, 50, 100, 200, 400, 10 ** 9]
 for lo, hi in zip(edges[:-1], edges[1:]):
     m = (us(gap) >= lo) & (us(gap) < hi)

@@ -7,6 +7,15 @@
 - <pmc_*_dir>: output directories of two SEPARATE `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes
   -> <tag>_pmc_FETCH_SIZE.csv, <tag>_pmc_WRITE_SIZE.csv (per launch of the factor kernel) and <tag>_pmc_summary.json
 Counter units are KB (MI355X_MICROARCH.md, HBM / rocprofv3 section).
+
+The measurement these files come from, on the GPU machine from the repository root (O = an output directory, TAG = vN;
+`make -C slip_lu_amd/csrc cprof` first; every step separately, the PMC passes without any tracing):
+  python3 tools/commit_profile.py $O/profiles/${TAG}_commit.json
+  python3 bench.py --steps 20 --warmup 3 > $O/profiles/${TAG}_bench_full.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_prof.json
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
+  python3 tools/profile_summary.py $TAG $O/stats $O/pmc_fetch $O/pmc_write $O/bench_prof.json $O/profiles
 """
 import csv
 import glob
