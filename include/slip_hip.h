@@ -15,6 +15,8 @@
  *        SLIP_LU/Include/SLIP_LU.h:212-223; defaults SLIP_LU_internal.h:136-149
  *   slip_hip_factor_solve                <->  the integer core of SLIP_LU_solve
  *        SLIP_LU/Source/SLIP_LU_solve.c:41-86 (slip_forward_sub.c, slip_array_mul.c, slip_back_sub.c)
+ *   slip_hip_factor_check,               <->  SLIP_check_solution (integer form)
+ *   slip_hip_check_solution                   SLIP_LU/Source/SLIP_check_solution.c:31-113, SLIP_LU.h:988-993
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
  *
  * The GMP-typed drop-in  SLIP_LU_factorize(L,U,A,S,rhos,pinv,option)  built on
@@ -37,6 +39,7 @@ extern "C" {
 #define SLIP_HIP_OUT_OF_MEMORY   (-1)
 #define SLIP_HIP_SINGULAR        (-2)
 #define SLIP_HIP_INCORRECT_INPUT (-3)
+#define SLIP_HIP_INCORRECT       (-4)     /* SLIP_INCORRECT: a checked solution is not exact */
 #define SLIP_HIP_DEVICE_ERROR    (-100)   /* HIP runtime failure (no GPU, launch error) */
 
 typedef struct slip_hip_options {
@@ -140,6 +143,39 @@ int slip_hip_factor_from_factors(slip_hip_factor **out, int32_t n,
                                  const int32_t *pinv, const slip_hip_options *opt);
 /* device time of the solve kernels of the last slip_hip_factor_solve, milliseconds */
 double slip_hip_factor_solve_ms(const slip_hip_factor *f);
+
+/* Exact solution check (SLIP_check_solution, SLIP_LU/Source/SLIP_check_solution.c:31-113, as one integer test on the
+ * device): with x_c = xnum_c / d_c over one common denominator, A * xnum_c == d_c * b_c row by row, exactly.
+ *
+ * slip_hip_factor_check: on a handle made by slip_hip_factor_create with the factorisation complete (K == n).  b as
+ * slip_hip_factor_solve takes it (nrhs columns of n entries, ORIGINAL row order); x in exactly the form slip_hip_factor_solve
+ * returns it: numerators by pivot POSITION p (x_final[q[p]] = xnum[p] / det) over det = rho[n-1] of the handle's own,
+ * unrescaled factors.  Checks A(:,q) * xnum_c == det * b_c for every right-hand side c.
+ *
+ * slip_hip_check_solution: no handle.  A as slip_hip_factor_create takes it; x in ORIGINAL column order (x[c*n + j]
+ * multiplies A(:,j)); one nonzero integer denominator d_c per right-hand side (dlen[nrhs], limbs back to back).  Checks
+ * A * x_c == d_c * b_c.
+ *
+ * Return: SLIP_HIP_OK when every right-hand side is exact, SLIP_HIP_INCORRECT when at least one is not.  In both cases
+ * first_bad_row[c] = the smallest original row id i with r_i != 0 (-1: none) and bad_rows[c] = the number of such rows;
+ * either pointer may be NULL.  Every limb array travels with its capacity in limbs (b_limbs, x_limbs, d_limbs).
+ * SLIP_HIP_INCORRECT_INPUT, before any array is read past its end: nrhs < 1; a limb array whose sum |len| exceeds its
+ * capacity; d_c == 0; a handle from slip_hip_factor_from_factors (it holds no A); an incomplete factorisation.  High zero
+ * limbs in the inputs are allowed.  No CPU fallback: without a device the result is SLIP_HIP_DEVICE_ERROR.
+ *
+ * Duplicates: a row repeated in a column of A keeps its LAST value, as slip_hip_factor_create does (slip_get_column.c:22),
+ * so the check tests the matrix that was factorised.  Here it differs from SLIP_check_solution, which sums duplicates. */
+int slip_hip_factor_check(slip_hip_factor *f, int32_t nrhs,
+                          const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                          const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                          int32_t *first_bad_row, int64_t *bad_rows, void *stream);
+int slip_hip_check_solution(int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *Alen, const uint64_t *Alimbs,
+                            int32_t nrhs, const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                            const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                            const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                            int32_t *first_bad_row, int64_t *bad_rows, void *stream);
+/* device time of the check kernel of the last slip_hip_factor_check, milliseconds */
+double slip_hip_factor_check_ms(const slip_hip_factor *f);
 
 /* Subtree farm (no counterpart in the reference, which has no parallelism): multiply the K committed
  * columns by per-column scales on the device -- L(:,k) and rho[k] by scale[k], an entry of U in the row whose pivot sits

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 
 STATUS = {0: "SLIP_OK", -1: "SLIP_OUT_OF_MEMORY", -2: "SLIP_SINGULAR",
-          -3: "SLIP_INCORRECT_INPUT", -100: "DEVICE_ERROR"}
+          -3: "SLIP_INCORRECT_INPUT", -4: "SLIP_INCORRECT", -100: "DEVICE_ERROR"}
 
 
 class SlipError(RuntimeError):
@@ -28,6 +28,46 @@ def ints_to_slab(values):
     lens = np.sign(v).astype(np.int32)
     limbs = np.abs(v[v != 0]).astype(np.uint64)
     return lens, limbs
+
+
+def _limb_arrays(lens, limbs):
+    """(signed limb counts, limbs) as contiguous int32 / uint64 arrays, the limbs never empty (a valid pointer), and the
+    capacity the C side is told: the limbs really given"""
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    limbs = np.ascontiguousarray(limbs, dtype=np.uint64)
+    cap = limbs.size
+    return lens, (limbs if cap else np.zeros(1, np.uint64)), cap
+
+
+def _check_result(rc, where, first, bad):
+    """SLIP_INCORRECT is a verdict, every other nonzero code an error"""
+    if rc not in (0, -4):
+        raise SlipError(rc, where)
+    return rc == 0, first, bad
+
+
+def check_solution(n, Ap, Ai, Alen, Alimbs, blen, blimbs, xlen, xlimbs, dlen, dlimbs, nrhs=1, lib_path=None):
+    """Exact check on the device (slip_hip_check_solution): A * x_c == d_c * b_c for every right-hand side c, with A as
+    Factorization() takes it, b by original row and x by ORIGINAL column (n entries per right-hand side), d one nonzero
+    denominator per right-hand side, all as limb slabs.  Returns (ok, first_bad_row int32[nrhs], bad_rows int64[nrhs])."""
+    lib = _lib.load(lib_path)
+    n, nrhs = int(n), int(nrhs)
+    Ap = np.ascontiguousarray(Ap, dtype=np.int64)
+    Ai = np.ascontiguousarray(Ai, dtype=np.int32)
+    Alen, Alimbs, _ = _limb_arrays(Alen, Alimbs)
+    blen, blimbs, bcap = _limb_arrays(blen, blimbs)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
+    if Ap.size != n + 1 or blen.size != n * nrhs or xlen.size != n * nrhs or dlen.size != nrhs:
+        raise ValueError("check_solution: Ap needs n+1 entries, blen and xlen n*nrhs, dlen nrhs")
+    if Ai.size == 0:
+        Ai = np.zeros(1, np.int32)
+    first = np.zeros(max(nrhs, 1), np.int32)
+    bad = np.zeros(max(nrhs, 1), np.int64)
+    rc = lib.slip_hip_check_solution(n, Ap.ctypes.data, Ai.ctypes.data, Alen.ctypes.data, Alimbs.ctypes.data, nrhs,
+                                     blen.ctypes.data, blimbs.ctypes.data, bcap, xlen.ctypes.data, xlimbs.ctypes.data, xcap,
+                                     dlen.ctypes.data, dlimbs.ctypes.data, dcap, first.ctypes.data, bad.ctypes.data, None)
+    return _check_result(rc, "slip_hip_check_solution", first[:nrhs], bad[:nrhs])
 
 
 def matgen(n, density, bits, seed, lib_path=None):
@@ -199,6 +239,24 @@ class Factorization:
         self.lib.slip_hip_free(pl)
         self.lib.slip_hip_free(px)
         return xlen, xlimbs
+
+    def check(self, blen, blimbs, xlen, xlimbs, nrhs=1, stream=None):
+        """Exact check of a solve on the device (slip_hip_factor_check): A(:,q) xnum_c == det b_c, with b as `solve` takes
+        it and (xlen, xlimbs) as `solve` returns them.  Returns (ok, first_bad_row int32[nrhs], bad_rows int64[nrhs])."""
+        nrhs = int(nrhs)
+        blen, blimbs, bcap = _limb_arrays(blen, blimbs)
+        xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+        if blen.size != self.n * nrhs or xlen.size != self.n * nrhs:
+            raise ValueError("blen and xlen must hold n*nrhs entries")
+        first = np.zeros(max(nrhs, 1), np.int32)
+        bad = np.zeros(max(nrhs, 1), np.int64)
+        rc = self.lib.slip_hip_factor_check(self.h, nrhs, blen.ctypes.data, blimbs.ctypes.data, bcap,
+                                            xlen.ctypes.data, xlimbs.ctypes.data, xcap, first.ctypes.data, bad.ctypes.data,
+                                            C.c_void_p(stream or 0))
+        return _check_result(rc, "slip_hip_factor_check", first[:nrhs], bad[:nrhs])
+
+    def check_ms(self):
+        return self.lib.slip_hip_factor_check_ms(self.h)
 
     def pivots(self):
         """the pivot chain rho[0..K) only (signed limb counts, limbs): what the subtree farm exchanges"""

@@ -171,6 +171,128 @@ static void slip_rescale_body(SlipRescaleArgs A)
     }
 }
 
+/* Exact solution check (slip_hip_factor_check, slip_hip_check_solution): the integer form of SLIP_check_solution
+ * (SLIP_check_solution.c:31-113).  With x_c = xnum_c / d_c over one common denominator the test is
+ *     r_i = sum_e A(i, j_e) * xnum_c[x(e)]  -  d_c * b_c[i]  == 0      for every row i and right-hand side c,
+ * a sparse big-integer product over a row-ordered view of A (rp: row pointer; re: CSC entry of each term; rx: the index of
+ * x it multiplies).  One wavefront per (row, right-hand side), grid-stride; everything in the loop is wave-uniform.
+ *
+ * Why a fixed-width sum is an exact test: the (row, rhs) picks W = max(max_e(|a_e| + |x_e|), |d| + |b_i|) + 1 digits from
+ * the ACTUAL operand lengths.  Every term is below B^(W-1) in magnitude and a row has fewer than 2^24 terms (n < 2^24 - 1,
+ * duplicates removed, plus the d*b term), so |r_i| < 2^24 * B^(W-1) < B^W.  The sum is formed modulo B^M for some M >= W
+ * (M = 64*D on the register path, M = W on the memory path), a ring homomorphism: the accumulator holds r_i mod B^M, and
+ * since |r_i| < B^M that is all zero digits exactly when r_i = 0.  No sign or overflow is ever tracked. */
+struct SlipCheckArgs {
+    int32_t n, nrhs;
+    const int64_t *rp, *re; const int32_t *rx;                                     /* row view of A                          */
+    const int32_t *alen; const int64_t *aoff; const uint64_t *alimbs;              /* A: signed digit counts, limb offsets   */
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* x: entry c*n + x(e)                    */
+    const int32_t *blen; const int64_t *boff; const uint64_t *blimbs;              /* b: entry c*n + i                       */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* d_c: entry c                           */
+    int32_t *first_bad, *nbad;                                                     /* per right-hand side                    */
+    dig_t *scratch; int32_t wcap;                                                  /* memory path: 2 * wcap digits per wave  */
+};
+
+/* x * B modulo B^(64*D): every digit one lane up, lane 63 of a chunk into lane 0 of the next */
+template <int D> SLIP_DEV WR<D> wr_shl_digit(const WR<D> &x)
+{
+    WR<D> out;
+#pragma unroll
+    for (int r = D - 1; r >= 0; r--) out.d[r] = slip_dpp_shr1_in(x.d[r], r > 0 ? slip_readlane(x.d[r - 1], 63) : 0u);
+    return out;
+}
+
+/* acc +/- a * y modulo B^(64*D), la, ly >= 1; a of one or two digits (nearly every entry of A) takes one-digit products */
+template <int D> SLIP_DEV WR<D> slip_check_mac_reg(WR<D> acc, const dig_t *a, int la, const dig_t *y, int ly, int sub)
+{
+    const WR<D> Y = wr_load<D>(y, ly);
+    if (la == 1) return wr_addsub<D>(acc, wr_mul_digit<D>(a[0], Y), sub);
+    if (la == 2) {
+        WR<D> p0, p1;
+        wr_mul_digit2<D>(a[0], a[1], Y, p0, p1);
+        return wr_addsub<D>(wr_addsub<D>(acc, p0, sub), wr_shl_digit<D>(p1), sub);
+    }
+    const WR<D> Av = wr_load<D>(a, la);
+    return wr_addsub<D>(acc, la <= ly ? wr_mul<D>(Av, la, Y) : wr_mul<D>(Y, ly, Av), sub);
+}
+
+/* nonzero when r_i != 0: register path, W <= 64*D */
+template <int D> SLIP_DEV int slip_check_row_reg(const SlipCheckArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1)
+{
+    WR<D> acc = wr_zero<D>();
+    for (int64_t t = r0; t < r1; t++) {
+        const int64_t e = A.re[t], xe = xb + A.rx[t];
+        const int32_t sa = A.alen[e], sx = A.xlen[xe];
+        if (sa == 0 || sx == 0) continue;
+        acc = slip_check_mac_reg<D>(acc, (const dig_t *)(A.alimbs + A.aoff[e]), slip_abs(sa),
+                                    (const dig_t *)(A.xlimbs + A.xoff[xe]), slip_abs(sx), (sa < 0) != (sx < 0));
+    }
+    const int32_t sd = A.dlen[c], sb = A.blen[bi];
+    if (sd != 0 && sb != 0) {
+        const dig_t *d = (const dig_t *)(A.dlimbs + A.doff[c]), *b = (const dig_t *)(A.blimbs + A.boff[bi]);
+        const int ld = slip_abs(sd), lb = slip_abs(sb), sub = (sd < 0) == (sb < 0);     /* acc -= d*b */
+        acc = lb <= ld ? slip_check_mac_reg<D>(acc, b, lb, d, ld, sub) : slip_check_mac_reg<D>(acc, d, ld, b, lb, sub);
+    }
+    return wr_len<D>(acc) != 0;
+}
+
+/* the same on W-digit buffers in global memory (acc, prod: this wave's scratch) */
+SLIP_DEV int slip_check_row_wide(const SlipCheckArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1, int W,
+                                 dig_t *acc, dig_t *prod)
+{
+    for (int k = slip_lane(); k < W; k += SLIP_WAVE) acc[k] = 0u;
+    slip_wave_sync();
+    for (int64_t t = r0; t < r1; t++) {
+        const int64_t e = A.re[t], xe = xb + A.rx[t];
+        const int32_t sa = A.alen[e], sx = A.xlen[xe];
+        if (sa == 0 || sx == 0) continue;
+        wb_mul_lo(prod, (const dig_t *)(A.alimbs + A.aoff[e]), slip_abs(sa), (const dig_t *)(A.xlimbs + A.xoff[xe]), slip_abs(sx), W);
+        wb_addsub(acc, acc, W, prod, W, W, (sa < 0) != (sx < 0));
+    }
+    const int32_t sd = A.dlen[c], sb = A.blen[bi];
+    if (sd != 0 && sb != 0) {
+        wb_mul_lo(prod, (const dig_t *)(A.dlimbs + A.doff[c]), slip_abs(sd), (const dig_t *)(A.blimbs + A.boff[bi]), slip_abs(sb), W);
+        wb_addsub(acc, acc, W, prod, W, W, (sd < 0) == (sb < 0));
+    }
+    return wb_len(acc, W) != 0;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_check_kernel(SlipCheckArgs A)
+#else
+static void slip_check_body(SlipCheckArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    dig_t *acc = A.scratch ? A.scratch + wave0 * 2 * A.wcap : (dig_t *) 0, *prod = acc ? acc + A.wcap : (dig_t *) 0;
+    const int64_t items = (int64_t) A.n * A.nrhs;
+    for (int64_t it = wave0; it < items; it += nwaves) {
+        const int c = (int)(it / A.n), i = (int)(it - (int64_t) c * A.n);
+        const int64_t xb = (int64_t) c * A.n, bi = xb + i, r0 = A.rp[i], r1 = A.rp[i + 1];
+        /* the width of this (row, rhs), from the operands' own lengths */
+        uint32_t w = 0;
+        for (int64_t t = r0 + lane; t < r1; t += SLIP_WAVE) {
+            const uint32_t s = (uint32_t)(slip_abs(A.alen[A.re[t]]) + slip_abs(A.xlen[xb + A.rx[t]]));
+            if (s > w) w = s;
+        }
+        w = slip_wave_max_u32(w);
+        const uint32_t wdb = (uint32_t)(slip_abs(A.dlen[c]) + slip_abs(A.blen[bi]));
+        const int W = (int)(w > wdb ? w : wdb) + 1;
+        int bad;
+        if (W <= 64) bad = slip_check_row_reg<1>(A, xb, bi, c, r0, r1);
+        else if (W <= 128) bad = slip_check_row_reg<2>(A, xb, bi, c, r0, r1);
+        else if (W <= 192) bad = slip_check_row_reg<3>(A, xb, bi, c, r0, r1);
+        else if (W <= 256) bad = slip_check_row_reg<4>(A, xb, bi, c, r0, r1);
+        else bad = slip_check_row_wide(A, xb, bi, c, r0, r1, W, acc, prod);      /* W <= wcap: the host sized it */
+        if (bad && lane == 0) {
+            slip_atomic_min_i32(&A.first_bad[c], i);
+            slip_atomic_add_i32(&A.nbad[c], 1);
+        }
+    }
+}
+
 #ifndef SLIP_EMULATE
 #define SLIP_MAX_WAVES 8                   /* at most 512 threads per worker: 256 VGPRs per lane, two waves per SIMD */
 template <bool FAST>
@@ -308,6 +430,10 @@ struct slip_hip_factor {
     SlipEnt *rsLe, *rsUe; uint64_t *rsLl, *rsUl; int64_t rsLnl, rsUnl, rsLexact, rsUexact; int64_t *rspiv; int32_t rescaled;
     /* owned device arrays that are only reachable through const pointers in P */
     int64_t *dAp; int32_t *dAi, *dAlen; int64_t *dAoff; uint64_t *dAlimbs; int32_t *dq;
+    int32_t amaxdig;       /* digits of the widest entry of A */
+    /* slip_hip_factor_check: the row-ordered view of A, built on the first check (x index = pivot position) */
+    int64_t *chk_rp, *chk_re; int32_t *chk_rx;
+    double check_ms;
 };
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -717,6 +843,7 @@ extern "C" void slip_hip_factor_destroy(slip_hip_factor *f)
     dev_free(P->Up); dev_free(P->Uo); dev_free(P->Ui); dev_free(P->Ue); dev_free(P->Ulimbs);
     dev_free(P->Lready.p_); dev_free(P->pat); dev_free(P->rlist); dev_free(P->rpos); dev_free(P->srow); dev_free(P->gscratch); dev_free(P->gbitmap); dev_free(P->dbg); dev_free(P->pkg.p_); dev_free(P->jobs.p_); dev_free(P->sw_row.p_); dev_free(P->sw_pos.p_);
     dev_free(f->ds); dev_free(f->ident);
+    dev_free(f->chk_rp); dev_free(f->chk_re); dev_free(f->chk_rx);
     rescale_drop(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
@@ -749,40 +876,30 @@ static int make_ident(slip_hip_factor *f)
     return rc;
 }
 
-extern "C" int slip_hip_factor_create(slip_hip_factor **out, int32_t n,
-                                      const int64_t *Ap, const int32_t *Ai,
-                                      const int32_t *Alen, const uint64_t *Alimbs,
-                                      const int32_t *q, const slip_hip_options *opt_in)
+/* host-side preparation of A (slip_hip_factor_create, slip_hip_check_solution): bounds check, de-duplicate, digit counts.
+ * out: the CSC with a repeated row of a column kept once, with its LAST value; signed DIGIT counts, limb offsets, high
+ * zero limbs trimmed; maxdig = digits of the widest entry (at least 1).  Release with host_a_free. */
+struct SlipHostA { int64_t *Ap; int32_t *Ai, *Alen; int64_t *Aoff; uint64_t *Alimbs; int64_t nnz, nl; int32_t maxdig; };
+static void host_a_free(SlipHostA *a) { free(a->Ap); free(a->Ai); free(a->Alen); free(a->Aoff); free(a->Alimbs); memset(a, 0, sizeof *a); }
+static int prepare_A(int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *Alen, const uint64_t *Alimbs, SlipHostA *out)
 {
-    /* SLIP_LU_factorize.c:48-52: any missing argument is SLIP_INCORRECT_INPUT */
-    if (!out || n <= 0 || !Ap || !Ai || !Alen || !Alimbs || !q) return SLIP_HIP_INCORRECT_INPUT;
-    *out = NULL;
-    if (slip_hip_device_count() <= 0) {
-        fprintf(stderr, "slip_hip: no HIP device available -- this library has no CPU fallback\n");
-        return SLIP_HIP_DEVICE_ERROR;
-    }
-    slip_hip_options opt;
-    if (opt_in) opt = *opt_in; else slip_hip_default_options(&opt);
-    if (opt.pivot < 0 || opt.pivot > 5) return SLIP_HIP_INCORRECT_INPUT;
+    memset(out, 0, sizeof *out);
     /* column and row numbers travel in 24-bit fields of the commit protocol (verdict words, package records) */
     if (n >= (1 << 24) - 1) return SLIP_HIP_INCORRECT_INPUT;
     const int64_t annz = Ap[n];
     if (Ap[0] != 0 || annz < 1) return SLIP_HIP_INCORRECT_INPUT;
 
-    /* ---- host-side preparation of A: bounds check, de-duplicate, digit counts ---- */
     int64_t *hAp = (int64_t *) malloc(((size_t) n + 1) * 8);
     int32_t *hAi = (int32_t *) malloc((size_t) annz * 4), *hAlen = (int32_t *) malloc((size_t) annz * 4);
     int64_t *hAoff = (int64_t *) malloc((size_t) annz * 8), *inoff = (int64_t *) malloc(((size_t) annz + 1) * 8);
     int32_t *last = (int32_t *) malloc((size_t) n * 4);
-    char *seen = (char *) calloc((size_t) n, 1);
-    if (!hAp || !hAi || !hAlen || !hAoff || !inoff || !last || !seen) {
-        free(hAp); free(hAi); free(hAlen); free(hAoff); free(inoff); free(last); free(seen);
+    if (!hAp || !hAi || !hAlen || !hAoff || !inoff || !last) {
+        free(hAp); free(hAi); free(hAlen); free(hAoff); free(inoff); free(last);
         return SLIP_HIP_OUT_OF_MEMORY;
     }
     int bad = 0;
     inoff[0] = 0;
     for (int64_t p = 0; p < annz; p++) inoff[p + 1] = inoff[p] + (Alen[p] < 0 ? -(int64_t) Alen[p] : Alen[p]);
-    for (int32_t j = 0; j < n && !bad; j++) { if (q[j] < 0 || q[j] >= n || seen[q[j]]) bad = 1; else seen[q[j]] = 1; }
     for (int32_t i = 0; i < n; i++) last[i] = -1;
     uint64_t *hAlimbs = (uint64_t *) malloc((size_t)(inoff[annz] > 0 ? inoff[annz] : 1) * 8);
     if (!hAlimbs) bad = 2;
@@ -814,13 +931,46 @@ extern "C" int slip_hip_factor_create(slip_hip_factor **out, int32_t n,
         for (int64_t p = Ap[j]; p < Ap[j + 1]; p++) last[Ai[p]] = -1;
     }
     hAp[n] = onz;
-    free(inoff); free(last); free(seen);
+    free(inoff); free(last);
     if (bad) { free(hAp); free(hAi); free(hAlen); free(hAoff); free(hAlimbs); return bad == 2 ? SLIP_HIP_OUT_OF_MEMORY : SLIP_HIP_INCORRECT_INPUT; }
+    out->Ap = hAp; out->Ai = hAi; out->Alen = hAlen; out->Aoff = hAoff; out->Alimbs = hAlimbs;
+    out->nnz = onz; out->nl = ol; out->maxdig = maxdig;
+    return SLIP_HIP_OK;
+
+}
+
+extern "C" int slip_hip_factor_create(slip_hip_factor **out, int32_t n,
+                                      const int64_t *Ap, const int32_t *Ai,
+                                      const int32_t *Alen, const uint64_t *Alimbs,
+                                      const int32_t *q, const slip_hip_options *opt_in)
+{
+    /* SLIP_LU_factorize.c:48-52: any missing argument is SLIP_INCORRECT_INPUT */
+    if (!out || n <= 0 || !Ap || !Ai || !Alen || !Alimbs || !q) return SLIP_HIP_INCORRECT_INPUT;
+    *out = NULL;
+    if (slip_hip_device_count() <= 0) {
+        fprintf(stderr, "slip_hip: no HIP device available -- this library has no CPU fallback\n");
+        return SLIP_HIP_DEVICE_ERROR;
+    }
+    slip_hip_options opt;
+    if (opt_in) opt = *opt_in; else slip_hip_default_options(&opt);
+    if (opt.pivot < 0 || opt.pivot > 5) return SLIP_HIP_INCORRECT_INPUT;
+    SlipHostA ha;
+    { const int e = prepare_A(n, Ap, Ai, Alen, Alimbs, &ha); if (e) return e; }
+    {
+        char *seen = (char *) calloc((size_t) n, 1);
+        int bad = !seen ? 2 : 0;
+        for (int32_t j = 0; j < n && !bad; j++) { if (q[j] < 0 || q[j] >= n || seen[q[j]]) bad = 1; else seen[q[j]] = 1; }
+        free(seen);
+        if (bad) { host_a_free(&ha); return bad == 2 ? SLIP_HIP_OUT_OF_MEMORY : SLIP_HIP_INCORRECT_INPUT; }
+    }
+    int64_t *hAp = ha.Ap; int32_t *hAi = ha.Ai, *hAlen = ha.Alen; int64_t *hAoff = ha.Aoff; uint64_t *hAlimbs = ha.Alimbs;
+    const int64_t onz = ha.nnz, ol = ha.nl;
+    const int32_t maxdig = ha.maxdig;
 
     slip_hip_factor *f = (slip_hip_factor *) calloc(1, sizeof(slip_hip_factor));
     if (!f) { free(hAp); free(hAi); free(hAlen); free(hAoff); free(hAlimbs); return SLIP_HIP_OUT_OF_MEMORY; }
     SlipParams *P = &f->P;
-    f->n = n; f->annz = onz; f->alimbs = ol;
+    f->n = n; f->annz = onz; f->alimbs = ol; f->amaxdig = maxdig;
     apply_options(f, opt);
     P->n = n; P->pivot_scheme = opt.pivot; P->limb_cap = opt.limb_cap;
     if (!(opt.tol > 0)) { P->tol_mode = 0; P->tol_m = 0; P->tol_e = 0; }
@@ -1377,6 +1527,240 @@ extern "C" int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int
 }
 
 extern "C" double slip_hip_factor_solve_ms(const slip_hip_factor *f) { return f ? f->solve_ms : 0.0; }
+
+/* ---- exact solution check (SLIP_check_solution.c:31-113 as one integer test; kernel: slip_check_kernel) ---- */
+
+/* a limb slab of `count` entries -> signed digit counts and limb offsets (high zero limbs trimmed); *total = limbs it spans.
+ * The capacity is checked from the counts alone, before any limb is read. */
+struct SlipSlab { int32_t *dig; int64_t *off; int64_t total; int32_t maxdig; };
+static void slab_free(SlipSlab *s) { free(s->dig); free(s->off); s->dig = NULL; s->off = NULL; }
+static int slab_prepare(int64_t count, const int32_t *len, const uint64_t *limbs, int64_t cap, SlipSlab *s)
+{
+    memset(s, 0, sizeof *s);
+    int64_t total = 0;
+    for (int64_t t = 0; t < count; t++) total += len[t] < 0 ? -(int64_t) len[t] : len[t];
+    if (total > cap) return SLIP_HIP_INCORRECT_INPUT;
+    s->dig = (int32_t *) malloc((size_t)(count > 0 ? count : 1) * 4);
+    s->off = (int64_t *) malloc((size_t)(count > 0 ? count : 1) * 8);
+    if (!s->dig || !s->off) { slab_free(s); return SLIP_HIP_OUT_OF_MEMORY; }
+    int64_t o = 0;
+    for (int64_t t = 0; t < count; t++) {
+        int64_t l = len[t] < 0 ? -(int64_t) len[t] : len[t];
+        const uint64_t *src = limbs + o;
+        s->off[t] = o;
+        o += l;
+        while (l > 0 && src[l - 1] == 0) l--;
+        int32_t dig = (int32_t)(2 * l);
+        if (l > 0 && (src[l - 1] >> 32) == 0) dig--;
+        s->dig[t] = len[t] < 0 ? -dig : dig;
+        if (dig > s->maxdig) s->maxdig = dig;
+    }
+    s->total = o;
+    return SLIP_HIP_OK;
+}
+
+/* the row-ordered view of a CSC pattern (counting sort on the rows): rp[n+1]; per term its CSC entry and the index of x it
+ * multiplies (xidx[j] for column j, or j itself when xidx is NULL) */
+static int build_row_view(int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *xidx, int64_t **rp_out, int64_t **re_out, int32_t **rx_out)
+{
+    const int64_t nz = Ap[n];
+    int64_t *rp = (int64_t *) calloc((size_t) n + 1, 8), *re = (int64_t *) malloc((size_t)(nz > 0 ? nz : 1) * 8), *w = (int64_t *) malloc((size_t) n * 8);
+    int32_t *rx = (int32_t *) malloc((size_t)(nz > 0 ? nz : 1) * 4);
+    if (!rp || !re || !w || !rx) { free(rp); free(re); free(w); free(rx); return SLIP_HIP_OUT_OF_MEMORY; }
+    for (int64_t e = 0; e < nz; e++) rp[Ai[e] + 1]++;
+    for (int32_t i = 0; i < n; i++) rp[i + 1] += rp[i];
+    memcpy(w, rp, (size_t) n * 8);
+    for (int32_t j = 0; j < n; j++)
+        for (int64_t e = Ap[j]; e < Ap[j + 1]; e++) { const int64_t t = w[Ai[e]]++; re[t] = e; rx[t] = xidx ? xidx[j] : j; }
+    free(w);
+    *rp_out = rp; *re_out = re; *rx_out = rx;
+    return SLIP_HIP_OK;
+}
+
+/* one check on the device: A (device, digit counts) through its row view, b and x prepared on the host, d_c on the device.
+ * Writes the verdicts, returns SLIP_HIP_OK / SLIP_HIP_INCORRECT or an error. */
+static int check_core(int32_t n, int32_t nrhs, const int64_t *drp, const int64_t *dre, const int32_t *drx,
+                      const int32_t *dalen, const int64_t *daoff, const uint64_t *dalimbs, int32_t amaxdig,
+                      const SlipSlab &bs, const uint64_t *blimbs, const SlipSlab &xs, const uint64_t *xlimbs,
+                      const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
+                      int32_t *first_bad_row, int64_t *bad_rows, hipStream_t stream, double *ms_out)
+{
+    const int64_t ne = (int64_t) n * nrhs;
+    /* every (row, rhs) width is at most this (slip_check_kernel): the memory path's scratch is sized from it */
+    const int64_t wcap = (amaxdig + xs.maxdig > dmaxdig + bs.maxdig ? amaxdig + xs.maxdig : dmaxdig + bs.maxdig) + 1;
+    if (wcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
+#ifndef SLIP_EMULATE
+    int64_t blocks = (ne + 3) / 4; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    const int64_t waves_per_block = 4;
+    if (wcap > 256) {                                          /* memory path: at most 256 MiB of scratch */
+        const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * 2 * wcap * 4);
+        if (blocks > fit) blocks = fit > 0 ? fit : 1;
+    }
+#else
+    const int64_t blocks = 2, waves_per_block = 2;
+#endif
+    int32_t *dxl = NULL, *dbl = NULL, *dfirst = NULL, *dbad = NULL; int64_t *dxo = NULL, *dbo = NULL; uint64_t *dxv = NULL, *dbv = NULL; dig_t *dscr = NULL;
+    int32_t *hfirst = (int32_t *) malloc((size_t) nrhs * 4), *hbad = (int32_t *) malloc((size_t) nrhs * 4);
+    hipEvent_t ev0 = NULL, ev1 = NULL;
+    int rc = (!hfirst || !hbad) ? SLIP_HIP_OUT_OF_MEMORY : 0;
+#define A_(call) do { if (!rc) rc = (call); } while (0)
+    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total)); A_(dev_alloc(&dbl, ne)); A_(dev_alloc(&dbo, ne)); A_(dev_alloc(&dbv, bs.total));
+    A_(dev_alloc(&dfirst, nrhs)); A_(dev_alloc(&dbad, nrhs));
+    if (wcap > 256) A_(dev_alloc(&dscr, blocks * waves_per_block * 2 * wcap));
+#undef A_
+    if (!rc) {
+        for (int32_t c = 0; c < nrhs; c++) { hfirst[c] = n; hbad[c] = 0; }
+        if (hipMemcpy(dxl, xs.dig, (size_t) ne * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dxo, xs.off, (size_t) ne * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            (xs.total > 0 && hipMemcpy(dxv, xlimbs, (size_t) xs.total * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+            hipMemcpy(dbl, bs.dig, (size_t) ne * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dbo, bs.off, (size_t) ne * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            (bs.total > 0 && hipMemcpy(dbv, blimbs, (size_t) bs.total * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+            hipMemcpy(dfirst, hfirst, (size_t) nrhs * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dbad, hbad, (size_t) nrhs * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)
+            rc = SLIP_HIP_DEVICE_ERROR;
+    }
+    if (!rc) {
+        SlipCheckArgs A; memset(&A, 0, sizeof A);
+        A.n = n; A.nrhs = nrhs; A.rp = drp; A.re = dre; A.rx = drx;
+        A.alen = dalen; A.aoff = daoff; A.alimbs = dalimbs;
+        A.xlen = dxl; A.xoff = dxo; A.xlimbs = dxv; A.blen = dbl; A.boff = dbo; A.blimbs = dbv;
+        A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
+        A.first_bad = dfirst; A.nbad = dbad; A.scratch = dscr; A.wcap = (int32_t) wcap;
+        if (hipEventRecord(ev0, stream) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
+#ifndef SLIP_EMULATE
+        if (!rc) {
+            hipLaunchKernelGGL(slip_check_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
+            if (hipGetLastError() != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
+        }
+#else
+        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_check_body(A); }, 256 * 1024, 1);
+#endif
+        if (!rc && (hipEventRecord(ev1, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)) rc = SLIP_HIP_DEVICE_ERROR;
+        float ms = 0;
+        if (!rc && hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
+        if (ms_out) *ms_out = ms;
+    }
+    if (!rc && (hipMemcpy(hfirst, dfirst, (size_t) nrhs * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(hbad, dbad, (size_t) nrhs * 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = SLIP_HIP_DEVICE_ERROR;
+    if (!rc) {
+        int exact = 1;
+        for (int32_t c = 0; c < nrhs; c++) {
+            if (hbad[c]) exact = 0;
+            if (first_bad_row) first_bad_row[c] = hbad[c] ? hfirst[c] : -1;
+            if (bad_rows) bad_rows[c] = hbad[c];
+        }
+        rc = exact ? SLIP_HIP_OK : SLIP_HIP_INCORRECT;
+    }
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dbl); dev_free(dbo); dev_free(dbv); dev_free(dfirst); dev_free(dbad); dev_free(dscr);
+    free(hfirst); free(hbad);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_check(slip_hip_factor *f, int32_t nrhs,
+                                     const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                                     const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                     int32_t *first_bad_row, int64_t *bad_rows, void *stream_v)
+{
+    if (!f || f->factors_only || nrhs < 1 || !blen || !blimbs || !xlen || !xlimbs) return SLIP_HIP_INCORRECT_INPUT;
+    const int32_t n = f->n;
+    if (f->hs.F != n || f->last_status == SLIP_HIP_DEVICE_ERROR) return SLIP_HIP_INCORRECT_INPUT;   /* needs the complete factorisation */
+    const int64_t ne = (int64_t) n * nrhs;
+    SlipSlab bs, xs;
+    int rc = slab_prepare(ne, blen, blimbs, b_limbs, &bs);
+    if (!rc) rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
+    else memset(&xs, 0, sizeof xs);
+    SlipParams *P = &f->P;
+    /* the row view of the resident A, once per handle: x is indexed by pivot position, column q[p] -> p */
+    if (!rc && !f->chk_rp) {
+        int64_t *hAp = (int64_t *) malloc(((size_t) n + 1) * 8), *rp = NULL, *re = NULL;
+        int32_t *hAi = (int32_t *) malloc((size_t)(f->annz > 0 ? f->annz : 1) * 4), *hq = (int32_t *) malloc((size_t) n * 4), *qinv = (int32_t *) malloc((size_t) n * 4), *rx = NULL;
+        if (!hAp || !hAi || !hq || !qinv) rc = SLIP_HIP_OUT_OF_MEMORY;
+        else if (hipMemcpy(hAp, f->dAp, ((size_t) n + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(hAi, f->dAi, (size_t) f->annz * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(hq, f->dq, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
+        if (!rc) { for (int32_t p = 0; p < n; p++) qinv[hq[p]] = p; rc = build_row_view(n, hAp, hAi, qinv, &rp, &re, &rx); }
+        if (!rc) {
+            const int64_t nz = hAp[n];
+            if (dev_alloc(&f->chk_rp, (int64_t) n + 1) || dev_alloc(&f->chk_re, nz) || dev_alloc(&f->chk_rx, nz)) rc = SLIP_HIP_OUT_OF_MEMORY;
+            else if (hipMemcpy(f->chk_rp, rp, ((size_t) n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                     hipMemcpy(f->chk_re, re, (size_t) nz * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                     hipMemcpy(f->chk_rx, rx, (size_t) nz * 4, hipMemcpyHostToDevice) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
+            if (rc) { dev_free(f->chk_rp); dev_free(f->chk_re); dev_free(f->chk_rx); f->chk_rp = NULL; f->chk_re = NULL; f->chk_rx = NULL; }
+        }
+        free(hAp); free(hAi); free(hq); free(qinv); free(rp); free(re); free(rx);
+    }
+    /* d = det = rho[n-1], read in place from the L slab through its pivot record */
+    int32_t *ddlen = NULL; int64_t *ddoff = NULL; int32_t dmaxdig = 0;
+    if (!rc) {
+        SlipPiv pr;
+        if (hipMemcpy(&pr, P->piv.p_ + (n - 1), sizeof pr, hipMemcpyDeviceToHost) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
+        else if (pr.len == 0 || pr.off < 0 || pr.off + (((pr.len < 0 ? -pr.len : pr.len) + 1) >> 1) > P->Lcap_nl) rc = SLIP_HIP_DEVICE_ERROR;
+        int32_t *hl = (int32_t *) malloc((size_t) nrhs * 4); int64_t *ho = (int64_t *) malloc((size_t) nrhs * 8);
+        if (!rc && (!hl || !ho)) rc = SLIP_HIP_OUT_OF_MEMORY;
+        if (!rc) {
+            for (int32_t c = 0; c < nrhs; c++) { hl[c] = pr.len; ho[c] = pr.off; }
+            dmaxdig = pr.len < 0 ? -pr.len : pr.len;
+            if (dev_alloc(&ddlen, nrhs) || dev_alloc(&ddoff, nrhs)) rc = SLIP_HIP_OUT_OF_MEMORY;
+            else if (hipMemcpy(ddlen, hl, (size_t) nrhs * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                     hipMemcpy(ddoff, ho, (size_t) nrhs * 8, hipMemcpyHostToDevice) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
+        }
+        free(hl); free(ho);
+    }
+    if (!rc) {
+        f->check_ms = 0;
+        rc = check_core(n, nrhs, f->chk_rp, f->chk_re, f->chk_rx, f->dAlen, f->dAoff, f->dAlimbs, f->amaxdig,
+                        bs, blimbs, xs, xlimbs, ddlen, ddoff, P->Llimbs, dmaxdig, first_bad_row, bad_rows, (hipStream_t) stream_v, &f->check_ms);
+    }
+    dev_free(ddlen); dev_free(ddoff);
+    slab_free(&bs); slab_free(&xs);
+    return rc;
+}
+
+extern "C" double slip_hip_factor_check_ms(const slip_hip_factor *f) { return f ? f->check_ms : 0.0; }
+
+extern "C" int slip_hip_check_solution(int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *Alen, const uint64_t *Alimbs,
+                                       int32_t nrhs, const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                                       const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                       const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                       int32_t *first_bad_row, int64_t *bad_rows, void *stream_v)
+{
+    if (n <= 0 || !Ap || !Ai || !Alen || !Alimbs || nrhs < 1 || !blen || !blimbs || !xlen || !xlimbs || !dlen || !dlimbs) return SLIP_HIP_INCORRECT_INPUT;
+    if (slip_hip_device_count() <= 0) {
+        fprintf(stderr, "slip_hip: no HIP device available -- this library has no CPU fallback\n");
+        return SLIP_HIP_DEVICE_ERROR;
+    }
+    const int64_t ne = (int64_t) n * nrhs;
+    SlipSlab bs, xs, ds;
+    memset(&xs, 0, sizeof xs); memset(&ds, 0, sizeof ds);
+    int rc = slab_prepare(ne, blen, blimbs, b_limbs, &bs);
+    if (!rc) rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
+    if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
+    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no solution */
+    SlipHostA ha; memset(&ha, 0, sizeof ha);
+    if (!rc) rc = prepare_A(n, Ap, Ai, Alen, Alimbs, &ha);
+    int64_t *rp = NULL, *re = NULL; int32_t *rx = NULL;
+    if (!rc) rc = build_row_view(n, ha.Ap, ha.Ai, NULL, &rp, &re, &rx);
+    int64_t *drp = NULL, *dre = NULL, *daoff = NULL, *ddoff = NULL; int32_t *drx = NULL, *dalen = NULL, *ddlen = NULL; uint64_t *dal = NULL, *ddl = NULL;
+    const int64_t nz = ha.nnz;
+#define A_(call) do { if (!rc) rc = (call); } while (0)
+    A_(dev_alloc(&drp, (int64_t) n + 1)); A_(dev_alloc(&dre, nz)); A_(dev_alloc(&drx, nz));
+    A_(dev_alloc(&dalen, nz)); A_(dev_alloc(&daoff, nz)); A_(dev_alloc(&dal, ha.nl));
+    A_(dev_alloc(&ddlen, nrhs)); A_(dev_alloc(&ddoff, nrhs)); A_(dev_alloc(&ddl, ds.total));
+#undef A_
+#define UP_(dst, src, bytes) do { if (!rc && (bytes) > 0 && hipMemcpy((void *)(dst), (src), (size_t)(bytes), hipMemcpyHostToDevice) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR; } while (0)
+    UP_(drp, rp, ((size_t) n + 1) * 8); UP_(dre, re, (size_t) nz * 8); UP_(drx, rx, (size_t) nz * 4);
+    UP_(dalen, ha.Alen, (size_t) nz * 4); UP_(daoff, ha.Aoff, (size_t) nz * 8); UP_(dal, ha.Alimbs, (size_t) ha.nl * 8);
+    UP_(ddlen, ds.dig, (size_t) nrhs * 4); UP_(ddoff, ds.off, (size_t) nrhs * 8); UP_(ddl, dlimbs, (size_t) ds.total * 8);
+#undef UP_
+    if (!rc) rc = check_core(n, nrhs, drp, dre, drx, dalen, daoff, dal, ha.maxdig, bs, blimbs, xs, xlimbs, ddlen, ddoff, ddl, ds.maxdig,
+                             first_bad_row, bad_rows, (hipStream_t) stream_v, NULL);
+    dev_free(drp); dev_free(dre); dev_free(drx); dev_free(dalen); dev_free(daoff); dev_free(dal); dev_free(ddlen); dev_free(ddoff); dev_free(ddl);
+    free(rp); free(re); free(rx);
+    host_a_free(&ha);
+    slab_free(&bs); slab_free(&xs); slab_free(&ds);
+    return rc;
+}
 
 /* ---- subtree farm: multiply the committed factors by per-column scales ---- */
 static void rescale_drop(slip_hip_factor *f)
