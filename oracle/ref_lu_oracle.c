@@ -487,7 +487,10 @@ orc_result *orc_factorize(int32_t n, const int64_t *Ap, const int32_t *Ai,
                 if (pivot >= 0 && diag_ok && ratio_ge_tol(&x[pivot], &x[col], tol)) pivot = col;
                 break;
         case 4: pivot = pick(1, x, pivs, n, top, xi);
-                if (pivot >= 0 && diag_ok && ratio_ge_tol(&x[col], &x[pivot], tol)) pivot = col;
+                /* :137-145 builds ratio = x[col] / x[pivot] without canonicalising and mpq_abs fixes only the numerator:
+                 * a negative largest candidate leaves a negative denominator, which mpq_cmp does not expect -- it then
+                 * reports ratio >= tol for every tol below 2^64, so the diagonal is taken (pivot rules) */
+                if (pivot >= 0 && diag_ok && (bz_sgn(&x[pivot]) < 0 || ratio_ge_tol(&x[col], &x[pivot], tol))) pivot = col;
                 break;
         default: pivot = pick(1, x, pivs, n, top, xi); break;
         }

@@ -973,6 +973,8 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
      * (slip_get_pivot.c:89-118, 126-146): 1 = take the diagonal; *err: scratch too small */
     auto diag_rule = [&](int pr, int *err) -> int {
         if (scheme == 1 || P.tol_mode == 0) return 1;
+        /* scheme 4: a negative largest candidate always yields to the diagonal, as the reference's ratio does */
+        if (scheme == 4 && P.xrow[pr].len < 0) return 1;
         const int lp_ = slip_abs(P.xrow[pr].len), lc_ = slip_abs(P.xrow[col].len);
         /* tol_m has exactly 53 bits, so tol_m*|den| has 52 or 53 bits more than |den|: most columns
          * are decided by the bit lengths alone */
@@ -1056,6 +1058,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             if (!est && A.diag_cand && e_pivrow != col) {
                 int derr = 0;
                 const int take = diag_rule(e_pivrow, &derr);
+                SLIP_TRACE_L0("diag col %d site search: best row %d len %d take %d\n", k, e_pivrow, P.xrow[e_pivrow].len, take);
                 if (derr) est = SLIPDEV_GROW_X;
                 else if (take) { e_pivrow = col; e_pivpos = pc_col; stg = -1; }
             }
@@ -1792,6 +1795,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
         if (diag_ok && pivrow != col) {
             int err = 0;
             const int take = diag_rule(pivrow, &err);
+            SLIP_TRACE("diag col %d site complete: best row %d len %d take %d\n", k, pivrow, P.xrow[pivrow].len, take);
             if (err) return SLIPDEV_GROW_X;
             if (take) pivrow = col;
         }

@@ -459,6 +459,10 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                     const uint64_t ad = (uint64_t) slip_readlane(c_a0, dc) | ((uint64_t) slip_readlane(c_a1, dc) << 32);
                                     const int tk = slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? ab : ad, scheme == 3 ? ad : ab);
                                     if (tk < 0) spec = 0x200u; else if (tk) bc = dc;
+                                    /* scheme 4 takes the diagonal when the largest candidate a*rho[j-1] is negative; rho[j-1]'s
+                                     * sign is known in the serial step only: the column is chosen again there */
+                                    else if (scheme == 4) spec = 0x100u;
+                                    SLIP_TRACE_L0("diag col %d site batch: tk %d spec %x\n", j, tk, spec);
                                 }
                             }
                         }
@@ -630,7 +634,10 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                             else {
                                 const uint64_t ab = (uint64_t) slip_readlane(c_a0, bc) | ((uint64_t) slip_readlane(c_a1, bc) << 32);
                                 const uint64_t ad = (uint64_t) slip_readlane(c_a0, dc) | ((uint64_t) slip_readlane(c_a1, dc) << 32);
-                                const int tk = slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? ab : ad, scheme == 3 ? ad : ab);
+                                /* scheme 4: a negative largest candidate yields to the diagonal; its sign is a's times rho[j-1]'s */
+                                const int neg = scheme == 4 && (int)((slip_readlane(c_ax, bc) >> 14) & 1u) != (M.len < 0);
+                                const int tk = neg ? 1 : slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? ab : ad, scheme == 3 ? ad : ab);
+                                SLIP_TRACE_L0("diag col %d site serial: best negative %d take %d\n", j, neg, tk);
                                 if (tk < 0) est = -1; else if (tk) bc = dc;
                             }
                         }
@@ -911,7 +918,10 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                         if (dv != 0) {
                                             if (scheme == 1 || P.tol_mode == 0) pt = dt;
                                             else {
-                                                const int tk = slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? bv : dv, scheme == 3 ? dv : bv);
+                                                /* scheme 4: a negative largest candidate yields to the diagonal */
+                                                const int neg = scheme == 4 && (est_meta[pt] >> 31);
+                                                const int tk = neg ? 1 : slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? bv : dv, scheme == 3 ? dv : bv);
+                                                SLIP_TRACE_L0("diag col %d site engine: best negative %d take %d\n", j, neg, tk);
                                                 if (tk < 0) reject = 2; else if (tk) pt = dt;
                                             }
                                         }

@@ -4,7 +4,7 @@
  * line -- libslip_lu_hip.so (HIP path; it serves SLIP_LU_solve as well) or the reference itself.  TEST ONLY; compiled here, where
  * the reference's headers exist (tests/dropin/Makefile), the binaries travel to the GPU box.
  *
- *   dropin_driver <triplet file> [pivot] [nrhs]
+ *   dropin_driver <triplet file> [pivot] [nrhs] [tol] [order]
  *   dropin_driver --errors            (the error paths, in the shape of Tcov/cov_test.c:342-345,466-472,674-678,751-763)
  * prints: status of SLIP_check_solution (exact A x == b), then the demo's report numbers
  *   sum bits(rhos) / sum bits(L)+bits(U)-bits(rhos) / L->nz+U->nz-n     (SLIPLU.c:339-367)
@@ -73,7 +73,7 @@ static int error_paths(void)
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { printf("usage: dropin_driver <triplet> [pivot] [nrhs] | --errors\n"); return 2; }
+    if (argc < 2) { printf("usage: dropin_driver <triplet> [pivot] [nrhs] [tol] [order] | --errors\n"); return 2; }
     if (!strcmp(argv[1], "--errors")) return error_paths();
     const int32_t nrhs = argc > 3 ? atoi(argv[3]) : 1;
     SLIP_initialize();
@@ -92,6 +92,8 @@ int main(int argc, char **argv)
     SLIP_dense *b = SLIP_create_dense();
     SLIP_options *option = SLIP_create_default_options();
     if (argc > 2) option->pivot = (SLIP_pivot) atoi(argv[2]);
+    if (argc > 4) option->tol = atof(argv[4]);
+    if (argc > 5) option->order = (SLIP_col_order) atoi(argv[5]);
     OK(SLIP_build_sparse_trip_mpz(A, I, J, xv, n, nz));
 
     /* b: a deterministic integer right-hand side */

@@ -133,9 +133,197 @@ def run_solve_cases():
     json.dump(idx, open(os.path.join(HERE, "solve_index.json"), "w"), indent=1)
 
 
+# ---- the pivot-edge corpus (pivot_corpus.json + pivot_corpus.slab.gz) ----
+# Small signed matrices whose columns put the candidates of slip_get_pivot in the places where a pivot rule can be
+# read wrongly: a negative largest candidate (scheme 4), magnitude ties with opposite signs, multi-limb candidates that
+# tie on the kernel's search key (bit length, top 40 bits) or are equal over several limbs, tolerance ratios exactly
+# on tol and one unit below it, a diagonal that is an explicit zero / missing / already pivotal, explicit zeros
+# first in the pattern, a singular column.  Crafted columns sit at the first column of a block of a block
+# lower-triangular matrix: there the block's rows are untouched, so a candidate is a*rho[k-1] and the crafted ties,
+# ratios and signs survive into multi-limb values (both sign polarities of a block are emitted, as the sign of
+# rho[k-1] is whatever the preceding blocks made it).  Column order 0: a crafted column stays where it was placed.
+# Every matrix runs under every scheme; schemes 3 and 4 under each tolerance of CORPUS_TOLS (0.375: the exact-tie
+# value the crafted 3:8 ratios hit).  Deterministic: the same seed gives the same bytes (gzip mtime 0).
+CORPUS_SEED = 20261015
+CORPUS_TOLS = (1.0, 0.5, 0.3, 0.1, 2.0 ** -20, 0.375)
+# candidate sizes: one limb (the in-lane paths), a few limbs, and register sizes up to and beyond the D=4 cap of
+# 256 32-bit digits (8192 bits)
+CORPUS_BITS = (20, 62, 64, 130, 1500, 8150, 8300)
+RATIO_BITS = (20, 64, 130, 8150)
+
+
+def _corpus_blocks(rnd):
+    """[(label, first-column entries {block row: value}, block size)] -- rows relative to the block, row 0 is the diagonal
+    (absent from the dict: no entry; 0: an explicit zero)."""
+    B = []
+
+    def big(bits):
+        return (1 << (bits - 1)) | rnd.getrandbits(bits - 1)
+
+    for bits in CORPUS_BITS:
+        v = big(bits)
+        # the largest candidate negative, the diagonal smaller / equal / an explicit zero / missing
+        B.append(("neg_largest_diag_smaller", {0: v // 3 + 1, 1: -v, 2: v // 2}, 4))
+        B.append(("neg_largest_diag_equal", {0: v, 1: -v, 2: v // 5}, 4))
+        B.append(("neg_largest_diag_zero", {0: 0, 1: -v, 2: v // 7}, 4))
+        B.append(("neg_largest_diag_missing", {1: v // 9, 2: -v}, 3))
+        # equal magnitudes, opposite signs: position order decides (schemes 0, 3, 4, 5)
+        B.append(("signed_tie_large", {0: v // 11 + 1, 1: v, 2: -v, 3: -v}, 4))
+        B.append(("signed_tie_small", {0: v, 1: -(v // 13 + 1), 2: v // 13 + 1, 3: v // 2}, 4))
+        # equal bit length and top 40 bits, differing lower down; equal over several limbs
+        if bits > 48:
+            d = rnd.randrange(1, 1 << 12)
+            B.append(("key_tie_low_digits", {0: v >> 3, 1: v, 2: -(v + d), 3: v + d - 1}, 4))
+            B.append(("key_tie_low_digits_small", {0: v, 1: -(v >> 4) - d, 2: (v >> 4) + d - 1, 3: -((v >> 4) + d)}, 4))
+        # ratios exactly on a dyadic tol, and one unit below it (scheme 4: |diag|/|largest|; scheme 3: |smallest|/|diag|)
+        for num, den in (((1, 2), (3, 8), (1, 1 << 20), (3, 10), (1, 1)) if bits in RATIO_BITS else ()):
+            w = v >> 21 if bits > 40 else v
+            B.append((f"ratio_{num}_{den}", {0: num * w, 1: den * w, 2: -(num * w - 1) if num * w > 1 else 7}, 3))
+            B.append((f"ratio_{num}_{den}_below", {0: num * w - 1 if num * w > 1 else 1, 1: -den * w, 2: den * w - 1}, 3))
+            B.append((f"ratio3_{num}_{den}", {0: den * w, 1: num * w, 2: -(den * w + 1)}, 3))
+            B.append((f"ratio3_{num}_{den}_below", {0: -den * w, 1: num * w - 1 if num * w > 1 else 1, 2: den * w + 2}, 3))
+        # 1/10 with tol 0.1: the double 0.1 is above 1/10, the diagonal is not taken
+        w = v >> 4 if bits > 8 else v
+        B.append(("ratio_1_10", {0: w, 1: 10 * w, 2: 3 * w}, 3))
+        B.append(("ratio3_1_10", {0: 10 * w, 1: -w, 2: 3 * w}, 3))
+        # explicit zeros first in the pattern (scheme 2), the diagonal among them
+        B.append(("zeros_first", {0: 0, 1: 0, 2: -v, 3: v // 3}, 4))
+    return B
+
+
+def _corpus_matrix(rnd, blocks, singular=False):
+    """a block lower-triangular matrix: each block's first column as crafted, its other columns small random values,
+    a few couplings into later blocks' rows (after the block's first column, so crafted columns stay clean)"""
+    n = sum(m for _, _, m in blocks)
+    ent = {}
+    s = 0
+    starts = []
+    for bi, (_, col0, m) in enumerate(blocks):
+        starts.append(s)
+        for r, v in col0.items():
+            ent[(s + r, s)] = v
+        for j in range(1, m):
+            for r in range(m):
+                if r == 0 and j == 1 and 0 not in col0 and bi % 2 == 0:
+                    continue       # the diagonal row of column s is the only source of row s: keep a missing diagonal missing
+                ent[(s + r, s + j)] = rnd.choice([1, -1]) * rnd.randrange(1, 1 << rnd.choice([3, 20, 63, 64, 100]))
+        s += m
+    # couplings: column c of a block into a row of a later block (never a later block's first column)
+    for bi in range(len(blocks) - 1):
+        for _ in range(2):
+            c = starts[bi] + rnd.randrange(1, blocks[bi][2])
+            r = starts[bi + 1] + rnd.randrange(blocks[bi + 1][2])
+            ent[(r, c)] = rnd.choice([1, -1]) * rnd.randrange(1, 1 << 40)
+    if singular:
+        # the last column a copy of the one before it: no eligible candidate once that one is committed
+        for key in [key for key in ent if key[1] == n - 1]:
+            del ent[key]
+        for (r, c), v in list(ent.items()):
+            if c == n - 2:
+                ent[(r, n - 1)] = v
+    return n, ent
+
+
+def _corpus_random(rnd):
+    """a small random signed matrix with many ties: values drawn from a pool of +-v, v from 1 up to 2^200"""
+    n = rnd.randint(2, 9)
+    pool = [rnd.choice([1, 2, 3, rnd.getrandbits(rnd.choice([8, 64, 65, 130, 200])) | 1]) for _ in range(rnd.randint(1, 4))]
+    dens = rnd.choice([0.4, 0.6, 0.9])
+    ent = {}
+    for j in range(n):
+        for i in range(n):
+            if i == j or rnd.random() < dens:
+                ent[(i, j)] = rnd.choice([1, -1]) * rnd.choice(pool) * rnd.choice([1, 1, 2])
+    return n, ent
+
+
+def corpus_matrices():
+    """[(name, n, {(row, col): value})], deterministic"""
+    import random
+    rnd = random.Random(CORPUS_SEED)
+    blocks = _corpus_blocks(rnd)
+    out = []
+    # the crafted blocks in both polarities, six or seven blocks to a matrix, in a shuffled order
+    both = []
+    for lab, col0, m in blocks:
+        both.append((lab, col0, m))
+        both.append((lab + "_neg", {r: -v for r, v in col0.items()}, m))
+    rnd.shuffle(both)
+    per = 10
+    for t in range(0, len(both), per):
+        chunk = both[t:t + per]
+        n, ent = _corpus_matrix(rnd, chunk)
+        out.append((f"crafted{t // per:02d}", n, ent))
+    # a singular column at the end of two crafted matrices
+    for t in range(2):
+        chunk = both[per * t:per * t + 3]
+        n, ent = _corpus_matrix(rnd, chunk, singular=True)
+        out.append((f"singular{t}", n, ent))
+    for t in range(20):
+        n, ent = _corpus_random(rnd)
+        out.append((f"random{t:02d}", n, ent))
+    return out
+
+
+def _slab_bytes(arrays):
+    import io
+    buf = io.BytesIO()
+    slabfile.save_to(buf, arrays)
+    return buf.getvalue()
+
+
+def run_corpus():
+    import gzip
+    import hashlib
+    slab, runs, mats = {}, [], []
+    with tempfile.TemporaryDirectory() as td:
+        for mi, (name, n, ent) in enumerate(corpus_matrices()):
+            trip = os.path.join(td, name + ".txt")
+            with open(trip, "w") as f:
+                f.write(f"{n} {n} {len(ent)}\n")
+                for (r, c), v in sorted(ent.items(), key=lambda e: (e[0][1], e[0][0])):
+                    f.write(f"{r + 1} {c + 1} {v}\n")
+            a_out = os.path.join(td, "a.slab")
+            subprocess.check_call([DRIVER, "order", "trip:" + trip, a_out, "0"], stderr=subprocess.DEVNULL)
+            a = slabfile.load(a_out)
+            assert np.array_equal(a["q"], np.arange(n)), name
+            for k in ("Ap", "Ai", "Alen", "Alimbs"):
+                slab[f"{name}.{k}"] = a[k]
+            mats.append(dict(name=name, n=n, nnz=int(len(a["Ai"]))))
+            for pivot in range(6):
+                for tol in (CORPUS_TOLS if pivot in (3, 4) else (1.0,)):
+                    out = os.path.join(td, "o.slab")
+                    subprocess.check_call([DRIVER, "window", "trip:" + trip, out, "0", "0", str(pivot), "0", repr(tol)],
+                                          stderr=subprocess.DEVNULL)
+                    d = slabfile.load(out)
+                    K, status = int(d["K"][0]), int(d["counters"][7])
+                    rid = len(runs)
+                    slab[f"r{rid:04d}.pinv"] = d["pinv"]
+                    runs.append(dict(id=rid, matrix=name, n=n, pivot=pivot, tol=tol, K=K, status=status,
+                                     digest=slabfile.factor_digest(d) if K > 0 else None, full=False,
+                                     counters={k: int(v) for k, v in zip(
+                                         ("N_upd", "B_read", "B_write", "N_src", "L_streamed", "maxlimbs", "K_done"),
+                                         d["counters"][:7])}))
+    raw = _slab_bytes(slab)
+    with open(os.path.join(HERE, "pivot_corpus.slab.gz"), "wb") as f:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0, compresslevel=9) as g:
+            g.write(raw)
+    # one record to a line: small, and a diff names the runs that changed
+    with open(os.path.join(HERE, "pivot_corpus.json"), "w") as f:
+        f.write('{"seed": %d, "tols": %s, "slab_sha256": "%s",\n' % (CORPUS_SEED, json.dumps(list(CORPUS_TOLS)),
+                                                                     hashlib.sha256(raw).hexdigest()))
+        f.write(' "matrices": [\n  ' + ",\n  ".join(json.dumps(m) for m in mats) + "],\n")
+        f.write(' "runs": [\n  ' + ",\n  ".join(json.dumps(r, separators=(",", ":")) for r in runs) + "]}\n")
+    print("pivot corpus:", len(mats), "matrices,", len(runs), "runs,",
+          sum(r["status"] != 0 for r in runs), "singular")
+
+
 def main():
     if sys.argv[1:] == ["solve"]:
         run_solve_cases()
+        return
+    if sys.argv[1:] == ["corpus"]:
+        run_corpus()
         return
     names = sys.argv[1:] or list(CASES)
     idx_path = os.path.join(HERE, "index.json")

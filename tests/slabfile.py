@@ -35,15 +35,20 @@ def load(path):
 def save(path, arrays):
     opener = gzip.open if str(path).endswith(".gz") else open
     with opener(path, "wb") as f:
-        f.write(b"SLAB0001")
-        for name, a in arrays.items():
-            a = np.ascontiguousarray(a)
-            code = _CODE[a.dtype]
-            f.write(name.encode().ljust(24, b"\0")[:24])
-            f.write(struct.pack("<iiq", code, 0, a.size))
-            raw = a.tobytes()
-            f.write(raw)
-            f.write(b"\0" * ((8 - len(raw) % 8) % 8))
+        save_to(f, arrays)
+
+
+def save_to(f, arrays):
+    """the slab bytes of `arrays` into the open binary file f"""
+    f.write(b"SLAB0001")
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        code = _CODE[a.dtype]
+        f.write(name.encode().ljust(24, b"\0")[:24])
+        f.write(struct.pack("<iiq", code, 0, a.size))
+        raw = a.tobytes()
+        f.write(raw)
+        f.write(b"\0" * ((8 - len(raw) % 8) % 8))
 
 
 FACTOR_KEYS = ("pinv", "Lp", "Li", "Llen", "Llimbs", "Up", "Ui", "Ulen", "Ulimbs",

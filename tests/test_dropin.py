@@ -64,6 +64,17 @@ def test_dropin_factorize_matches_reference(tmp_path, name, pivot, nrhs):
     assert got == want
 
 
+def test_dropin_scheme4_negative_largest_matches_reference(tmp_path):
+    """SLIP_TOL_LARGEST where the largest candidate of column 0 is negative: the reference takes the diagonal whatever
+    the ratio (pivot rules), so the drop-in must return pinv = identity here, not the largest row"""
+    trip = tmp_path / "A.txt"
+    trip.write_text("3 3 9\n1 1 1\n2 1 -1000000\n3 1 5\n1 2 2\n2 2 3\n3 2 7\n1 3 4\n2 3 1\n3 3 9\n")
+    for tol in ("0.5", "1"):
+        got, want = run_both([str(trip), "4", "1", tol, "0"])
+        assert got.startswith("check=0 check_corrupt=-4 ")
+        assert got == want, tol
+
+
 def test_dropin_error_paths_match_reference():
     """NULL arguments -> SLIP_INCORRECT_INPUT, a singular matrix -> SLIP_SINGULAR under three pivot schemes,
     then SLIP_delete_sparse on whatever came back (Tcov/cov_test.c:342-345,466-472,674-678)."""

@@ -52,9 +52,10 @@ def test_gpu_matches_oracle_on_fresh_seeds():
         Ap, Ai, Ax = oracle_lib.matgen(n, d, b, seed)
         Alen, Alimbs = np.sign(Ax).astype(np.int32), np.abs(Ax).astype(np.uint64)
         q = np.random.RandomState(seed).permutation(n).astype(np.int32)
-        for pivot in (3, 0, 5) if n < 1000 else (3,):
-            ref = oracle_lib.factorize(n, Ap, Ai, Alen, Alimbs, q, pivot=pivot, kmax=kmax)
-            got = sl.factorize(n, Ap, Ai, Alen, Alimbs, q, pivot=pivot, kmax=kmax, check=False)
+        for pivot in (3, 0, 5, 1, 2, 4) if n < 1000 else (3,):
+            tol = 0.5 if pivot == 4 else 1.0
+            ref = oracle_lib.factorize(n, Ap, Ai, Alen, Alimbs, q, pivot=pivot, tol=tol, kmax=kmax)
+            got = sl.factorize(n, Ap, Ai, Alen, Alimbs, q, pivot=pivot, tol=tol, kmax=kmax, check=False)
             assert got["status"] == ref["status"] and got["K"] == ref["K"]
             for k in ("pinv", "Lp", "Li", "Llen", "Llimbs", "Up", "Ui", "Ulen", "Ulimbs", "rholen", "rholimbs"):
                 assert np.array_equal(np.asarray(got[k]).astype(np.int64), np.asarray(ref[k]).astype(np.int64)), (seed, pivot, k)
