@@ -72,7 +72,7 @@ typedef struct slip_hip_info {
     int32_t lds_bytes;        /* dynamic LDS per worker                                   */
     int32_t short_commits;    /* columns whose pivot was published by the short commit chain (diagnostic) */
     int32_t committer_commits;         /* ... of those, by the committer workgroup */
-    int32_t farm_jobs, farm_items, pad2;   /* update queues opened to helpers; items helpers ran (diagnostic) */
+    int32_t farm_jobs, farm_items, batch_commits;   /* update queues opened to helpers; items helpers ran (diagnostic); columns the committer committed side by side */
     int32_t engine_commits, engine_sources; /* columns committed by the committer's chain engine from FULL packages; late sources it applied */
     int32_t retractions, reexports;        /* packages a worker took back because a source arrived; packages exported again */
 } slip_hip_info;

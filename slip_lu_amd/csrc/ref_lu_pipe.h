@@ -89,6 +89,7 @@ typedef struct SlipState {
     int64_t out_used;                               /* solve: limbs of the output slab in use                            */
     unsigned long long c_upd, c_read, c_write, c_src, c_streamed, c_maxdig, c_macs, c_short, c_farm;   /* c_farm: queues opened to helpers (low word), items helpers ran (high word); c_short: columns committed by the short chain (high word: by the committer) */
     unsigned long long c_eng, c_retract;            /* c_eng: columns committed by the committer's chain engine (low word), late sources it applied (high word); c_retract: packages retracted (low), exported again (high) */
+    unsigned long long c_batch;                     /* columns the committer committed side by side (its run of candidates-only columns) */
     unsigned long long prof[24];                    /* SLIP_PROFILE builds only */
 } SlipState;
 

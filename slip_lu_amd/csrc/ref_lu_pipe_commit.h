@@ -209,6 +209,191 @@ SLIP_DEV int slip_tol_small(uint64_t tol_m, int te, uint64_t num, uint64_t den)
 /* a pivot of the committer's ring: one-limb pivots keep what the in-lane arithmetic needs */
 struct SlipSmallPiv { uint64_t lo, inv; int ctz, sgn, small, bits; };
 
+/* the run: rho[kc-1] (lm digits in LDS) times Pw (la digits, chunk 0) -> the stage slot (at least two digits, whole limbs);
+ * its length, bit count and low limb (what slip_commit_mul gives) */
+template <int D> SLIP_DEV void slip_run_rho(const dig_t *Ms, int lm, const WR<1> &Pw, int la, dig_t *slotp, int *len_out, int *bits_out, uint64_t *lo_out)
+{
+    const int lane = slip_lane();
+    WR<D> A = wr_zero<D>();
+    A.d[0] = Pw.d[0];
+    const WR<D> Y = wr_mul<D>(A, la, wr_load<D>(Ms, lm));
+    const int len = wr_len<D>(Y);
+    const int cnt = len < 2 ? 2 : (len + 1) & ~1;
+#pragma unroll
+    for (int q = 0; q < D; q++) { const int c = 64 * q + lane; if (c < cnt) slotp[c] = Y.d[q]; }
+    const uint32_t top = len ? wr_digit<D>(Y, len - 1) : 0u;
+    *len_out = len; *bits_out = len ? 32 * len - slip_clz32(top) : 0;
+    *lo_out = (uint64_t) slip_readlane(Y.d[0], 0) | ((uint64_t) slip_readlane(Y.d[0], 1) << 32);
+}
+
+/* (c0) THE RUN.  The longest prefix of the batch whose columns are candidates-only packages that the load step neither sent
+ * back nor left undecided (no tie, no diagonal row left to the worker, no unknown pivot before them) carries nothing from
+ * column to column but rho, the slab cursors and the swaps: rho[kc+i] = rho[kc-1] * (a_kc ... a_kc+i) is a product of one-limb
+ * factors, the cursors are a prefix sum of sizes that depend on rho[kc+i-1]'s length and bits only, and the swaps are a few
+ * register operations.  So the products are formed side by side (one wave per column), then wave 0 (lane i: column kc+i)
+ * takes the sizes, the cursors and the capacity checks at once, and commits the columns up to the first that fails any check;
+ * that column and the rest of the batch are left to the serial step, which rejects it for the same reason as before.  What
+ * the serial step would have left behind -- the publish records, the rings, the mirror, the permutation stores (one wave,
+ * column after column), rho's record and digits, the cursors -- is left here the same way.  All threads (one barrier when
+ * there is a run); returns to wave 0 the columns committed (0: the serial step starts at column kc). */
+SLIP_DEVN int slip_commit_run_out(const SlipParams *Pg, uint32_t *lds, const int kc, const int nb, unsigned long long *nrun)
+{
+    const SlipParams &P = *Pg;
+    const int lane = slip_lane(), wave = slip_wave(), nw = slip_nwaves();
+    volatile int64_t *sv64 = (volatile int64_t *)(lds + SLIP_LDS_VARS);
+    const SlipCommitLayout Ly = slip_commit_layout(P.n, P.engine);
+    uint32_t *base = lds + SLIP_LDS_WORK;
+    const uint32_t *cbuf = base + Ly.cbuf;
+    uint32_t *pub = base + Ly.pub;
+    dig_t *stage = base + Ly.stage, *Ms = base + Ly.Ms;
+    uint32_t *ring_row = base + Ly.ring_row, *ring_disp = base + Ly.ring_disp, *ring_opos = base + Ly.ring_opos;
+    uint32_t *pr_lo0 = base + Ly.pr_lo0, *pr_lo1 = base + Ly.pr_lo1, *pr_inv0 = base + Ly.pr_inv0, *pr_inv1 = base + Ly.pr_inv1, *pr_meta = base + Ly.pr_meta;
+    uint32_t *ld_col = base + Ly.ld_col;
+    uint16_t *pinvm = (uint16_t *)(base + Ly.pinvm);
+    SlipPiv *Mrec = (SlipPiv *)(lds + SLIP_LDS_SCAN);
+    /* lane e: column kc + e's words from the load step */
+    const uint32_t *ce = cbuf + (lane < nb ? lane : 0) * SLIP_CBW;
+    const bool ok = lane < nb && ce[18] == 0u && ce[21] == 0u && !(ce[24] & 0x700u) && ce[30] == 0u;
+    const uint32_t ra0 = ce[26], ra1 = ce[27], rax = ce[28];
+    const int lm0 = slip_abs(Mrec->len), neg0 = Mrec->len < 0, brho0 = Mrec->bits;
+    int r = slip_ctz64(~slip_ballot(ok));
+    if (lm0 < 1 || lm0 > SLIP_CB_SLOTW - 6) r = 0;
+    if (r < 2) return 0;
+    /* (c0.1) rho of every column of the run: P_i = a_kc ... a_kc+i (built up along the wave's columns), then rho[kc-1] * P_i */
+    {
+        WR<1> Pw; Pw.d[0] = lane == 0 ? 1u : 0u;
+        int done = -1, neg = neg0;
+        for (int i = wave; i < r; i += nw) {
+            for (int e = done + 1; e <= i; e++) {
+                const uint32_t a0 = slip_readlane(ra0, e), a1 = slip_readlane(ra1, e), ax = slip_readlane(rax, e);
+                WR<1> A; A.d[0] = lane == 0 ? a0 : lane == 1 ? a1 : 0u;
+                Pw = wr_mul<1>(A, 2, Pw);
+                neg ^= (int)((ax >> 14) & 1u);
+            }
+            done = i;
+            const int la = wr_len<1>(Pw), tot = lm0 + la;
+            dig_t *sl = stage + i * SLIP_CB_SLOTW;
+            int len = -1, bits = 0; uint64_t lo = 0;                    /* -1: longer than the products the serial step forms */
+            if (tot <= 64) slip_run_rho<1>(Ms, lm0, Pw, la, sl, &len, &bits, &lo);
+            else if (tot <= 128) slip_run_rho<2>(Ms, lm0, Pw, la, sl, &len, &bits, &lo);
+            else if (tot <= 192) slip_run_rho<3>(Ms, lm0, Pw, la, sl, &len, &bits, &lo);
+            else if (tot <= 256) slip_run_rho<4>(Ms, lm0, Pw, la, sl, &len, &bits, &lo);
+            uint32_t *pb = pub + i * SLIP_PUBW;                         /* words 22..26: rho[kc+i] for the step below */
+            const uint32_t w_ = lane == 0 ? (uint32_t) len : lane == 1 ? (uint32_t) bits : lane == 2 ? (uint32_t) lo : lane == 3 ? (uint32_t)(lo >> 32) : (uint32_t) neg;
+            if (lane < 5) pb[22 + lane] = w_;
+        }
+    }
+    slip_block_sync();
+    if (wave != 0) return 0;
+    /* (c0.2) wave 0, lane i: column kc + i's sizes from rho[kc+i-1]'s length and bits (slip_committer's kind-0 step) */
+    const bool in = lane < r;
+    const uint32_t *pm = pub + (in ? lane : 0) * SLIP_PUBW, *pp = pub + (in && lane > 0 ? lane - 1 : 0) * SLIP_PUBW;
+    const int lp_ = (int) pm[22], pbits = (int) pm[23], pneg = (int) pm[26];
+    const uint64_t plo = (uint64_t) pm[24] | ((uint64_t) pm[25] << 32);
+    const int lm = lane == 0 ? lm0 : (int) pp[22], brho = lane == 0 ? brho0 : (int) pp[23];
+    const int nrows = (int) ce[16], nS = (int) ce[2], nB = (int) ce[6], nUc_all = (int) ce[3];
+    const uint64_t U_l = (uint64_t) ce[4];
+    const int nA = lm > 2 ? nS : 0, slot = (lm + 3) >> 1, slotw = (lm + 5) & ~1;
+    const int maxc = (int) ce[9] - SLIP_PP_BIAS + brho;
+    const int maxub_all = maxc > (int) ce[10] ? maxc : (int) ce[10];
+    const uint64_t L_b = (uint64_t) ce[5] + (uint64_t) nB * (uint64_t)((brho + 63) >> 6) + (lm <= 2 ? 2ull * (uint64_t) nS : 0ull);
+    const uint64_t preserve = (uint64_t)((maxub_all + 63) >> 6) + 1;
+    const uint64_t Lb_total = (uint64_t) nA * (uint64_t) slot + preserve + L_b, Ub_total = U_l + preserve;
+    const int nLc = nrows - nUc_all;
+    const uint64_t plimbs = (uint64_t)((lp_ + 1) >> 1);
+    const int64_t poff_rel = lm > 2 ? (int64_t)(rax & 0x3FFu) * slot : (int64_t) nA * slot;
+    const uint64_t lalloc = (uint64_t) nA * (uint64_t) slot + (lm > 2 ? 0ull : plimbs);
+    int bad = lp_ < 1 || lm < 1;
+    {
+        const bool A_ok = lm + 2 <= P.xcap && lm + 2 <= 256;
+        if (lm > SLIP_CB_SLOTW - 6 || slotw > SLIP_CB_SLOTW || (lm > 2 && !A_ok)) bad = 1;
+        if (nB > 0) {
+            const int Wn = (((int) ce[7] - SLIP_PP_BIAS + brho + 31) >> 5) + (((int) ce[8] + 31) >> 5) + 1;
+            if (Wn > P.wcap || Wn > P.xcap || Wn > P.invcap) bad = 1;
+        }
+        if (P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) bad = 1;
+    }
+    /* the cursors before each column: an exclusive prefix sum over the run */
+    const int64_t dLnz = in ? (int64_t) nLc : 0, dLnl = in ? (int64_t) Lb_total : 0, dUnz = in ? (int64_t) nUc_all + 1 : 0, dUnl = in ? (int64_t)(U_l + plimbs) : 0;
+    int64_t Lnz_ = sv64[SV_LNZ / 2], Lnl_ = sv64[SV_LNL / 2], Unz_ = sv64[SV_UNZ / 2], Unl_ = sv64[SV_UNL / 2];
+    auto rl64 = [&](int64_t v, int e) -> int64_t { return (int64_t)((uint64_t) slip_readlane((uint32_t) v, e) | ((uint64_t) slip_readlane((uint32_t)((uint64_t) v >> 32), e) << 32)); };
+    for (int e = 0; e < r - 1; e++) {
+        const int64_t x0 = rl64(dLnz, e), x1 = rl64(dLnl, e), x2 = rl64(dUnz, e), x3 = rl64(dUnl, e);
+        if (e < lane) { Lnz_ += x0; Lnl_ += x1; Unz_ += x2; Unl_ += x3; }
+    }
+    if (Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) bad = 1;
+    if (Unz_ + nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) bad = 1;
+    const int rc = slip_ctz64(~slip_ballot(in && !bad));
+    if (rc == 0) return 0;
+    /* (c0.3) the swaps, in column order (the row at position j: the last swap of the batch that displaced a row there; the pivot
+     * row's position: the last swap that displaced it) */
+    uint32_t bs_row = 0xFFFFFFFFu, bs_disp = 0xFFFFFFFFu, bs_opos = 0xFFFFFFFFu;
+    const uint32_t h17 = ce[17], h25 = ce[25], h29 = ce[29];
+    for (int e = 0; e < rc; e++) {
+        uint32_t im2 = slip_readlane(h17, e), prow = slip_readlane(h25, e), ppos = slip_readlane(h29, e);
+        const uint64_t m1 = slip_ballot(lane < e && bs_opos == (uint32_t)(kc + e));
+        const uint64_t m2 = slip_ballot(lane < e && bs_disp == prow);
+        const uint32_t d1 = slip_readlane(bs_disp, m1 ? 63 - slip_clz64(m1) : 0), o2 = slip_readlane(bs_opos, m2 ? 63 - slip_clz64(m2) : 0);
+        if (m1) im2 = d1;
+        if (m2) ppos = o2;
+        if (lane == e) { bs_row = prow; bs_disp = im2; bs_opos = ppos; }
+    }
+    /* (c0.4) lane i < rc: column kc + i's pivot record, publish record and ring entries */
+    const bool cm = lane < rc;
+    const int j = kc + lane, s_ = j & (SLIP_CB_RING - 1);
+    SlipPiv pr; pr.off = Lnl_ + poff_rel; pr.len = pneg ? -lp_ : lp_; pr.bits = pbits; pr.invlen = 0; pr.pad = 0; pr.lo = plo;
+    {
+        const int z = lp_ <= 2 && plo ? slip_ctz64(plo) : 0;
+        pr.ctz = z; pr.inv64 = lp_ <= 2 && plo ? slip_inv64(plo >> z) : 0;
+    }
+    const int64_t nUnz = Unz_ + nUc_all + 1, nLnz = Lnz_ + nLc, nUnl = Unl_ + (int64_t)(U_l + plimbs), nLnl = Lnl_ + (int64_t) Lb_total;
+    if (cm) {
+        uint32_t *pb = pub + lane * SLIP_PUBW;
+        pb[0] = bs_row; pb[1] = bs_opos; pb[2] = bs_disp; pb[3] = (uint32_t) pr.len; pb[4] = (uint32_t) pbits; pb[5] = (uint32_t) lp_;
+        pb[6] = 0u; pb[7] = 0u;
+        pb[8] = (uint32_t) pr.off; pb[9] = (uint32_t)((uint64_t) pr.off >> 32); pb[10] = (uint32_t) lalloc; pb[11] = (uint32_t)(lalloc >> 32);
+        pb[12] = (uint32_t) nUnz; pb[13] = (uint32_t)((uint64_t) nUnz >> 32); pb[14] = (uint32_t) nLnz; pb[15] = (uint32_t)((uint64_t) nLnz >> 32);
+        pb[16] = (uint32_t) nUnl; pb[17] = (uint32_t)((uint64_t) nUnl >> 32); pb[18] = (uint32_t) nLnl; pb[19] = (uint32_t)((uint64_t) nLnl >> 32);
+        pb[20] = ce[20]; pb[21] = 0u;
+        const int small = lp_ <= 2;
+        pr_lo0[s_] = (uint32_t) plo; pr_lo1[s_] = (uint32_t)(plo >> 32); pr_inv0[s_] = (uint32_t) pr.inv64; pr_inv1[s_] = (uint32_t)(pr.inv64 >> 32);
+        pr_meta[s_] = (uint32_t)(pr.ctz & 0xFF) | (pneg ? 0x100u : 0u) | (small ? 0x200u : 0u) | ((uint32_t)(small ? pbits : 0) << 16);
+        ring_row[s_] = bs_row; ring_disp[s_] = bs_disp; ring_opos[s_] = bs_opos;
+        ld_col[s_] = 0xFFFFFFFFu;                                       /* its L values are long: not in the engine's ring */
+    }
+    /* the mirror and the permutation, column after column (successive columns touch the same entries; only stores of one wave
+     * to one address keep their order: see the serial step) */
+    for (int e = 0; e < rc; e++) {
+        const uint32_t row = slip_readlane(bs_row, e), disp = slip_readlane(bs_disp, e), opos = slip_readlane(bs_opos, e);
+        if (P.engine && lane == 0) { pinvm[row] = (uint16_t)(kc + e); pinvm[disp] = (uint16_t) opos; }
+#ifndef SLIP_EMU_BUG_PERM
+        uint32_t *a4 = (uint32_t *) 0; uint32_t v4 = 0;
+        switch (lane) {
+            case 0: a4 = (uint32_t *) P.row_perm.at(kc + e); v4 = row; break;
+            case 1: a4 = (uint32_t *) P.row_perm.at((int) opos); v4 = disp; break;
+            case 2: a4 = (uint32_t *) P.pinv.at((int) row); v4 = (uint32_t)(kc + e); break;
+            case 3: a4 = (uint32_t *) P.pinv.at((int) disp); v4 = opos; break;
+            default: break;
+        }
+        if (a4) slip_st_u32(a4, v4);
+#endif
+    }
+    /* (c0.5) the chain as the serial step continues it: rho[kc+rc-1]'s record and digits, the cursors */
+    const int last = rc - 1;
+    if (lane == last) {
+        *Mrec = pr;
+        sv64[SV_LNZ / 2] = nLnz; sv64[SV_LNL / 2] = nLnl; sv64[SV_UNZ / 2] = nUnz; sv64[SV_UNL / 2] = nUnl;
+    }
+    {
+        const int ll = (int) slip_readlane((uint32_t) lp_, last);
+        const dig_t *src = stage + last * SLIP_CB_SLOTW;
+        for (int c = lane; c < ((ll + 1) & ~1); c += SLIP_WAVE) Ms[c] = src[c];
+    }
+    if (lane == 0) *nrun += (unsigned long long) rc;
+    slip_wave_sync_lds();
+    return rc;
+}
+
 /* the kernel body of the committer (block 0 of a launch with P.committer set) */
 #if SLIP_PROFILE == 2 && !defined(SLIP_EMULATE)
 /* the committer's profile build: calibration, in place -- what a dependent LDS read, a dependent VALU op and an s_memrealtime
@@ -525,19 +710,24 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
         }
         slip_block_sync();
         SLIP_CT(2);                                  /* 2: rho after a resynchronisation */
-        /* (c) the columns of the batch, one after the other, by wave 0 on LDS only */
+        /* (c0) the run of candidates-only columns whose pivots the load step has chosen, side by side */
+        const int run0 = slip_commit_run_out(&P, lds, kc, nb, eacc + 7);
+        SLIP_CT(14);                                 /* 14: the run */
+        /* (c) the rest of the batch, one column after the other, by wave 0 on LDS only */
         if (wave == 0) {
-            int nbc = 0, rej = -1;
+            int nbc = run0, rej = -1;
             /* what the chain carries from column to column lives in registers: the slab cursors, rho[j-1]'s record, the swaps of
              * this batch (lane e: column kc + e).  LDS is touched with whole-wave reads only (a dependent LDS round trip is
              * 30-40 ns here, and the old code made a hundred of them per column). */
             int64_t Lnz_ = sv64[SV_LNZ / 2], Lnl_ = sv64[SV_LNL / 2], Unz_ = sv64[SV_UNZ / 2], Unl_ = sv64[SV_UNL / 2];
             SlipPiv M = *Mrec;
-            uint32_t bs_row = 0xFFFFFFFFu, bs_disp = 0xFFFFFFFFu, bs_opos = 0xFFFFFFFFu;
+            /* (the swaps of the run: its publish records) */
+            const uint32_t *pr_ = pub + (lane < nbc ? lane : 0) * SLIP_PUBW;
+            uint32_t bs_row = lane < nbc ? pr_[0] : 0xFFFFFFFFu, bs_disp = lane < nbc ? pr_[2] : 0xFFFFFFFFu, bs_opos = lane < nbc ? pr_[1] : 0xFFFFFFFFu;
             const int xcap_ = P.xcap, wcapP = P.wcap, invcap_ = P.invcap, limb_cap_ = P.limb_cap, nworkers_ = P.nworkers;
             const int64_t Lcap_nz_ = P.Lcap_nz, Lcap_nl_ = P.Lcap_nl, Ucap_nz_ = P.Ucap_nz, Ucap_nl_ = P.Ucap_nl;
             uint32_t *const mbox0 = P.pkg.at() + (int64_t) nworkers_ * SLIP_PKG_WORDS;
-            for (int i = 0; i < nb; i++) {
+            for (int i = nbc; i < nb; i++) {
                 const int j = kc + i;
                 uint32_t *cb = cbuf + i * SLIP_CBW;
                 uint32_t *pb = pub + i * SLIP_PUBW;
@@ -1149,6 +1339,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
         if (eacc[3]) slip_agent_add_u64(&st->c_upd, eacc[3]);
         if (eacc[4]) slip_agent_add_u64(&st->c_macs, eacc[4]);
         if (eacc[5] || eacc[6]) slip_agent_add_u64(&st->c_eng, eacc[5] | (eacc[6] << 32));
+        if (eacc[7]) slip_agent_add_u64(&st->c_batch, eacc[7]);
     }
     SLIP_PROF_C(if (tid == 0) for (int q = 0; q < 24; q++) st->prof[q] = tacc_[q]);      /* (the workers do not stamp in this build) */
 }

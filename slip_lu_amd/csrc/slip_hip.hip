@@ -1880,7 +1880,7 @@ extern "C" int slip_hip_factor_info(const slip_hip_factor *f, slip_hip_info *o)
     o->short_commits = (int32_t)(uint32_t) h->c_short; o->committer_commits = (int32_t)(h->c_short >> 32);
     o->farm_jobs = (int32_t)(uint32_t) h->c_farm; o->farm_items = (int32_t)(h->c_farm >> 32);
     o->engine_commits = (int32_t)(uint32_t) h->c_eng; o->engine_sources = (int32_t)(h->c_eng >> 32);
-    o->retractions = (int32_t)(uint32_t) h->c_retract; o->reexports = (int32_t)(h->c_retract >> 32); o->pad2 = 0;
+    o->retractions = (int32_t)(uint32_t) h->c_retract; o->reexports = (int32_t)(h->c_retract >> 32); o->batch_commits = (int32_t) h->c_batch;
     return SLIP_HIP_OK;
 }
 
