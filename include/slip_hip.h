@@ -17,6 +17,8 @@
  *        SLIP_LU/Source/SLIP_LU_solve.c:41-86 (slip_forward_sub.c, slip_array_mul.c, slip_back_sub.c)
  *   slip_hip_factor_check,               <->  SLIP_check_solution (integer form)
  *   slip_hip_check_solution                   SLIP_LU/Source/SLIP_check_solution.c:31-113, SLIP_LU.h:988-993
+ *   slip_hip_factor_solve_transpose,     <->  no counterpart: the reference solves A x = b only (KLU's klu_tsolve,
+ *   slip_hip_factor_check_transpose           UMFPACK's A' system are the transposed solves of other sparse LUs)
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
  *
  * The GMP-typed drop-in  SLIP_LU_factorize(L,U,A,S,rhos,pinv,option)  built on
@@ -176,6 +178,30 @@ int slip_hip_check_solution(int32_t n, const int64_t *Ap, const int32_t *Ai, con
                             int32_t *first_bad_row, int64_t *bad_rows, void *stream);
 /* device time of the check kernel of the last slip_hip_factor_check, milliseconds */
 double slip_hip_factor_check_ms(const slip_hip_factor *f);
+
+/* Exact transposed solve on the same resident factors: A(:,q)^T x = b, the system slip_hip_factor_solve solves, transposed
+ * (the dual of an LP basis, a simplex code's BTRAN).  No second factorisation: the REF factorisation of the transpose of
+ * the factorised matrix, in the identity pivot order, is (U^T, L^T) with the same pivots, and the same substitution kernels
+ * run on that view of the factors (built on the device on the first call, kept until reset; no limb is copied).  Needs the
+ * complete factorisation (K == n); a handle from slip_hip_factor_from_factors works too.
+ *   b: dense, nrhs columns of n entries by pivot POSITION -- b[c*n + k] pairs with column q[k] of A;
+ *   x: numerators over det = rho[n-1] (the denominator of slip_hip_factor_solve) by ORIGINAL row id: x[c*n + i] is for row i
+ *      of A, i.e. for column i of A^T.  To solve A^T x = b_orig, pass b[k] = b_orig[q[k]] (the input-side counterpart of
+ *      SLIP_permute_x).
+ * Slabs, ownership and statuses as slip_hip_factor_solve. */
+int slip_hip_factor_solve_transpose(slip_hip_factor *f, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                    int32_t **xlen_out, uint64_t **xlimbs_out, int64_t *xnl_out, void *stream);
+/* Exact check of a transposed solve: for every position k, sum_i A(i, q[k]) * xnum_c[i] == det * b_c[k], with b and x exactly
+ * as slip_hip_factor_solve_transpose takes and returns them (a row repeated in a column of A keeps its LAST value, as in
+ * slip_hip_factor_check).  first_bad_pos[c] = the smallest position k with a nonzero residual (-1: none), bad_pos[c] = how
+ * many; statuses and rejected inputs as slip_hip_factor_check (nrhs < 1, a limb array longer than its capacity, a handle from
+ * slip_hip_factor_from_factors, an incomplete factorisation: SLIP_HIP_INCORRECT_INPUT). */
+int slip_hip_factor_check_transpose(slip_hip_factor *f, int32_t nrhs,
+                                    const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                                    const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                    int32_t *first_bad_pos, int64_t *bad_pos, void *stream);
+/* device ms of the last transposed solve's substitution kernels; *view_ms (may be NULL): the view build of that call, 0 if reused */
+double slip_hip_factor_solve_transpose_ms(const slip_hip_factor *f, double *view_ms);
 
 /* Subtree farm (no counterpart in the reference, which has no parallelism): multiply the K committed
  * columns by per-column scales on the device -- L(:,k) and rho[k] by scale[k], an entry of U in the row whose pivot sits

@@ -35,7 +35,8 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_free", "slip_hip_wave_op_test", "slip_hip_version",
            "slip_hip_factor_phase_cycles", "slip_hip_factor_solve", "slip_hip_factor_solve_ms",
            "slip_hip_factor_from_factors", "slip_hip_factor_rescale", "slip_hip_factor_set_prefix", "slip_hip_pool_release", "slip_hip_read_triplet", "slip_hip_write_triplet",
-           "slip_hip_factor_check", "slip_hip_check_solution", "slip_hip_factor_check_ms")
+           "slip_hip_factor_check", "slip_hip_check_solution", "slip_hip_factor_check_ms",
+           "slip_hip_factor_solve_transpose", "slip_hip_factor_check_transpose", "slip_hip_factor_solve_transpose_ms")
 
 _libs = {}
 
@@ -91,5 +92,11 @@ def load(path=None):
     lib.slip_hip_check_solution.restype = C.c_int
     lib.slip_hip_factor_check_ms.argtypes = [vp]
     lib.slip_hip_factor_check_ms.restype = C.c_double
+    lib.slip_hip_factor_solve_transpose.argtypes = lib.slip_hip_factor_solve.argtypes
+    lib.slip_hip_factor_solve_transpose.restype = C.c_int
+    lib.slip_hip_factor_check_transpose.argtypes = lib.slip_hip_factor_check.argtypes
+    lib.slip_hip_factor_check_transpose.restype = C.c_int
+    lib.slip_hip_factor_solve_transpose_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.slip_hip_factor_solve_transpose_ms.restype = C.c_double
     _libs[path] = lib
     return lib

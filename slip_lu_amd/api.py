@@ -235,6 +235,20 @@ class Factorization:
     def solve(self, blen, blimbs, nrhs=1, stream=None):
         """REF forward/back substitution on the resident factors (slip_hip_factor_solve): dense b in
         original row order as a limb slab -> (xlen, xlimbs) numerators over det by pivot position."""
+        return self._solve("slip_hip_factor_solve", blen, blimbs, nrhs, stream)
+
+    def solve_transpose(self, blen, blimbs, nrhs=1, stream=None):
+        """The transposed system on the same resident factors (slip_hip_factor_solve_transpose): A(:,q)^T x = b, no second
+        factorisation.  b is dense by pivot POSITION -- b[c*n + k] pairs with column q[k] of A -- and the numerators over
+        det = rho[n-1] (the denominator of `solve`) come back by ORIGINAL row id: x[c*n + i] is for row i of A.  To solve
+        A^T x = b_orig, pass b[k] = b_orig[q[k]]:
+
+            xlen, xlimbs = f.solve_transpose(*ints_to_slab(b_orig[q]))      # x[i] = xnum[i] / det
+
+        Returns (xlen, xlimbs) as `solve` does."""
+        return self._solve("slip_hip_factor_solve_transpose", blen, blimbs, nrhs, stream)
+
+    def _solve(self, fn, blen, blimbs, nrhs, stream):
         blen = np.ascontiguousarray(blen, dtype=np.int32)
         blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
         if blen.size != self.n * nrhs:
@@ -242,10 +256,10 @@ class Factorization:
         if blimbs.size == 0:
             blimbs = np.zeros(1, dtype=np.uint64)
         pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
-        rc = self.lib.slip_hip_factor_solve(self.h, int(nrhs), blen.ctypes.data, blimbs.ctypes.data,
-                                            C.byref(pl), C.byref(px), C.byref(nl), C.c_void_p(stream or 0))
+        rc = getattr(self.lib, fn)(self.h, int(nrhs), blen.ctypes.data, blimbs.ctypes.data,
+                                   C.byref(pl), C.byref(px), C.byref(nl), C.c_void_p(stream or 0))
         if rc:
-            raise SlipError(rc, "slip_hip_factor_solve")
+            raise SlipError(rc, fn)
         xlen = np.ctypeslib.as_array(C.cast(pl, C.POINTER(C.c_int32)), shape=(self.n * nrhs,)).copy()
         xlimbs = (np.ctypeslib.as_array(C.cast(px, C.POINTER(C.c_uint64)), shape=(nl.value,)).copy()
                   if nl.value else np.zeros(0, np.uint64))
@@ -256,6 +270,15 @@ class Factorization:
     def check(self, blen, blimbs, xlen, xlimbs, nrhs=1, stream=None):
         """Exact check of a solve on the device (slip_hip_factor_check): A(:,q) xnum_c == det b_c, with b as `solve` takes
         it and (xlen, xlimbs) as `solve` returns them.  Returns (ok, first_bad_row int32[nrhs], bad_rows int64[nrhs])."""
+        return self._check("slip_hip_factor_check", blen, blimbs, xlen, xlimbs, nrhs, stream)
+
+    def check_transpose(self, blen, blimbs, xlen, xlimbs, nrhs=1, stream=None):
+        """Exact check of a transposed solve on the device (slip_hip_factor_check_transpose): for every position k,
+        sum_i A(i, q[k]) xnum_c[i] == det b_c[k], with b as `solve_transpose` takes it (by position) and (xlen, xlimbs) as it
+        returns them (by original row id).  Returns (ok, first_bad_pos int32[nrhs], bad_pos int64[nrhs])."""
+        return self._check("slip_hip_factor_check_transpose", blen, blimbs, xlen, xlimbs, nrhs, stream)
+
+    def _check(self, fn, blen, blimbs, xlen, xlimbs, nrhs, stream):
         nrhs = int(nrhs)
         blen, blimbs, bcap = _limb_arrays(blen, blimbs)
         xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
@@ -263,13 +286,19 @@ class Factorization:
             raise ValueError("blen and xlen must hold n*nrhs entries")
         first = np.zeros(max(nrhs, 1), np.int32)
         bad = np.zeros(max(nrhs, 1), np.int64)
-        rc = self.lib.slip_hip_factor_check(self.h, nrhs, blen.ctypes.data, blimbs.ctypes.data, bcap,
-                                            xlen.ctypes.data, xlimbs.ctypes.data, xcap, first.ctypes.data, bad.ctypes.data,
-                                            C.c_void_p(stream or 0))
-        return _check_result(rc, "slip_hip_factor_check", first[:nrhs], bad[:nrhs])
+        rc = getattr(self.lib, fn)(self.h, nrhs, blen.ctypes.data, blimbs.ctypes.data, bcap,
+                                   xlen.ctypes.data, xlimbs.ctypes.data, xcap, first.ctypes.data, bad.ctypes.data,
+                                   C.c_void_p(stream or 0))
+        return _check_result(rc, fn, first[:nrhs], bad[:nrhs])
 
     def check_ms(self):
         return self.lib.slip_hip_factor_check_ms(self.h)
+
+    def solve_transpose_ms(self):
+        """(device ms of the last transposed solve's substitution kernels, ms of that call's view build: 0 when it was reused)"""
+        view = C.c_double()
+        ms = self.lib.slip_hip_factor_solve_transpose_ms(self.h, C.byref(view))
+        return ms, view.value
 
     def pivots(self):
         """the pivot chain rho[0..K) only (signed limb counts, limbs): what the subtree farm exchanges"""

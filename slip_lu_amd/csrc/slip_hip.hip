@@ -293,6 +293,87 @@ static void slip_check_body(SlipCheckArgs A)
     }
 }
 
+/* The transposed view of complete factors (slip_hip_factor_solve_transpose).  With M = A(row_perm, q) the matrix that was
+ * factorised, every entry of a REF factorisation is a minor of M (L(i,k) = det M[{0..k-1,i},{0..k}], U(k,j) =
+ * det M[{0..k},{0..k-1,j}], rho_k = det M[0..k,0..k]); transposing swaps the rows and columns of every minor, so the REF
+ * factorisation of M^T in the identity pivot order is L' = U^T, U' = L^T with the same rho_k.  Both are laid out by pivot
+ * POSITION, from the factors in HBM: count per position, an exclusive scan, a scatter.  The entry records are copied as
+ * they are and index the other slab (L' reads the U limbs, U' the L limbs); no limb moves.
+ *   L'(:,p): for every U entry m of column j with pinv[Ui[m]] = p, row j and record Ue[m] (any order);
+ *   U'(:,p): for every L entry m of column k with pinv[Li[m]] = p, row k and record Le[m], the pivot (k = p) LAST, in the
+ *            slot kept for it (the back substitution reads Up[p+1]-1 as the pivot and skips it);
+ *   piv'[k]: piv[k] reading its digits from the U pivot record, its inverse cache empty. */
+struct SlipTViewArgs {
+    int32_t n, phase;                                                              /* 0 count, 1 scatter, 2 pivot records    */
+    const int64_t *Lp, *Up; const int32_t *Li, *Ui; const SlipEnt *Le, *Ue;       /* the complete factors                  */
+    const int32_t *pinv; const SlipPiv *piv;
+    int32_t *cntL, *cntU;      /* per position: entries of L'(:,p), non-pivot entries of U'(:,p); the fill counters of the scatter */
+    int64_t *tLp, *tUp; int32_t *tLi, *tUi; SlipEnt *tLe, *tUe; SlipPiv *tpiv;    /* the view                              */
+};
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_tview_kernel(SlipTViewArgs A)
+#else
+static void slip_tview_body(SlipTViewArgs A)
+#endif
+{
+    const int n = A.n;
+    if (A.phase == 2) {
+        const int64_t t0 = (int64_t) slip_block() * slip_nthreads() + slip_tid(), nt = (int64_t) slip_nblocks() * slip_nthreads();
+        for (int64_t k = t0; k < n; k += nt) {
+            SlipPiv r = A.piv[k];
+            r.off = A.Ue[A.Up[k + 1] - 1].off; r.invlen = 0; r.pad = 0;
+            A.tpiv[k] = r;
+        }
+        return;
+    }
+    /* one wavefront per source column: U's n columns, then L's */
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    for (int64_t it = wave0; it < 2 * (int64_t) n; it += nwaves) {
+        const int fromU = it < n, c = (int)(fromU ? it : it - n);
+        const int64_t m0 = fromU ? A.Up[c] : A.Lp[c], m1 = fromU ? A.Up[c + 1] : A.Lp[c + 1];
+        for (int64_t m = m0 + lane; m < m1; m += SLIP_WAVE) {
+            const int p = A.pinv[fromU ? A.Ui[m] : A.Li[m]];
+            if (fromU) {
+                if (A.phase == 0) { slip_atomic_add_i32(&A.cntL[p], 1); continue; }
+                const int64_t t = A.tLp[p] + slip_atomic_add_i32(&A.cntL[p], 1);
+                A.tLi[t] = c; A.tLe[t] = A.Ue[m];
+            } else {
+                if (A.phase == 0) { if (p != c) slip_atomic_add_i32(&A.cntU[p], 1); continue; }
+                const int64_t t = p == c ? A.tUp[p + 1] - 1 : A.tUp[p] + slip_atomic_add_i32(&A.cntU[p], 1);
+                A.tUi[t] = c; A.tUe[t] = A.Le[m];
+            }
+        }
+    }
+}
+
+/* the column pointers of the view: exclusive sums of cntL and of cntU + 1 (the pivot's slot), one workgroup, every thread a
+ * contiguous share; tmp: 2 words per wave */
+SLIP_DEV void slip_tview_scan_body(const SlipTViewArgs &A, uint64_t *tmp)
+{
+    const int tid = slip_tid(), T = slip_nthreads();
+    const int64_t n = A.n, per = (n + T - 1) / T, i0 = (int64_t) tid * per < n ? (int64_t) tid * per : n, i1 = i0 + per < n ? i0 + per : n;
+    uint64_t sL = 0, sU = 0;
+    for (int64_t i = i0; i < i1; i++) { sL += (uint64_t) A.cntL[i]; sU += (uint64_t) A.cntU[i] + 1u; }
+    uint64_t eL, eU, tL, tU;
+    slip_block_scan2(sL, sU, tmp, &eL, &eU, &tL, &tU);
+    for (int64_t i = i0; i < i1; i++) {
+        A.tLp[i] = (int64_t) eL; A.tUp[i] = (int64_t) eU;
+        eL += (uint64_t) A.cntL[i]; eU += (uint64_t) A.cntU[i] + 1u;
+    }
+    if (tid == 0) { A.tLp[n] = (int64_t) tL; A.tUp[n] = (int64_t) tU; }
+}
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(1024)
+slip_tview_scan_kernel(SlipTViewArgs A)
+{
+    __shared__ uint64_t tmp[32];
+    slip_tview_scan_body(A, tmp);
+}
+#endif
+
 #ifndef SLIP_EMULATE
 #define SLIP_MAX_WAVES 8                   /* at most 512 threads per worker: 256 VGPRs per lane, two waves per SIMD */
 template <bool FAST>
@@ -434,6 +515,14 @@ struct slip_hip_factor {
     /* slip_hip_factor_check: the row-ordered view of A, built on the first check (x index = pivot position) */
     int64_t *chk_rp, *chk_re; int32_t *chk_rx;
     double check_ms;
+    /* slip_hip_factor_solve_transpose: the transposed view of the complete factors (slip_tview_kernel), built on the first
+     * transposed solve, dropped at reset; its own pivot records and inverse cache (stride tinvcap), the handle's limbs */
+    int64_t *tLp, *tUp; int32_t *tLi, *tUi; SlipEnt *tLe, *tUe; SlipPiv *tpiv; uint32_t *tinvd; int32_t tinvcap;
+    int32_t *tpinv;        /* host copy of pinv: the output gather x[i] = y[pinv[i]] */
+    double tsolve_ms, tview_ms;
+    /* slip_hip_factor_check_transpose: the column view of A in q order (row k of the check = column q[k]), built on the first
+     * transposed check */
+    int64_t *chkt_rp, *chkt_re; int32_t *chkt_rx;
 };
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -448,6 +537,7 @@ struct slip_hip_factor {
 #define TRY_(call) do { const int e_ = (call); if (e_) return e_; } while (0)
 
 static void rescale_drop(slip_hip_factor *f);
+static void tview_drop(slip_hip_factor *f);
 
 /* Device buffers go through a process-level pool: the drop-in SLIP_LU_factorize creates and destroys a
  * handle per call, and a handle's private row arrays are gigabytes -- hipMalloc / hipFree of those cost milliseconds each.
@@ -857,6 +947,7 @@ extern "C" int slip_hip_factor_reset(slip_hip_factor *f)
     const int32_t n = f->n;
     if (!P->xd || !P->xrow) return SLIP_HIP_OUT_OF_MEMORY;
     if (f->rescaled) rescale_drop(f);
+    tview_drop(f);
     /* tickets double as row tags and are never reused -- until they would wrap: then every private row is untagged and
      * the count starts over (a launch draws at most one ticket per column plus one per worker) */
     if (f->hs.ticket > (1 << 30)) {
@@ -892,7 +983,9 @@ extern "C" void slip_hip_factor_destroy(slip_hip_factor *f)
     dev_free(P->Lready.p_); dev_free(P->pat); dev_free(P->rlist); dev_free(P->rpos); dev_free(P->srow); dev_free(P->gscratch); dev_free(P->gbitmap); dev_free(P->dbg); dev_free(P->pkg.p_); dev_free(P->jobs.p_); dev_free(P->sw_row.p_); dev_free(P->sw_pos.p_);
     dev_free(f->ds); dev_free(f->ident);
     dev_free(f->chk_rp); dev_free(f->chk_re); dev_free(f->chk_rx);
+    dev_free(f->chkt_rp); dev_free(f->chkt_re); dev_free(f->chkt_rx);
     rescale_drop(f);
+    tview_drop(f);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     free(f);
@@ -1107,10 +1200,9 @@ static int launch_device(const slip_hip_factor *f, int32_t W, hipStream_t stream
     return 0;
 }
 #else
-/* W emulated workgroups, each with its own LDS arena, run body(fast, Pw, lds) with the worker's parameters */
-template <class Body> static int launch_emulated(const slip_hip_factor *f, int32_t W, Body body)
+/* W emulated workgroups, each with its own LDS arena, run body(fast, Pw, lds) with the worker's share of P */
+template <class Body> static int launch_emulated(const slip_hip_factor *f, const SlipParams &P, int32_t W, Body body)
 {
-    const SlipParams P = f->P;
     const int fast = f->bitmap_in_lds && f->scratch_in_lds;
     const size_t words = (((size_t) f->lds_words + 64) + 3) & ~(size_t) 3;      /* every emulated workgroup's LDS 16-byte aligned, as on the device */
     uint32_t *lds_all = (uint32_t *) calloc((size_t) W * words, 4);
@@ -1161,7 +1253,7 @@ static int launch_columns(slip_hip_factor *f, hipStream_t stream)
     TRY_(launch_device(f, W, stream, slip_factor_kernel<true>, slip_factor_kernel<false>, f->P, f->ds));
 #else
     SlipState *ds = f->ds;
-    TRY_(launch_emulated(f, W, [ds](int fast, const SlipParams &Pw, uint32_t *lds) {
+    TRY_(launch_emulated(f, f->P, W, [ds](int fast, const SlipParams &Pw, uint32_t *lds) {
         if (Pw.committer && slip_block() == 0) { if (fast) slip_committer<true>(Pw, ds, lds); else slip_committer<false>(Pw, ds, lds); }
         else if (fast) slip_factor_worker<true>(Pw, ds, lds);
         else slip_factor_worker<false>(Pw, ds, lds);
@@ -1413,40 +1505,137 @@ extern "C" int slip_hip_factor_set_prefix(slip_hip_factor *f, int32_t K,
 #ifndef SLIP_SOLVE_HELPERS
 #define SLIP_SOLVE_HELPERS 16
 #endif
-static int launch_solve(slip_hip_factor *f, const SlipSolveArgs &A, int32_t *rhs_done, hipStream_t stream)
+/* one launch of slip_solve_kernel with the parameters P (the handle's, or those of its transposed view); its time is added to *ms */
+static int launch_solve(slip_hip_factor *f, SlipParams &P, const SlipSolveArgs &A, int32_t *rhs_done, hipStream_t stream, double *ms)
 {
-    f->P.t0 = f->hs.ticket;
+    P.t0 = f->hs.ticket;
     f->hs.stop = INT64_MAX; f->hs.exited = 0;
-    f->P.farm = 0; f->P.committer = 0; f->P.st = f->ds; f->P.in_factor = 0;
+    P.farm = 0; P.committer = 0; P.st = f->ds; P.in_factor = 0;
     for (int q_ = 0; q_ < 32; q_++) f->hs.farm_hint[q_] = 0;
     TRY_(upload_state(f, stream));
     /* one workgroup per right-hand side in flight; with fewer right-hand sides than workgroups, up to SLIP_SOLVE_HELPERS more
      * that only help with the long update queues (ref_lu_pipe_cols.h: slip_solve_worker) */
     int32_t W = f->nworkers;
     if (W > A.nrhs) {
-        int32_t H = f->no_farm || !f->P.jobs.p_ ? 0 : SLIP_SOLVE_HELPERS;
+        int32_t H = f->no_farm || !P.jobs.p_ ? 0 : SLIP_SOLVE_HELPERS;
         if (A.nrhs + H > W) H = W - A.nrhs;
         W = A.nrhs + H;
-        f->P.farm = H > 0;
+        P.farm = H > 0;
     }
     if (W < 1) W = 1;
-    f->P.nworkers = W;
-    if (f->P.farm) CK(hipMemsetAsync(f->P.jobs.p_, 0, (size_t) W * SLIP_JOB_WORDS * 4, stream));
+    P.nworkers = W;
+    if (P.farm) CK(hipMemsetAsync(P.jobs.p_, 0, (size_t) W * SLIP_JOB_WORDS * 4, stream));
     CK(hipEventRecord(f->ev0, stream));
 #ifndef SLIP_EMULATE
-    TRY_(launch_device(f, W, stream, slip_solve_kernel<true>, slip_solve_kernel<false>, f->P, f->ds, A, rhs_done));
+    TRY_(launch_device(f, W, stream, slip_solve_kernel<true>, slip_solve_kernel<false>, P, f->ds, A, rhs_done));
 #else
     SlipState *ds = f->ds;
-    TRY_(launch_emulated(f, W, [ds, A, rhs_done](int fast, const SlipParams &Pw, uint32_t *lds) {
+    TRY_(launch_emulated(f, P, W, [ds, A, rhs_done](int fast, const SlipParams &Pw, uint32_t *lds) {
         if (fast) slip_solve_worker<true>(Pw, ds, A, rhs_done, lds);
         else slip_solve_worker<false>(Pw, ds, A, rhs_done, lds);
     }));
 #endif
-    return launch_end(f, stream, &f->solve_ms);
+    return launch_end(f, stream, ms);
 }
 
-extern "C" int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
-                                     int32_t **xlen_out, uint64_t **xlimbs_out, int64_t *xnl_out, void *stream_v)
+/* ---- the transposed view of the complete factors (slip_tview_kernel), for slip_hip_factor_solve_transpose ---- */
+static void tview_drop(slip_hip_factor *f)
+{
+    dev_free(f->tLp); dev_free(f->tUp); dev_free(f->tLi); dev_free(f->tUi); dev_free(f->tLe); dev_free(f->tUe); dev_free(f->tpiv); dev_free(f->tinvd);
+    free(f->tpinv);
+    f->tLp = f->tUp = NULL; f->tLi = f->tUi = NULL; f->tLe = f->tUe = NULL; f->tpiv = NULL; f->tinvd = NULL; f->tinvcap = 0; f->tpinv = NULL;
+}
+
+static SlipTViewArgs tview_args(const slip_hip_factor *f)
+{
+    const SlipParams &P = f->P;
+    SlipTViewArgs A; memset(&A, 0, sizeof A);
+    A.n = f->n; A.Lp = P.Lp; A.Up = P.Up; A.Li = P.Li; A.Ui = P.Ui; A.Le = P.Le; A.Ue = P.Ue; A.pinv = P.pinv.p_; A.piv = P.piv.p_;
+    A.tLp = f->tLp; A.tUp = f->tUp; A.tLi = f->tLi; A.tUi = f->tUi; A.tLe = f->tLe; A.tUe = f->tUe; A.tpiv = f->tpiv;
+    return A;
+}
+
+static int tview_launch(SlipTViewArgs A, int phase, hipStream_t stream)
+{
+    A.phase = phase;
+#ifndef SLIP_EMULATE
+    int64_t blocks = phase == 2 ? ((int64_t) A.n + 255) / 256 : (2 * (int64_t) A.n + 3) / 4;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(slip_tview_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, A);
+    CK(hipGetLastError());
+#else
+    emu::launch(2, 128, [A]() { slip_tview_body(A); }, 256 * 1024, 1);
+#endif
+    return 0;
+}
+
+/* the view's inverse cache follows the handle's stride (a GROW_X reallocates both): a new one starts empty, so the pivot
+ * records are laid out again with invlen = 0 */
+static int tview_sync(slip_hip_factor *f, hipStream_t stream)
+{
+    if (f->tinvcap == f->P.invcap) return 0;
+    dev_free(f->tinvd); f->tinvd = NULL; f->tinvcap = 0;
+    TRY_(dev_alloc(&f->tinvd, (int64_t) f->n * f->P.invcap));
+    f->tinvcap = f->P.invcap;
+    return tview_launch(tview_args(f), 2, stream);
+}
+
+/* count by position, exclusive scan, scatter (slip_tview_kernel), from the factors in HBM; f->tview_ms: the device time */
+static int tview_build(slip_hip_factor *f, hipStream_t stream)
+{
+    SlipParams *P = &f->P;
+    const int32_t n = f->n;
+    const int64_t lnz = f->hs.Lnz, unz = f->hs.Unz;
+    int32_t *cnt = NULL;
+    int rc = 0;
+    if (!f->ident) A_(make_ident(f));                            /* (a handle around given factors has none yet) */
+    A_(dev_alloc(&f->tLp, (int64_t) n + 1)); A_(dev_alloc(&f->tUp, (int64_t) n + 1));
+    A_(dev_alloc(&f->tLi, unz)); A_(dev_alloc(&f->tLe, unz)); A_(dev_alloc(&f->tUi, lnz)); A_(dev_alloc(&f->tUe, lnz));
+    A_(dev_alloc(&f->tpiv, n)); A_(dev_alloc(&cnt, 2 * (int64_t) n));
+    if (!rc && !(f->tpinv = (int32_t *) malloc((size_t) n * 4))) rc = SLIP_HIP_OUT_OF_MEMORY;
+    DOWN_(f->tpinv, P->pinv.p_, (size_t) n * 4);
+    if (!rc) {
+        SlipTViewArgs A = tview_args(f);
+        A.cntL = cnt; A.cntU = cnt + n;
+        HIP_(hipEventRecord(f->ev0, stream));
+        HIP_(hipMemsetAsync(cnt, 0, (size_t) n * 8, stream));
+        A_(tview_launch(A, 0, stream));
+#ifndef SLIP_EMULATE
+        if (!rc) { hipLaunchKernelGGL(slip_tview_scan_kernel, dim3(1), dim3(1024), 0, stream, A); HIP_(hipGetLastError()); }
+#else
+        if (!rc) { uint64_t tmp[32]; emu::launch(1, 256, [A, &tmp]() { slip_tview_scan_body(A, tmp); }, 256 * 1024, 1); }
+#endif
+        HIP_(hipMemsetAsync(cnt, 0, (size_t) n * 8, stream));
+        A_(tview_launch(A, 1, stream));
+        A_(tview_sync(f, stream));
+        HIP_(hipEventRecord(f->ev1, stream)); HIP_(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIP_(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+        f->tview_ms = ms;
+    }
+    dev_free(cnt);
+    if (rc) tview_drop(f);
+    return rc;
+}
+
+/* the parameters of a transposed solve launch: the handle's, with the view's factors, pivot records and inverse cache and the
+ * identity permutation (the view's rows are positions).  Shared with the handle: x and its rows (tags from the one ticket
+ * counter), the scratch and bitmap, the job slots, the state.  Lo/Uo, Lready, the swap log and the package fields stay the
+ * handle's: the ungated sweep and the back substitution never read them. */
+static SlipParams tview_params(const slip_hip_factor *f)
+{
+    SlipParams P = f->P;
+    P.Lp = f->tLp; P.Li = f->tLi; P.Le = f->tLe; P.Llimbs = f->P.Ulimbs; P.Lcap_nz = f->hs.Unz; P.Lcap_nl = f->P.Ucap_nl;
+    P.Up = f->tUp; P.Ui = f->tUi; P.Ue = f->tUe; P.Ulimbs = f->P.Llimbs; P.Ucap_nz = f->hs.Lnz; P.Ucap_nl = f->P.Lcap_nl;
+    P.piv.p_ = f->tpiv; P.invd.p_ = f->tinvd;
+    P.pinv.p_ = f->ident; P.row_perm.p_ = f->ident;
+    return P;
+}
+
+/* slip_hip_factor_solve (transpose 0) and slip_hip_factor_solve_transpose (1): the launches, the grow-and-relaunch loop and
+ * the gather are one; the transposed solve runs on the view and gathers its output by row id, x[i] = y[pinv[i]] */
+static int solve_core(slip_hip_factor *f, int transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                      int32_t **xlen_out, uint64_t **xlimbs_out, int64_t *xnl_out, void *stream_v)
 {
     if (!f || nrhs <= 0 || !blen || !blimbs || !xlen_out || !xlimbs_out || !xnl_out) return SLIP_HIP_INCORRECT_INPUT;
     *xlen_out = NULL; *xlimbs_out = NULL; *xnl_out = 0;
@@ -1455,6 +1644,11 @@ extern "C" int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int
     if (!f->P.xd || !f->P.xrow) return SLIP_HIP_OUT_OF_MEMORY;
     hipStream_t stream = (hipStream_t) stream_v;
     SlipParams *P = &f->P;
+    double *ms = transpose ? &f->tsolve_ms : &f->solve_ms;
+    if (transpose) {
+        f->tview_ms = 0;
+        if (!f->tLp) TRY_(tview_build(f, stream));
+    }
     const int64_t ne = (int64_t) n * nrhs;
     /* b: signed limb counts -> signed digit counts + offsets (zero high limbs trimmed) */
     SlipSlab bs;
@@ -1480,11 +1674,13 @@ extern "C" int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int
     HIP_(hipMemset(ddone, 0, (size_t) nrhs * 4));
     if (!rc) {
         SlipState *h = &f->hs;
-        f->solve_ms = 0;
+        *ms = 0;
         A.nrhs = nrhs; A.blen = dblen; A.boff = dboff; A.blimbs = dbl; A.olen = dolen; A.ooff = dooff; A.olimbs = dol;
         A.ocap = ostride * nrhs; A.ostride = ostride;
         for (int guard = 0; !rc && guard < 64; guard++) {
-            int e = launch_solve(f, A, ddone, stream);
+            int e;
+            if (!transpose) e = launch_solve(f, f->P, A, ddone, stream, ms);
+            else if (!(e = tview_sync(f, stream))) { SlipParams Pt = tview_params(f); e = launch_solve(f, Pt, A, ddone, stream, ms); }
             if (e) { rc = e; break; }
             DOWN_(hdone, ddone, (size_t) nrhs * 4);
             if (rc) break;
@@ -1517,18 +1713,22 @@ extern "C" int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int
             int64_t nl = 0;
             for (int64_t t = 0; t < ne; t++) { const int32_t d = xl[t]; nl += ((d < 0 ? -d : d) + 1) >> 1; }
             xlimbs = (uint64_t *) malloc((size_t)(nl > 0 ? nl : 1) * 8);
-            if (!xlimbs) rc = SLIP_HIP_OUT_OF_MEMORY;
+            int32_t *ol = transpose ? (int32_t *) malloc((size_t) ne * 4) : xl;     /* the output's counts, in its order */
+            if (!xlimbs || !ol) rc = SLIP_HIP_OUT_OF_MEMORY;
             else {
                 int64_t at = 0;
                 for (int64_t t = 0; t < ne; t++) {
-                    const int32_t d = xl[t], l = ((d < 0 ? -d : d) + 1) >> 1;
-                    if (l) memcpy(xlimbs + at, raw + hooff[t], (size_t) l * 8);
+                    const int64_t s = transpose ? t - t % n + f->tpinv[t % n] : t;       /* the region entry output t comes from */
+                    const int32_t d = xl[s], l = ((d < 0 ? -d : d) + 1) >> 1;
+                    if (l) memcpy(xlimbs + at, raw + hooff[s], (size_t) l * 8);
                     at += l;
-                    xl[t] = d < 0 ? -l : l;
+                    ol[t] = d < 0 ? -l : l;
                 }
-                *xlen_out = xl; *xlimbs_out = xlimbs; *xnl_out = nl;
-                xl = NULL; xlimbs = NULL;
+                *xlen_out = ol; *xlimbs_out = xlimbs; *xnl_out = nl;
+                if (!transpose) xl = NULL;
+                ol = NULL; xlimbs = NULL;
             }
+            if (transpose) free(ol);
         }
     }
     free(xl); free(xlimbs); slab_free(&bs); free(hdone); free(raw); free(hooff);
@@ -1536,7 +1736,25 @@ extern "C" int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int
     return rc;
 }
 
+extern "C" int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                     int32_t **xlen_out, uint64_t **xlimbs_out, int64_t *xnl_out, void *stream_v)
+{
+    return solve_core(f, 0, nrhs, blen, blimbs, xlen_out, xlimbs_out, xnl_out, stream_v);
+}
+
+extern "C" int slip_hip_factor_solve_transpose(slip_hip_factor *f, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                               int32_t **xlen_out, uint64_t **xlimbs_out, int64_t *xnl_out, void *stream_v)
+{
+    return solve_core(f, 1, nrhs, blen, blimbs, xlen_out, xlimbs_out, xnl_out, stream_v);
+}
+
 extern "C" double slip_hip_factor_solve_ms(const slip_hip_factor *f) { return f ? f->solve_ms : 0.0; }
+
+extern "C" double slip_hip_factor_solve_transpose_ms(const slip_hip_factor *f, double *view_ms)
+{
+    if (view_ms) *view_ms = f ? f->tview_ms : 0.0;
+    return f ? f->tsolve_ms : 0.0;
+}
 
 /* ---- exact solution check (SLIP_check_solution.c:31-113 as one integer test; kernel: slip_check_kernel) ---- */
 
@@ -1630,10 +1848,41 @@ static int check_core(int32_t n, int32_t nrhs, const int64_t *drp, const int64_t
     return rc;
 }
 
-extern "C" int slip_hip_factor_check(slip_hip_factor *f, int32_t nrhs,
-                                     const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
-                                     const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
-                                     int32_t *first_bad_row, int64_t *bad_rows, void *stream_v)
+/* the column view of the resident A in q order, for slip_hip_factor_check_transpose: "row" k of the check is column q[k] of A,
+ * its terms the column's entries, each multiplying x at the entry's row id */
+static int build_col_view(slip_hip_factor *f)
+{
+    const int32_t n = f->n;
+    int64_t *hAp = (int64_t *) malloc(((size_t) n + 1) * 8), *rp = (int64_t *) malloc(((size_t) n + 1) * 8), *re = NULL;
+    int32_t *hAi = (int32_t *) malloc((size_t)(f->annz > 0 ? f->annz : 1) * 4), *hq = (int32_t *) malloc((size_t) n * 4), *rx = NULL;
+    int rc = !hAp || !rp || !hAi || !hq ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    DOWN_(hAp, f->dAp, ((size_t) n + 1) * 8); DOWN_(hAi, f->dAi, (size_t) f->annz * 4); DOWN_(hq, f->dq, (size_t) n * 4);
+    const int64_t nz = rc ? 0 : hAp[n];
+    if (!rc) {
+        re = (int64_t *) malloc((size_t)(nz > 0 ? nz : 1) * 8); rx = (int32_t *) malloc((size_t)(nz > 0 ? nz : 1) * 4);
+        if (!re || !rx) rc = SLIP_HIP_OUT_OF_MEMORY;
+    }
+    if (!rc) {
+        int64_t t = 0;
+        rp[0] = 0;
+        for (int32_t k = 0; k < n; k++) {
+            for (int64_t e = hAp[hq[k]]; e < hAp[hq[k] + 1]; e++) { re[t] = e; rx[t] = hAi[e]; t++; }
+            rp[k + 1] = t;
+        }
+        if (dev_alloc(&f->chkt_rp, (int64_t) n + 1) || dev_alloc(&f->chkt_re, nz) || dev_alloc(&f->chkt_rx, nz)) rc = SLIP_HIP_OUT_OF_MEMORY;
+        UP_(f->chkt_rp, rp, ((size_t) n + 1) * 8); UP_(f->chkt_re, re, (size_t) nz * 8); UP_(f->chkt_rx, rx, (size_t) nz * 4);
+        if (rc) { dev_free(f->chkt_rp); dev_free(f->chkt_re); dev_free(f->chkt_rx); f->chkt_rp = NULL; f->chkt_re = NULL; f->chkt_rx = NULL; }
+    }
+    free(hAp); free(rp); free(re); free(hAi); free(hq); free(rx);
+    return rc;
+}
+
+/* slip_hip_factor_check (transpose 0: A(:,q) xnum == det b by row) and slip_hip_factor_check_transpose (1: A(:,q)^T xnum ==
+ * det b by position): the same kernel over the row view or the column view of the resident A */
+static int check_on_handle(slip_hip_factor *f, int transpose, int32_t nrhs,
+                           const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                           const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                           int32_t *first_bad, int64_t *bad, void *stream_v)
 {
     if (!f || f->factors_only || nrhs < 1 || !blen || !blimbs || !xlen || !xlimbs) return SLIP_HIP_INCORRECT_INPUT;
     const int32_t n = f->n;
@@ -1644,8 +1893,9 @@ extern "C" int slip_hip_factor_check(slip_hip_factor *f, int32_t nrhs,
     if (!rc) rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
     else memset(&xs, 0, sizeof xs);
     SlipParams *P = &f->P;
+    if (!rc && transpose && !f->chkt_rp) rc = build_col_view(f);
     /* the row view of the resident A, once per handle: x is indexed by pivot position, column q[p] -> p */
-    if (!rc && !f->chk_rp) {
+    if (!rc && !transpose && !f->chk_rp) {
         int64_t *hAp = (int64_t *) malloc(((size_t) n + 1) * 8), *rp = NULL, *re = NULL;
         int32_t *hAi = (int32_t *) malloc((size_t)(f->annz > 0 ? f->annz : 1) * 4), *hq = (int32_t *) malloc((size_t) n * 4), *qinv = (int32_t *) malloc((size_t) n * 4), *rx = NULL;
         if (!hAp || !hAi || !hq || !qinv) rc = SLIP_HIP_OUT_OF_MEMORY;
@@ -1675,14 +1925,32 @@ extern "C" int slip_hip_factor_check(slip_hip_factor *f, int32_t nrhs,
         }
         free(hl); free(ho);
     }
-    if (!rc) {
+    if (!rc && !transpose) {
         f->check_ms = 0;
         rc = check_core(n, nrhs, f->chk_rp, f->chk_re, f->chk_rx, f->dAlen, f->dAoff, f->dAlimbs, f->amaxdig,
-                        bs, blimbs, xs, xlimbs, ddlen, ddoff, P->Llimbs, dmaxdig, first_bad_row, bad_rows, (hipStream_t) stream_v, &f->check_ms);
-    }
+                        bs, blimbs, xs, xlimbs, ddlen, ddoff, P->Llimbs, dmaxdig, first_bad, bad, (hipStream_t) stream_v, &f->check_ms);
+    } else if (!rc)
+        rc = check_core(n, nrhs, f->chkt_rp, f->chkt_re, f->chkt_rx, f->dAlen, f->dAoff, f->dAlimbs, f->amaxdig,
+                        bs, blimbs, xs, xlimbs, ddlen, ddoff, P->Llimbs, dmaxdig, first_bad, bad, (hipStream_t) stream_v, NULL);
     dev_free(ddlen); dev_free(ddoff);
     slab_free(&bs); slab_free(&xs);
     return rc;
+}
+
+extern "C" int slip_hip_factor_check(slip_hip_factor *f, int32_t nrhs,
+                                     const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                                     const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                     int32_t *first_bad_row, int64_t *bad_rows, void *stream_v)
+{
+    return check_on_handle(f, 0, nrhs, blen, blimbs, b_limbs, xlen, xlimbs, x_limbs, first_bad_row, bad_rows, stream_v);
+}
+
+extern "C" int slip_hip_factor_check_transpose(slip_hip_factor *f, int32_t nrhs,
+                                               const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                                               const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                               int32_t *first_bad_pos, int64_t *bad_pos, void *stream_v)
+{
+    return check_on_handle(f, 1, nrhs, blen, blimbs, b_limbs, xlen, xlimbs, x_limbs, first_bad_pos, bad_pos, stream_v);
 }
 
 extern "C" double slip_hip_factor_check_ms(const slip_hip_factor *f) { return f ? f->check_ms : 0.0; }
