@@ -235,14 +235,33 @@ enum { SV_ERR = 0, SV_CNT0 = 1 /* 3 rotating work counters */, SV_MAXDIG = 4, SV
        SV_CUP = 53 /* the committer has been seen running */, SV_PPFL = 55 /* the frontier (threshold) the last pre-pass ran at */, SV_NOENG = 56 /* the column at which this WORKER last saw a pivot of more than one limb (full packages are not tried for a while); survives the columns */, SV_K1STAMP = 54 /* a full package is only exported beyond this frontier (the stamp of one that was sent back) */,
        SV_PKGVER = 60 /* version of this worker's exported package (0: none yet) */, SV_PKGX = 61 /* 1: exported and still valid */,
        SV_PKGF = 62 /* the frontier the package's positions were read at */ };
+/* what the pre-pass of the commit chain found (slip_prepass): one word each at sv[SV_PP + ..], in the package at
+ * SLIP_PKG_SUMS + .. and at the head of the committer's batch column */
+enum {
+    PP_VALID = 0,   /* the pre-pass stands: no source has been applied since */
+    PP_NCAND,       /* candidates listed */
+    PP_NS,          /* class-S rows (never updated, one limb) */
+    PP_NUC,         /* pivotal rows */
+    PP_UL,          /* ... their limbs */
+    PP_LB,          /* limb bound of the class-B rows (without rho[k-1]'s share) */
+    PP_NB,          /* class-B rows */
+    PP_MAXCB,       /* largest c of a class-B row (biased by SLIP_PP_BIAS) */
+    PP_MAXZH,       /* largest ctz of their rho[h] */
+    PP_MAXC,        /* largest c of any row (biased); 0: no nonzero non-pivotal row */
+    PP_MAXUB,       /* longest pivotal row (bits) */
+    PP_BEST,        /* best bound */
+    PP_NONS,        /* candidates that are not class S */
+    PP_DIAG         /* table index + 1 of the diagonal row when it is a candidate */
+};
 #define SLIP_PP_WORDS  14
+static_assert(PP_DIAG + 1 == SLIP_PP_WORDS, "the pre-pass sums");
 /* a column's package for the committer (ref_lu_pipe_commit.h), offsets in 32-bit words */
 #define SLIP_PKG_CANDS   16       /* a package lists at most this many candidates ... */
 #define SLIP_PKG_NROWMAX 256      /* ... of a pattern of at most this many rows (512 measured slower: the committer reads every row) */
 #define SLIP_PKG_HDR     0        /* 64-bit {k+1, version}: even = valid, odd = being written or retracted; a column may export again */
 #define SLIP_PKG_STAMP   2
 #define SLIP_PKG_NROWS   3
-#define SLIP_PKG_SUMS    4        /* SLIP_PP_WORDS words */
+#define SLIP_PKG_SUMS    4        /* SLIP_PP_WORDS words (PP_*) */
 #define SLIP_PKG_STAMP0  18
 #define SLIP_PKG_VER     19       /* the version the sums belong to (every candidate record carries it too) */
 #define SLIP_PKG_WORKER  20       /* the exporting worker: its verdict goes to ITS mailbox (the slot may be reused by column k + nworkers before the worker has read it) */
@@ -251,16 +270,56 @@ enum { SV_ERR = 0, SV_CNT0 = 1 /* 3 rotating work counters */, SV_MAXDIG = 4, SV
 #define SLIP_PKG_FULLMAX 128      /* a full package carries at most this many non-pivotal rows ... */
 #define SLIP_ENG_ROWS    256      /* ... which late sources may fill up to this many in the committer's chain engine */
 #define SLIP_MIRROR_MAX  16384    /* the chain engine keeps pinv in LDS (16-bit): matrices up to this dimension */
-#define SLIP_MBOX_HDR    32       /* a worker's mailbox, behind the package slots: the outcome words, then (full packages) the rows handed back */
-#define SLIP_MBOX_WORDS  (SLIP_MBOX_HDR + 4 * SLIP_ENG_ROWS)
-#define SLIP_PKG_OUT     0        /* the outcome words, as offsets into the exporting worker's MAILBOX (P.pkg.at() + nworkers * SLIP_PKG_WORDS + worker * SLIP_MBOX_WORDS) */
-#define SLIP_PKG_CAND    64       /* 6 words per candidate: table index, value (2), aux, position, version */
+#define SLIP_PKG_CAND    64       /* SLIP_PKG_CANDS candidate records (CAND_*) */
 #define SLIP_PKG_ROWS    160      /* kind 0: the rows of the pattern; kind 1: four arrays of SLIP_PKG_FULLMAX words: row, value (2), sign | history */
 #define SLIP_PKG_WORDS   704
+/* one candidate record of a package */
+enum {
+    CAND_T = 0,     /* index into the worker's row table (the committer's load step puts the row itself there) */
+    CAND_A0,        /* the one-limb value, low digit */
+    CAND_A1,        /* ... high digit */
+    CAND_AUX,       /* slot, digits and sign: slip_aux_* */
+    CAND_POS,       /* the row's position as the pre-pass read it (the load step: as it stands at the batch's first column) */
+    CAND_VER        /* version of the package the record belongs to */
+};
+#define SLIP_CAND_WORDS  6
+/* a worker's mailbox, behind the package slots (slip_mailbox): the outcome words, then (full packages) the rows handed back */
+#define SLIP_MBOX_HDR    32
+#define SLIP_MBOX_WORDS  (SLIP_MBOX_HDR + 4 * SLIP_ENG_ROWS)
+enum {
+    MB_VERDICT = 0, /* {version << 24 | k + 1}: committed; its negative: sent back */
+    MB_PROW,        /* the pivot row; of a full package that was sent back: why (SLIP_REJ_*) */
+    MB_PPOS,        /* the pivot row's position before the swap */
+    MB_SLEN,        /* rho[k]: signed digits */
+    MB_BITS,        /* ... bits */
+    MB_NFIN,        /* full package: rows handed back */
+    MB_POFF,        /* 64 bit: rho[k]'s limbs in the L slab */
+    MB_LALLOC = 8,  /* 64 bit: limbs of the L slab handed out to the column's direct rows */
+    MB_NLATE = 10   /* full package: sources the engine applied */
+};
+/* why the committer does not commit a package */
+enum { SLIP_REJ_AGAIN = 1 /* it is offered again later / the worker's business */, SLIP_REJ_FINAL = 2 /* for good */ };
+static_assert(SLIP_PKG_SUMS + SLIP_PP_WORDS <= SLIP_PKG_STAMP0, "package: the sums");
+static_assert(SLIP_PKG_NFULL < SLIP_PKG_CAND, "package: the header words");
+static_assert(SLIP_PKG_CAND + SLIP_CAND_WORDS * SLIP_PKG_CANDS <= SLIP_PKG_ROWS, "package: the candidate records");
+static_assert(SLIP_PKG_ROWS + 4 * SLIP_PKG_FULLMAX <= SLIP_PKG_WORDS, "package: the rows of a full package");
+static_assert(SLIP_PKG_ROWS + SLIP_PKG_NROWMAX <= SLIP_PKG_WORDS, "package: the rows of the pattern");
+static_assert(SLIP_PKG_CANDS <= SLIP_WAVE, "one candidate per lane");
+static_assert(MB_NLATE < SLIP_MBOX_HDR, "mailbox: the outcome words");
+
+/* the aux word of a class-S row (f_aux of the pre-pass, CAND_AUX of a candidate record) */
+SLIP_DEV uint32_t slip_aux_pack(uint32_t slot, int nd, int neg) { return slot | ((uint32_t) nd << 12) | (neg ? 1u << 14 : 0u); }
+SLIP_DEV uint32_t slip_aux_slot(uint32_t aux) { return aux & 0x3FFu; }      /* which slot of the L slab the pre-pass handed out to the row */
+SLIP_DEV int slip_aux_nd(uint32_t aux) { return (int)((aux >> 12) & 3u); }  /* digits of the value: 1 or 2 */
+SLIP_DEV uint32_t slip_aux_neg(uint32_t aux) { return (aux >> 14) & 1u; }   /* 1: the value is negative */
 
 SLIP_DEV int slip_sgn(int32_t slen) { return (slen > 0) - (slen < 0); }
 SLIP_DEV int slip_abs(int32_t v) { return v < 0 ? -v : v; }
 SLIP_DEV int slip_limbs(int32_t slen) { return (slip_abs(slen) + 1) >> 1; }
+
+/* column k's package slot; a worker's mailbox (its index as the caller holds it: a word of a record, or P.worker) */
+SLIP_DEV uint32_t *slip_pkg_slot(const SlipParams &P, int k) { return P.pkg.at() + (int64_t)(k % P.nworkers) * SLIP_PKG_WORDS; }
+SLIP_DEV uint32_t *slip_mailbox(const SlipParams &P, int64_t worker) { return P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + worker * SLIP_MBOX_WORDS; }
 
 SLIP_DEV uint64_t slip_shfl_up_u64(uint64_t v, int d)
 {
@@ -274,6 +333,14 @@ SLIP_DEV int slip_wave_max_i32(int v)
     const int lane = slip_lane();
     for (int d = 32; d >= 1; d >>= 1) { const int o = (int) slip_shfl_u32((uint32_t) v, lane ^ d); if (o > v) v = o; }
     return v;
+}
+
+/* minimum of a 64-bit key over the lanes of a wave (all lanes call): the high words, then the low words among the lanes that hold it */
+SLIP_DEV uint64_t slip_wave_min_u64(uint64_t key)
+{
+    const uint32_t mh = slip_wave_min_u32((uint32_t)(key >> 32));
+    const uint32_t ml = slip_wave_min_u32((uint32_t)(key >> 32) == mh ? (uint32_t) key : 0xFFFFFFFFu);
+    return ((uint64_t) mh << 32) | ml;
 }
 
 /* exclusive prefix sums of two values over the workgroup's threads; totals returned */

@@ -147,14 +147,11 @@ SLIP_DEV void slip_rlist_push(const SlipParams &P, volatile int32_t *sv, uint32_
  * so WHICH rows can be the pivot (bound against bound) does not depend on it.  The pre-pass classifies the rows, adds up
  * what the capacity checks need and lists the candidates; when the frontier arrives, one wave only has to multiply the
  * listed candidates, search among them and publish (slip_do_column, "the short commit chain").  Any source applied
- * afterwards invalidates it (sv[SV_PP] = 0: the sweep does that).
+ * afterwards invalidates it (sv[SV_PP + PP_VALID] = 0: the sweep does that).
  * Row table entry f_inf = class | (c + SLIP_PP_BIAS) << 2 with  bits(value) <= c + bits(rho[k-1]):
  *   class 0: pivotal or zero; 2: never updated, one limb (S: lane product or straight into the L slab, slot handed out
  *   here); 3: anything else (B: a wave item at commit time).
- * sv[SV_PP + ..]: 0 valid, 1 candidates, 2 S rows, 3 pivotal rows, 4 their limbs, 5 limb bound of the B rows (without
- * rho[k-1]'s share), 6 B rows, 7 largest c of a B row (biased), 8 largest ctz of their rho[h], 9 largest c (biased),
- * 10 longest pivotal row (bits), 11 best bound, 12 candidates that are not class S, 13 table index + 1 of the diagonal row
- * when it is a candidate.  Called by all threads; barriers inside. */
+ * The sums land in sv[SV_PP + PP_*] (ref_lu_pipe.h).  Called by all threads; barriers inside. */
 #define SLIP_PP_BIAS   (1 << 20)
 #define SLIP_PP_CAND   64               /* one candidate per lane of the committing wave */
 /* Two refinements on top of the bounds (round 3):
@@ -180,7 +177,7 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
     const int diagpref = scheme == 1 || scheme == 3 || scheme == 4;
     const int col = P.q[k];
     const int nrows = sv[SV_NROWS];
-    if (tid < SLIP_PP_WORDS) sv[SV_PP + tid] = tid == 11 && kind == 0 ? 0x7FFFFFFF : 0;
+    if (tid < SLIP_PP_WORDS) sv[SV_PP + tid] = tid == PP_BEST && kind == 0 ? 0x7FFFFFFF : 0;
     if (tid == SLIP_PP_WORDS) { sv[SV_PPF] = 0; sv[SV_TMP] = 0; sv[SV_TMP2] = 0; }
     /* the full package is a possibility only with the engine running, a committed predecessor and room for the fill */
     /* (a worker that has just seen a multi-limb pivot does not try for the next 64 columns: the values only grow) */
@@ -209,7 +206,7 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
                 const uint64_t xv = slip_limb0(P.xd + (int64_t) r * P.xcap);
                 f_k0[t] = (uint32_t) xv; f_k1[t] = (uint32_t)(xv >> 32);
                 f_meta[t] = xr.len < 0 ? 0x80000000u : 0u;
-                asgn = ((uint32_t) slip_abs(xr.len) << 12) | (xr.len < 0 ? 1u << 14 : 0u);
+                asgn = slip_aux_pack(0u, slip_abs(xr.len), xr.len < 0);
                 const uint64_t key = kind == 0 ? xv : ~xv;
                 if (key < smin) smin = key;
             } else {
@@ -243,7 +240,7 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
         /* S rows get their slots in the L slab now (slot index kept in the row's own x area, behind the value) */
         const uint64_t am = slip_ballot(isS);
         int abase = 0;
-        if (lane == 0 && am) abase = slip_atomic_add_i32((int32_t *) &sv[SV_PP + 2], slip_popc64(am));
+        if (lane == 0 && am) abase = slip_atomic_add_i32((int32_t *) &sv[SV_PP + PP_NS], slip_popc64(am));
         abase = (int) slip_bcast0_u32((uint32_t) abase);
         if (isS) {
             const int si = abase + slip_popc64(am & ((1ull << lane) - 1ull));
@@ -278,17 +275,17 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
         const uint32_t w_b = kind == 0 ? slip_wave_min_u32(best) : slip_wave_max_u32(best);
         const uint32_t w_fb = slip_wave_max_u32((uint32_t) fullbad);
         if (lane == 0) {
-            if (w_n) { slip_atomic_add_i32((int32_t *) &sv[SV_PP + 3], (int) w_n); slip_atomic_add_i32((int32_t *) &sv[SV_PP + 4], (int) w_u); }
-            if (w_nb) { slip_atomic_add_i32((int32_t *) &sv[SV_PP + 5], (int) w_s); slip_atomic_add_i32((int32_t *) &sv[SV_PP + 6], (int) w_nb); }
-            slip_atomic_max_i32((int32_t *) &sv[SV_PP + 7], (int) w_cb); slip_atomic_max_i32((int32_t *) &sv[SV_PP + 8], (int) w_zh);
-            slip_atomic_max_i32((int32_t *) &sv[SV_PP + 9], (int) w_c); slip_atomic_max_i32((int32_t *) &sv[SV_PP + 10], (int) w_up);
-            if (kind == 0) slip_atomic_min_i32((int32_t *) &sv[SV_PP + 11], (int) w_b); else slip_atomic_max_i32((int32_t *) &sv[SV_PP + 11], (int) w_b);
+            if (w_n) { slip_atomic_add_i32((int32_t *) &sv[SV_PP + PP_NUC], (int) w_n); slip_atomic_add_i32((int32_t *) &sv[SV_PP + PP_UL], (int) w_u); }
+            if (w_nb) { slip_atomic_add_i32((int32_t *) &sv[SV_PP + PP_LB], (int) w_s); slip_atomic_add_i32((int32_t *) &sv[SV_PP + PP_NB], (int) w_nb); }
+            slip_atomic_max_i32((int32_t *) &sv[SV_PP + PP_MAXCB], (int) w_cb); slip_atomic_max_i32((int32_t *) &sv[SV_PP + PP_MAXZH], (int) w_zh);
+            slip_atomic_max_i32((int32_t *) &sv[SV_PP + PP_MAXC], (int) w_c); slip_atomic_max_i32((int32_t *) &sv[SV_PP + PP_MAXUB], (int) w_up);
+            if (kind == 0) slip_atomic_min_i32((int32_t *) &sv[SV_PP + PP_BEST], (int) w_b); else slip_atomic_max_i32((int32_t *) &sv[SV_PP + PP_BEST], (int) w_b);
             if (w_fb) slip_atomic_max_i32((int32_t *) &sv[SV_PPF], 1);
         }
     }
     const uint64_t sbest = slip_block_min_u64(smin, scan_tmp);       /* barriers inside: the sums above are complete behind it */
-    const uint32_t bestb = (uint32_t) sv[SV_PP + 11];
-    const int any = sv[SV_PP + 9] != 0;                            /* a nonzero non-pivotal row exists */
+    const uint32_t bestb = (uint32_t) sv[SV_PP + PP_BEST];
+    const int any = sv[SV_PP + PP_MAXC] != 0;                            /* a nonzero non-pivotal row exists */
     for (int t0 = 0; t0 < nrows && any; t0 += T) {
         const int t = t0 + tid;
         int cand = 0;
@@ -302,13 +299,13 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
                     const uint64_t xv = (uint64_t) f_k0[t] | ((uint64_t) f_k1[t] << 32);
                     cand = (kind == 0 ? xv : ~xv) == sbest;
                 }
-                if (diagpref && (int) f_row[t] == col) { cand = 1; sv[SV_PP + 13] = t + 1; }
-                if (cand && cls != 2) sv[SV_PP + 12] = 1;
+                if (diagpref && (int) f_row[t] == col) { cand = 1; sv[SV_PP + PP_DIAG] = t + 1; }
+                if (cand && cls != 2) sv[SV_PP + PP_NONS] = 1;
             }
         }
         const uint64_t mC = slip_ballot(cand);
         int bC = 0;
-        if (lane == 0 && mC) bC = slip_atomic_add_i32((int32_t *) &sv[SV_PP + 1], slip_popc64(mC));
+        if (lane == 0 && mC) bC = slip_atomic_add_i32((int32_t *) &sv[SV_PP + PP_NCAND], slip_popc64(mC));
         bC = (int) slip_bcast0_u32((uint32_t) bC);
         if (cand) { const int at = bC + slip_popc64(mC & ((1ull << lane) - 1ull)); if (at < SLIP_PP_CAND) cl[at] = (uint32_t) t; }
     }
@@ -318,8 +315,8 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
      * knows, rho[Fl-1] -- x rho[Fl-1] / rho[h] against a_best rho[Fl-1]; the common factor rho[k-1] / rho[Fl-1] that is
      * still to come does not change the order.  A B candidate strictly on the far side can never be the pivot and leaves
      * the list; if all of them do, the column is a candidates-only package after all. */
-    if (sv[SV_PP + 12] && any && sbest != ~0ull && Fl >= 1 && sv[SV_PP + 1] >= 2 && sv[SV_PP + 1] <= SLIP_PP_CAND && P.committer) {
-        const int ncand0 = sv[SV_PP + 1], wave = slip_wave(), nw = slip_nwaves();
+    if (sv[SV_PP + PP_NONS] && any && sbest != ~0ull && Fl >= 1 && sv[SV_PP + PP_NCAND] >= 2 && sv[SV_PP + PP_NCAND] <= SLIP_PP_CAND && P.committer) {
+        const int ncand0 = sv[SV_PP + PP_NCAND], wave = slip_wave(), nw = slip_nwaves();
         const uint64_t av = kind == 0 ? sbest : ~sbest;
         const uint32_t a0 = (uint32_t) av, a1 = (uint32_t)(av >> 32);
         const int nd = a1 ? 2 : 1;
@@ -345,7 +342,7 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
             if (tid == 0) {
                 int m = 0;
                 for (int c = 0; c < ncand0; c++) if (cl[c] != 0xFFFFFFFFu) cl[m++] = cl[c];
-                sv[SV_PP + 1] = m; sv[SV_PP + 12] = 0;
+                sv[SV_PP + PP_NCAND] = m; sv[SV_PP + PP_NONS] = 0;
             }
         } else if (tid == 0) {
             /* some B candidate stays: the list is as the bounds made it (the marks are undone from the table) */
@@ -360,16 +357,56 @@ SLIP_DEV void slip_prepass(const SlipParams &P, const int k, const int tag, uint
                 if (diagpref && (int) f_row[t] == col) cand = 1;
                 if (cand) cl[m++] = (uint32_t) t;
             }
-            sv[SV_PP + 1] = m;
+            sv[SV_PP + PP_NCAND] = m;
         }
         slip_block_sync();
     }
     if (tid == 0) {
-        sv[SV_PP] = any && sv[SV_PP + 1] >= 1 && sv[SV_PP + 1] <= SLIP_PP_CAND;
+        sv[SV_PP + PP_VALID] = any && sv[SV_PP + PP_NCAND] >= 1 && sv[SV_PP + PP_NCAND] <= SLIP_PP_CAND;
         sv[SV_PPF] = (want_full && !sv[SV_PPF]) ? sv[SV_TMP] : -1;
         sv[SV_PPFL] = Fl;
     }
     slip_block_sync();
+}
+
+/* What a column whose candidates are class-S rows takes in the slabs, from the pre-pass sums and rho[k-1] (lm digits, brho
+ * bits): rho[k-1]'s share is added to every bound here, once, for the three places that commit such a column (the worker's
+ * short chain, the committer's serial step and its run).  get(w) is sum word PP_w wherever the caller keeps the sums. */
+struct SlipColSizes {
+    int lm, nA, slot, slotw;        /* class-S rows that go into the slab as products (one limb times a one-limb pivot stays in the lane), limbs / digits of one */
+    int nUc, nLc, maxub_all, Wn;    /* entries of U(:,k) without the pivot, of L(:,k); longest value (bits); digits a class-B row's update needs (0: no such row) */
+    uint64_t Lb_total, Ub_total;    /* limbs the column may take in the L / U slab (bounds) */
+};
+template <class G> SLIP_DEV SlipColSizes slip_col_sizes(G get, int nrows, int lm, int brho)
+{
+    SlipColSizes z;
+    const int nS = get(PP_NS), nB = get(PP_NB);
+    z.lm = lm; z.nA = lm > 2 ? nS : 0; z.slot = (lm + 3) >> 1; z.slotw = (lm + 5) & ~1;
+    const int maxc = get(PP_MAXC) - SLIP_PP_BIAS + brho;
+    z.maxub_all = maxc > get(PP_MAXUB) ? maxc : get(PP_MAXUB);
+    const uint64_t L_b = (uint64_t)(uint32_t) get(PP_LB) + (uint64_t) nB * (uint64_t)((brho + 63) >> 6) + (lm <= 2 ? 2ull * (uint64_t) nS : 0ull);
+    const uint64_t preserve = (uint64_t)((z.maxub_all + 63) >> 6) + 1;
+    z.Lb_total = (uint64_t) z.nA * (uint64_t) z.slot + preserve + L_b;
+    z.Ub_total = (uint64_t)(uint32_t) get(PP_UL) + preserve;
+    z.nUc = get(PP_NUC); z.nLc = nrows - z.nUc;
+    z.Wn = nB > 0 ? ((get(PP_MAXCB) - SLIP_PP_BIAS + brho + 31) >> 5) + ((get(PP_MAXZH) + 31) >> 5) + 1 : 0;
+    return z;
+}
+/* the capacities such a column is checked against, as values (the committer keeps them in registers along its chain) */
+struct SlipCaps { int xcap, wcap, invcap, limb_cap; int64_t Lcap_nz, Lcap_nl, Ucap_nz, Ucap_nl; };
+SLIP_DEV SlipCaps slip_caps(const SlipParams &P) { return SlipCaps{P.xcap, P.wcap, P.invcap, P.limb_cap, P.Lcap_nz, P.Lcap_nl, P.Ucap_nz, P.Ucap_nl}; }
+/* which of the checks every site makes the column fails (0: it fits), with the slab cursors before it: a product too long for the
+ * register path, a class-B row's update too wide, the L / U slab or index arrays full, a value above limb_cap */
+enum { SLIP_MISFIT_A = 1, SLIP_MISFIT_W = 2, SLIP_MISFIT_L = 4, SLIP_MISFIT_U = 8, SLIP_MISFIT_LIMB = 16 };
+SLIP_DEV int slip_col_misfit(const SlipCaps &c, const SlipColSizes &z, int64_t Lnz, int64_t Lnl, int64_t Unz, int64_t Unl)
+{
+    int bad = 0;
+    if (z.lm > 2 && !(z.lm + 2 <= c.xcap && z.lm + 2 <= 256)) bad |= SLIP_MISFIT_A;
+    if (z.Wn > c.wcap || z.Wn > c.xcap || z.Wn > c.invcap) bad |= SLIP_MISFIT_W;
+    if (Lnz + z.nLc > c.Lcap_nz || Lnl + (int64_t) z.Lb_total > c.Lcap_nl) bad |= SLIP_MISFIT_L;
+    if (Unz + z.nUc + 1 > c.Ucap_nz || Unl + (int64_t) z.Ub_total > c.Ucap_nl) bad |= SLIP_MISFIT_U;
+    if (c.limb_cap > 0 && (int)((z.maxub_all + 63) >> 6) > c.limb_cap) bad |= SLIP_MISFIT_LIMB;
+    return bad;
 }
 
 /* ------------------------------------------------------------------ */
@@ -419,7 +456,7 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
             SLIP_PROF_W(const unsigned long long tw0_ = slip_clock());
             int Fn;
             /* still dry: the exported package holds for every pivot below the frontier this worker knows */
-            if (GATED && pp_fresh && tid == 0 && sv[SV_PKGX]) slip_st_u32(P.pkg.at() + (int64_t)(k % P.nworkers) * SLIP_PKG_WORDS + SLIP_PKG_STAMP, (uint32_t) Fl);
+            if (GATED && pp_fresh && tid == 0 && sv[SV_PKGX]) slip_st_u32(slip_pkg_slot(P, k) + SLIP_PKG_STAMP, (uint32_t) Fl);
             Fn = -2;
             if (pp_want && sv[SV_NROWS] <= SLIP_TAB_CAP) {
                 if (!pp_fresh) {
@@ -427,7 +464,7 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
                     if (Fn >= 0 && Fn <= Fl) {       /* nothing to do but wait: classify the rows and list the pivot candidates meanwhile */
                         slip_prepass(P, k, tag, lds, Fl, b0);
                         pp_fresh = 1;
-                        SLIP_TRACE("worker: col %d prepass valid %d ncand %d nonS %d nrows %d full %d committer %d\n", k, (int) sv[SV_PP], (int) sv[SV_PP + 1], (int) sv[SV_PP + 12], (int) sv[SV_NROWS], (int) sv[SV_PPF], P.committer);
+                        SLIP_TRACE("worker: col %d prepass valid %d ncand %d nonS %d nrows %d full %d committer %d\n", k, (int) sv[SV_PP + PP_VALID], (int) sv[SV_PP + PP_NCAND], (int) sv[SV_PP + PP_NONS], (int) sv[SV_NROWS], (int) sv[SV_PPF], P.committer);
                         Fn = -2;
                     }
                 }
@@ -452,7 +489,7 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
                             SLIP_TL(tid == 0, k, 1);                 /* time line 1: package exported */
                             if (cur_io) { *cur_io = cur; return 2; }
                         }
-                    } else if (can_pkg && sv[SV_PP] && !sv[SV_PP + 12] && sv[SV_NROWS] <= SLIP_PKG_NROWMAX && sv[SV_PP + 1] <= SLIP_PKG_CANDS) {
+                    } else if (can_pkg && sv[SV_PP + PP_VALID] && !sv[SV_PP + PP_NONS] && sv[SV_NROWS] <= SLIP_PKG_NROWMAX && sv[SV_PP + PP_NCAND] <= SLIP_PKG_CANDS) {
                         /* a column whose candidates are all one-limb values is handed to the committer */
                         if (tid == 0) { sv[SV_PKGF] = sv[SV_PPFL]; if (sv[SV_PKGVER]) slip_agent_add_u64(&st->c_retract, 1ull << 32); }
                         slip_export_package(P, k, lds, sv[SV_PPFL], Fl);
@@ -502,7 +539,7 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
         cur = jn;
         /* this source changes the rows: what the pre-pass found no longer holds (also after this sweep was taken up again behind a
          * full package that came back: pp_fresh is per call, the flags are the column's) */
-        if (GATED) { pp_fresh = 0; if (tid == 0 && (sv[SV_PP] || sv[SV_PKGX])) { sv[SV_PP] = 0; if (sv[SV_PKGX]) slip_retract_package(P, k, sv); } }
+        if (GATED) { pp_fresh = 0; if (tid == 0 && (sv[SV_PP + PP_VALID] || sv[SV_PKGX])) { sv[SV_PP + PP_VALID] = 0; if (sv[SV_PKGX]) slip_retract_package(P, k, sv); } }
         if (GATED && jn >= sv[SV_F2] && P.engine && pp_want && cur_io && !sv[SV_NOK1] && !(sv[SV_NOENG] > 0 && k - sv[SV_NOENG] < 64) && k - Fl <= SLIP_K1_NEAR && jn >= 1 && jn > sv[SV_K1STAMP]      /* (a package of this column, if any, has just been retracted) */
             && sv[SV_NROWS] <= SLIP_TAB_CAP) {
             /* this column's turn is near and the next source's L column is not published yet (its worker is still in stage 2):
@@ -520,12 +557,12 @@ SLIP_DEV int slip_sweep(const SlipParams &P, SlipState *st, const int k, const i
                 if (sv[SV_CUP] && sv[SV_PKGVER] < 120 && k < (1 << 24) - 1) {
                     slip_prepass(P, k, tag, lds, jn, b0);               /* rows at positions >= jn travel with their values */
                     if (sv[SV_PPF] >= 1 && sv[SV_PPF] <= SLIP_PKG_FULLMAX) {
-                        if (tid == 0) { sv[SV_PKGF] = jn; sv[SV_PP] = 0; if (sv[SV_PKGVER]) slip_agent_add_u64(&st->c_retract, 1ull << 32); }
+                        if (tid == 0) { sv[SV_PKGF] = jn; sv[SV_PP + PP_VALID] = 0; if (sv[SV_PKGVER]) slip_agent_add_u64(&st->c_retract, 1ull << 32); }
                         slip_export_full(P, k, lds, jn, jn);
                         *cur_io = jn - 1;                            /* taken up again AT this source should the package come back */
                         return 2;
                     }
-                    if (tid == 0) { sv[SV_NOK1] = 1; sv[SV_PP] = 0; }   /* a value the engine does not take: no further attempts for this column */
+                    if (tid == 0) { sv[SV_NOK1] = 1; sv[SV_PP + PP_VALID] = 0; }   /* a value the engine does not take: no further attempts for this column */
                     slip_block_sync();
                 }
             }
@@ -724,7 +761,7 @@ SLIP_DEV int slip_publish_digits(dig_t *dst, const dig_t *src, int src_shared, i
 SLIP_DEV int slip_wait_verdict(const SlipParams &P, SlipState *st, uint32_t *lds, const int k, dig_t *b0, dig_t *b1, dig_t *b2)
 {
     volatile int32_t *sv = (volatile int32_t *)(lds + SLIP_LDS_VARS);
-    const uint32_t *pk = P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) P.worker * SLIP_MBOX_WORDS;      /* this worker's mailbox */
+    const uint32_t *pk = slip_mailbox(P, P.worker);      /* this worker's mailbox */
     for (;;) {
         slip_block_sync();
         if (slip_tid() == 0) {
@@ -734,7 +771,7 @@ SLIP_DEV int slip_wait_verdict(const SlipParams &P, SlipState *st, uint32_t *lds
                 SlipHints H;
                 if (P.farm) H = slip_farm_hints_load(st);
                 const int64_t stop = slip_ld_i64(&st->stop);
-                const int v = (int) slip_ld_u32(pk + SLIP_PKG_OUT), mine_ = (sv[SV_PKGVER] << 24) | (k + 1);      /* a verdict names the version it is about */
+                const int v = (int) slip_ld_u32(pk + MB_VERDICT), mine_ = (sv[SV_PKGVER] << 24) | (k + 1);      /* a verdict names the version it is about */
                 if (v == mine_) { res = 1; break; }
                 if (v == -mine_) { res = 0; break; }
                 if ((stop >> 8) < (int64_t) k || (int)(stop & 0xFF) == SLIPDEV_INTERNAL) { res = -1; break; }
@@ -764,9 +801,9 @@ SLIP_DEV void slip_takeover_full(const SlipParams &P, const int k, const int tag
     uint32_t *f_row = lds + SLIP_LDS_TAB, *f_pos = f_row + SLIP_TAB_CAP;
     const uint32_t *f_npi = lds + SLIP_LDS_ROWS;
     uint32_t *t_row = lds + SLIP_LDS_KEYS, *t_pos = t_row + SLIP_PAT_CAP;
-    const uint32_t *mb = P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) P.worker * SLIP_MBOX_WORDS;
-    const int nold = sv[SV_NROWS], nU = sv[SV_PP + 3];
-    const int nfin = (int) slip_ld_u32(mb + SLIP_PKG_OUT + 5);
+    const uint32_t *mb = slip_mailbox(P, P.worker);
+    const int nold = sv[SV_NROWS], nU = sv[SV_PP + PP_NUC];
+    const int nfin = (int) slip_ld_u32(mb + MB_NFIN);
     slip_block_sync();
     for (int t = tid; t < nold; t += T) {
         const uint32_t pi = f_npi[t];
@@ -822,7 +859,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     /* ---- phase 0: clear the pattern bitmap, take a snapshot of the commit frontier ---- */
     for (int w = tid; w < P.bm_words; w += T) bm[w] = 0;
     if (tid == 0) {
-        sv[SV_ERR] = 0; sv[SV_CNT0] = 0; sv[SV_CNT0 + 1] = 0; sv[SV_CNT0 + 2] = 0; sv[SV_MAXDIG] = 0; sv[SV_NROWS] = 0; sv[SV_ACNT] = 0; sv[SV_EST] = -1; sv[SV_PP] = 0; sv[SV_PKGX] = 0; sv[SV_PKGVER] = 0; sv[SV_ABORT] = 0; sv[SV_PPF] = -1; sv[SV_PKGK] = 0; sv[SV_NOK1] = 0; sv[SV_K1STAMP] = 0;
+        sv[SV_ERR] = 0; sv[SV_CNT0] = 0; sv[SV_CNT0 + 1] = 0; sv[SV_CNT0 + 2] = 0; sv[SV_MAXDIG] = 0; sv[SV_NROWS] = 0; sv[SV_ACNT] = 0; sv[SV_EST] = -1; sv[SV_PP + PP_VALID] = 0; sv[SV_PKGX] = 0; sv[SV_PKGVER] = 0; sv[SV_ABORT] = 0; sv[SV_PPF] = -1; sv[SV_PKGK] = 0; sv[SV_NOK1] = 0; sv[SV_K1STAMP] = 0;
         sv64[SV_LALLOC / 2] = 0; sv64[SV_LEXACT / 2] = 0;
         /* the ready frontier first: it never passes the commit frontier, also not between the two loads */
         sv[SV_F2] = slip_ld_i32(&st->F2);
@@ -879,8 +916,8 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             if (tid == 0) {
                 /* sent back: for good (a value the engine does not handle), or until this worker has applied the source
                  * the engine could not (its column was committed elsewhere): the next full package must be a later one */
-                const uint32_t *mb_ = P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) P.worker * SLIP_MBOX_WORDS;
-                if (slip_ld_u32(mb_ + SLIP_PKG_OUT + 1) != 1u) sv[SV_NOK1] = 1;
+                const uint32_t *mb_ = slip_mailbox(P, P.worker);
+                if (slip_ld_u32(mb_ + MB_PROW) != (uint32_t) SLIP_REJ_AGAIN) sv[SV_NOK1] = 1;
                 sv[SV_K1STAMP] = sv[SV_PKGF];
             }
             slip_block_sync();
@@ -927,12 +964,12 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
         if (v < 0) return SLIPDEV_ABORTED;
         adopted = v;
     }
-    const bool fastc = !adopted && try_early && nw >= 2 && sv[SV_PP] != 0;
+    const bool fastc = !adopted && try_early && nw >= 2 && sv[SV_PP + PP_VALID] != 0;
     uint32_t *ppcl = work + SLIP_CAND_CAP;                 /* the pre-pass's candidate list (table indices) */
     int r0_ = 0, pos0_ = 0; SlipRow xr0_; xr0_.len = 0; xr0_.h = 0; xr0_.bits = 0; xr0_.tag = 0;
     int c_t = -1, c_r = 0, c_pos = 0; SlipRow c_x = xr0_;  /* short chain, wave 0: this lane's candidate */
     if (fastc) {
-        if (wave == 0 && lane < sv[SV_PP + 1]) {
+        if (wave == 0 && lane < sv[SV_PP + PP_NCAND]) {
             c_t = (int) ppcl[lane]; c_r = (int) f_row[c_t];
             c_pos = slip_ld_i32(P.pinv.at(c_r));
             c_x = P.xrow[c_r];
@@ -1028,10 +1065,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             for (int c0 = 0; c0 < A.ncand; c0 += SLIP_WAVE) {
                 const int c = c0 + lane;
                 const uint64_t key = c < A.ncand ? key_of((int) A.cl[c]) : ~0ull;
-                /* 64-bit minimum over the wave: the high words first, the low words among the lanes that hold the minimum */
-                const uint32_t mh = slip_wave_min_u32((uint32_t)(key >> 32));
-                const uint32_t ml = slip_wave_min_u32((uint32_t)(key >> 32) == mh ? (uint32_t) key : 0xFFFFFFFFu);
-                const uint64_t wm = ((uint64_t) mh << 32) | ml;
+                const uint64_t wm = slip_wave_min_u64(key);
                 if (wm < mk) mk = wm;
             }
             int bt = -1;
@@ -1078,7 +1112,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
                 pxr.bits = (int)(key >> 40);
                 const int len_ = (pxr.bits + 31) >> 5;
                 pxr.len = (f_inf[bt] >> 31) ? -len_ : len_; pxr.h = -2; pxr.tag = tag;
-                pdirect = 1; poff = A.Lnl_ + (int64_t)(f_aux[bt] & 0x3FFu) * slot;
+                pdirect = 1; poff = A.Lnl_ + (int64_t) slip_aux_slot(f_aux[bt]) * slot;
             } else {
                 pxr = P.xrow[e_pivrow];
                 pdirect = pxr.h == -2;
@@ -1126,7 +1160,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     int ec = -1;                                 /* 0: committed early; > 0: a status; -1: the full pass below decides */
     if (adopted) {
         /* the committer has published this column's pivot: take over the outcome from this worker's mailbox */
-        const uint32_t *pk = P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) P.worker * SLIP_MBOX_WORDS;
+        const uint32_t *pk = slip_mailbox(P, P.worker);
         if (BMs) { const dig_t *Mg = slip_piv_digits(P, M); for (int c = tid; c < lm; c += T) Ms[c] = slip_ld_u32(Mg + c); }
         /* the position snapshot (pinv as the reference has it at column k): the value the pre-pass read at frontier stamp0, or
          * where the LAST swap in [stamp0, k) that displaced the row put it (positions of non-pivotal rows only ever grow, and a
@@ -1151,12 +1185,12 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             }
         }
         if (tid == 0) {
-            const int pr = (int) slip_ld_u32(pk + SLIP_PKG_OUT + 1);
-            SlipRow nr; nr.len = (int32_t) slip_ld_u32(pk + SLIP_PKG_OUT + 3); nr.h = -2; nr.bits = (int32_t) slip_ld_u32(pk + SLIP_PKG_OUT + 4); nr.tag = tag;
+            const int pr = (int) slip_ld_u32(pk + MB_PROW);
+            SlipRow nr; nr.len = (int32_t) slip_ld_u32(pk + MB_SLEN); nr.h = -2; nr.bits = (int32_t) slip_ld_u32(pk + MB_BITS); nr.tag = tag;
             P.xrow[pr] = nr;
-            *(int64_t *)(P.xd + (int64_t) pr * P.xcap) = (int64_t) slip_ld_u64((const uint64_t *)(pk + SLIP_PKG_OUT + 6));
-            sv64[SV_LALLOC / 2] = (int64_t) slip_ld_u64((const uint64_t *)(pk + SLIP_PKG_OUT + 8));
-            sv[SV_EPR] = pr; sv[SV_EPP] = (int) slip_ld_u32(pk + SLIP_PKG_OUT + 2);
+            *(int64_t *)(P.xd + (int64_t) pr * P.xcap) = (int64_t) slip_ld_u64((const uint64_t *)(pk + MB_POFF));
+            sv64[SV_LALLOC / 2] = (int64_t) slip_ld_u64((const uint64_t *)(pk + MB_LALLOC));
+            sv[SV_EPR] = pr; sv[SV_EPP] = (int) slip_ld_u32(pk + MB_PPOS);
         }
         slip_block_sync();
         pc_col = sv[SV_TMP3];
@@ -1165,9 +1199,8 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
     }
     if (fastc) {
         if (wave == 0) {
-            const int ncand = sv[SV_PP + 1], nS = sv[SV_PP + 2], nB = sv[SV_PP + 6];
-            const uint32_t nUc_all = (uint32_t) sv[SV_PP + 3];
-            const uint64_t U_l = (uint64_t)(uint32_t) sv[SV_PP + 4];
+            const int ncand = sv[SV_PP + PP_NCAND], nS = sv[SV_PP + PP_NS], nB = sv[SV_PP + PP_NB];
+            const uint64_t U_l = (uint64_t)(uint32_t) sv[SV_PP + PP_UL];
             /* rho[k-1]'s digits into LDS (phase 4 uses the copy as well) */
             if (BMs) { const dig_t *Mg = slip_piv_digits(P, M); for (int c = lane; c < lm; c += SLIP_WAVE) Ms[c] = slip_ld_u32(Mg + c); }
             slip_wave_sync();                    /* the cursors and the digits are in LDS */
@@ -1175,30 +1208,15 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
             pc_col = sv[SV_TMP3];
             const int64_t Lnz_ = sv64[SV_LNZ / 2], Lnl_ = sv64[SV_LNL / 2], Unz_ = sv64[SV_UNZ / 2], Unl_ = sv64[SV_UNL / 2];
             /* the bounds with rho[k-1]'s share added; the same checks as the full pass makes */
-            const bool A_ok = lm + 2 <= P.xcap && lm + 2 <= 256;
-            const int nA = lm > 2 ? nS : 0;      /* one limb times a one-limb pivot stays in the lane, anything longer goes into the slab */
-            const int maxc = sv[SV_PP + 9] - SLIP_PP_BIAS + brho;
-            const int maxub_all = maxc > sv[SV_PP + 10] ? maxc : sv[SV_PP + 10];
-            const uint64_t L_b = (uint64_t)(uint32_t) sv[SV_PP + 5] + (uint64_t) nB * (uint64_t)((brho + 63) >> 6) + (lm <= 2 ? 2ull * (uint64_t) nS : 0ull);
-            const uint64_t preserve = (uint64_t)((maxub_all + 63) >> 6) + 1;
-            const uint64_t Lb_total = (uint64_t) nA * (uint64_t) slot + preserve + L_b;
-            const uint64_t Ub_total = U_l + preserve;
-            const int nLc = nrows - (int) nUc_all;
-            int ok = 1;
-            if (lm > 2 && !A_ok && nS > 0) ok = 0;
-            if (nB > 0) {
-                const int Wn = ((sv[SV_PP + 7] - SLIP_PP_BIAS + brho + 31) >> 5) + ((sv[SV_PP + 8] + 31) >> 5) + 1;
-                if (Wn > P.wcap || Wn > P.xcap || Wn > P.invcap || lm > P.wcap) ok = 0;
-            }
-            if (Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) ok = 0;
-            if (Unz_ + (int) nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) ok = 0;
-            if (P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ok = 0;
-            SLIP_PROF_W(if (lane == 0) P.dbg[slip_dbg_flags(P.n) + k] |= 0x100 | (ok ? 0x200 : 0) | ((lm > 2 && !A_ok && nS > 0) ? 0x400 : 0)
-                | ((Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) ? 0x800 : 0)
-                | ((Unz_ + (int) nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) ? 0x1000 : 0)
-                | ((P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) ? 0x2000 : 0));
+            const SlipColSizes Z = slip_col_sizes([&](int w) -> int { return sv[SV_PP + w]; }, nrows, lm, brho);
+            const int nA = Z.nA, nLc = Z.nLc, slotw = Z.slotw; const uint32_t nUc_all = (uint32_t) Z.nUc; const uint64_t Lb_total = Z.Lb_total;
+            int bad = slip_col_misfit(slip_caps(P), Z, Lnz_, Lnl_, Unz_, Unl_);
+            if (nS == 0) bad &= ~SLIP_MISFIT_A;                          /* (the worker: only when a class-S row goes into the slab) */
+            if (nB > 0 && lm > P.wcap) bad |= SLIP_MISFIT_W;
+            const int ok = !bad;
+            SLIP_PROF_W(if (lane == 0) P.dbg[slip_dbg_flags(P.n) + k] |= 0x100 | (ok ? 0x200 : 0) | ((bad & SLIP_MISFIT_A) ? 0x400 : 0)
+                | ((bad & SLIP_MISFIT_L) ? 0x800 : 0) | ((bad & SLIP_MISFIT_U) ? 0x1000 : 0) | ((bad & SLIP_MISFIT_LIMB) ? 0x2000 : 0));
             const int diag_cand = (scheme == 1 || scheme == 3 || scheme == 4) && pc_col >= k && P.xrow[col].tag == tag && P.xrow[col].len != 0;
-            const int slotw = (lm + 5) & ~1;
             const int nstage = (3 * SLIP_PAT_CAP) / slotw < 30 ? (3 * SLIP_PAT_CAP) / slotw : 30;
             uint32_t *wlB = work, *wlA = work + 2 * SLIP_CAND_CAP;
             int ncA = 0, ncB = 0;
@@ -1235,8 +1253,8 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
                     const int at = slip_popc64(mA & below);
                     const uint32_t ax = f_aux[c_t];
                     wlA[5 * at] = (uint32_t) c_r; wlA[5 * at + 1] = f_k0[c_t]; wlA[5 * at + 2] = f_k1[c_t];
-                    wlA[5 * at + 3] = ((uint32_t) c_t << 3) | ((ax >> 14) & 1u ? 4u : 0u) | ((ax >> 12) & 3u);
-                    wlA[5 * at + 4] = (ax & 0x3FFu) * (uint32_t) slot;
+                    wlA[5 * at + 3] = ((uint32_t) c_t << 3) | (slip_aux_neg(ax) ? 4u : 0u) | (uint32_t) slip_aux_nd(ax);
+                    wlA[5 * at + 4] = slip_aux_slot(ax) * (uint32_t) slot;
                 } else if (wantB) wlB[slip_popc64(mB & below)] = (uint32_t) c_r;
                 slip_wave_sync();
             }
@@ -1342,7 +1360,7 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
                 } else if (xr.h < 0 && slip_abs(xr.len) <= 2 && lm + 2 <= P.xcap && lm + 2 <= 256) {
                     cls = 2; isA = 1; ub = xr.bits + brho;
                     f_k0[t] = (uint32_t) xv; f_k1[t] = (uint32_t)(xv >> 32);       /* the one-limb value, for the candidate record (the key comes later) */
-                    asgn = ((uint32_t) slip_abs(xr.len) << 12) | (xr.len < 0 ? 1u << 14 : 0u);
+                    asgn = slip_aux_pack(0u, slip_abs(xr.len), xr.len < 0);
                 } else {
                     cls = 3;
                     int bh = 0, zh = 0;
@@ -1483,8 +1501,8 @@ SLIP_DEV int slip_do_column(const SlipParams &P, SlipState *st, const int k, con
                     if (at < SLIP_CAND_CAP) {
                         const uint32_t ax = f_aux[t];
                         wlA[5 * at] = (uint32_t) r; wlA[5 * at + 1] = f_k0[t]; wlA[5 * at + 2] = f_k1[t];
-                        wlA[5 * at + 3] = ((uint32_t) t << 3) | ((ax >> 14) & 1u ? 4u : 0u) | ((ax >> 12) & 3u);
-                        wlA[5 * at + 4] = (ax & 0x3FFu) * (uint32_t) slot;
+                        wlA[5 * at + 3] = ((uint32_t) t << 3) | (slip_aux_neg(ax) ? 4u : 0u) | (uint32_t) slip_aux_nd(ax);
+                        wlA[5 * at + 4] = slip_aux_slot(ax) * (uint32_t) slot;
                     }
                 } else if (wantB) { const int at = bB + slip_popc64(mB & below); if (at < SLIP_CAND_CAP) wlB[at] = (uint32_t) r; }
             }

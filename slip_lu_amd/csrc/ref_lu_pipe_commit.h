@@ -34,10 +34,69 @@
 
 #define SLIP_CB          8                  /* columns per batch */
 #define SLIP_CB_RING     512                /* swaps and pivots the committer remembers (more than the columns in flight) */
-#define SLIP_CBW         640                /* one batch column in LDS: 32 header words, 96 candidate words, 512 row words */
+#define SLIP_CBW         640                /* one batch column in LDS: the header, the candidate records, the rows */
+#define SLIP_CB_HDRW     32                 /* ... header: the pre-pass sums (PP_*), then CBH_* */
+#define SLIP_CB_CANDS    SLIP_CB_HDRW       /* ... SLIP_PKG_CANDS candidate records (CAND_*) */
+#define SLIP_CB_ROWS     (SLIP_CB_CANDS + SLIP_CAND_WORDS * SLIP_PKG_CANDS)    /* ... the rows of the package (SLIP_PKG_ROWS) */
+#define SLIP_CB_ROWW     512
 #define SLIP_CB_SLOTW    264                /* rho_j: a product of a one-limb value and a pivot of at most 256 digits, whole limbs */
 #define SLIP_LRING       3072               /* entries of the engine's ring of L columns (3 words each) */
-#define SLIP_PUBW        32
+#define SLIP_PUBW        32                 /* one publish record in LDS (PUB_*) */
+
+/* the header of a batch column behind the pre-pass sums: what the load step (b) knows about the column by itself */
+enum {
+    CBH_STAMP = SLIP_PP_WORDS,  /* the frontier up to which the worker has checked its rows */
+    CBH_STAMP0,     /* the frontier the pre-pass ran at */
+    CBH_NROWS,      /* rows of the pattern */
+    CBH_ROWJ,       /* the row at position j when the batch began */
+    CBH_REJ,        /* SLIP_REJ_* from the load step, or 0 */
+    CBH_VER,        /* version of the package */
+    CBH_WORKER,     /* the exporting worker */
+    CBH_KIND,       /* 0 candidates, 1 full */
+    CBH_NFULL,      /* full package: rows carried */
+    CBH_DIAGC,      /* which candidate is the diagonal row, or SLIP_DC_* */
+    CBH_CHOICE,     /* the candidate the load step chose | SLIP_CH_* */
+    CBH_PROW,       /* the chosen candidate: row, ... */
+    CBH_A0,         /* ... value, low digit */
+    CBH_A1,         /* ... value, high digit */
+    CBH_AUX,        /* ... aux word (slip_aux_*) */
+    CBH_PPOS,       /* ... position */
+    CBH_UNK         /* mask of the earlier columns of the batch whose pivot the load step did not know */
+};
+/* CBH_CHOICE above the candidate's index: why the choice is not final */
+#define SLIP_CH_TIE      (1u << 8)          /* equal values: decided by positions in the serial step */
+#define SLIP_CH_WORKER   (1u << 9)          /* the worker decides (the diagonal row was not sent, or the tolerance test does not fit) */
+#define SLIP_CH_NONE     (1u << 10)         /* no candidate at all (inconsistent package) */
+#define SLIP_CH_MASK     (SLIP_CH_TIE | SLIP_CH_WORKER | SLIP_CH_NONE)
+/* CBH_DIAGC when no candidate is the diagonal row */
+enum { SLIP_DC_NONE = 255 /* the column has no diagonal row to prefer */, SLIP_DC_NOTSENT = 254 /* it is not among the candidates sent */ };
+/* a publish record: what the serial step (c) or the run (c0) leaves for the publish step (d); 64-bit entries by their low word */
+enum {
+    PUB_PROW = 0,       /* pivot row */
+    PUB_PPOS,           /* its position before the swap */
+    PUB_DISP,           /* the row it changes places with */
+    PUB_SLEN,           /* rho[j]: signed digits */
+    PUB_BITS,           /* ... bits */
+    PUB_LEN,            /* ... digits */
+    PUB_NFIN,           /* full package: rows handed back */
+    PUB_NLATE,          /* full package: sources the engine applied */
+    PUB_POFF,           /* 64 bit: rho[j]'s limbs in the L slab */
+    PUB_LALLOC = 10,    /* 64 bit: limbs handed out to the column's direct rows */
+    PUB_UNZ = 12,       /* 64 bit: Up[j + 1] */
+    PUB_LNZ = 14,       /* 64 bit: Lp[j + 1] */
+    PUB_UNL = 16,       /* 64 bit: Uo[j + 1] */
+    PUB_LNL = 18,       /* 64 bit: Lo[j + 1] */
+    PUB_WORKER = 20,    /* the exporting worker */
+    PUB_KIND,           /* kind of the package */
+    PUB_R_LEN,          /* the run, between its two steps: rho[kc + i]'s digits, ... */
+    PUB_R_BITS,         /* ... bits, ... */
+    PUB_R_LO,           /* ... low limb (64 bit) ... */
+    PUB_R_NEG = 26      /* ... and sign */
+};
+static_assert(SLIP_CB_ROWS + SLIP_CB_ROWW == SLIP_CBW, "batch column: header, candidates, rows");
+static_assert(SLIP_CB_ROWW >= 4 * SLIP_PKG_FULLMAX && SLIP_CB_ROWW >= SLIP_PKG_NROWMAX, "batch column: the rows of either kind");
+static_assert(CBH_UNK < SLIP_CB_HDRW && SLIP_CB_HDRW <= 32, "HF reads the header one lane per word");
+static_assert(PUB_R_NEG < SLIP_PUBW, "publish record");
 
 /* where the committer keeps what in its LDS (words from lds + SLIP_LDS_WORK); the host sizes the launch with it */
 struct SlipCommitLayout {
@@ -88,24 +147,24 @@ SLIP_DEV void slip_export_package(const SlipParams &P, const int k, uint32_t *ld
     const uint32_t *f_row = lds + SLIP_LDS_TAB, *f_pos = f_row + SLIP_TAB_CAP, *f_aux = f_row + 3 * SLIP_TAB_CAP;
     const uint32_t *f_k0 = lds + SLIP_LDS_KEYS, *f_k1 = f_k0 + SLIP_PAT_CAP;
     const uint32_t *cl = lds + SLIP_LDS_WORK + SLIP_CAND_CAP;
-    uint32_t *pk = P.pkg.at() + (int64_t)(k % P.nworkers) * SLIP_PKG_WORDS;
-    const int nrows = sv[SV_NROWS], ncand = sv[SV_PP + 1];
+    uint32_t *pk = slip_pkg_slot(P, k);
+    const int nrows = sv[SV_NROWS], ncand = sv[SV_PP + PP_NCAND];
     const uint32_t ver = ((uint32_t) sv[SV_PKGVER] | 1u) + 1u;          /* 2, 4, 6, ... */
     if (tid == 0) { slip_st_u64((uint64_t *)(pk + SLIP_PKG_HDR), ((uint64_t)(ver - 1u) << 32) | (uint32_t)(k + 1)); slip_vm_drain(); }
     slip_block_sync();
     for (int t = tid; t < nrows; t += T) slip_st_u32(pk + SLIP_PKG_ROWS + t, f_row[t]);
     for (int c = tid; c < ncand; c += T) {
         const int t = (int) cl[c];
-        uint32_t *cr = pk + SLIP_PKG_CAND + 6 * c;
-        slip_st_u32(cr, (uint32_t) t); slip_st_u32(cr + 1, f_k0[t]); slip_st_u32(cr + 2, f_k1[t]); slip_st_u32(cr + 3, f_aux[t]); slip_st_u32(cr + 4, f_pos[t]);
-        slip_st_u32(cr + 5, ver);
+        uint32_t *cr = pk + SLIP_PKG_CAND + SLIP_CAND_WORDS * c;
+        slip_st_u32(cr + CAND_T, (uint32_t) t); slip_st_u32(cr + CAND_A0, f_k0[t]); slip_st_u32(cr + CAND_A1, f_k1[t]); slip_st_u32(cr + CAND_AUX, f_aux[t]); slip_st_u32(cr + CAND_POS, f_pos[t]);
+        slip_st_u32(cr + CAND_VER, ver);
     }
     if (tid < SLIP_PP_WORDS) slip_st_u32(pk + SLIP_PKG_SUMS + tid, (uint32_t) sv[SV_PP + tid]);
     if (tid == SLIP_PP_WORDS) {
         slip_st_u32(pk + SLIP_PKG_STAMP, (uint32_t) Fl); slip_st_u32(pk + SLIP_PKG_STAMP0, (uint32_t) F0);
         slip_st_u32(pk + SLIP_PKG_NROWS, (uint32_t) nrows); slip_st_u32(pk + SLIP_PKG_VER, ver); slip_st_u32(pk + SLIP_PKG_WORKER, (uint32_t) P.worker);
         slip_st_u32(pk + SLIP_PKG_KIND, 0u); slip_st_u32(pk + SLIP_PKG_NFULL, 0u);
-        slip_st_u32(P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) P.worker * SLIP_MBOX_WORDS + SLIP_PKG_OUT, 0u);
+        slip_st_u32(slip_mailbox(P, P.worker) + MB_VERDICT, 0u);
     }
     slip_vm_drain();
     slip_block_sync();
@@ -126,7 +185,7 @@ SLIP_DEV void slip_export_full(const SlipParams &P, const int k, uint32_t *lds, 
     const uint32_t *f_row = lds + SLIP_LDS_TAB;
     const uint32_t *f_k0 = lds + SLIP_LDS_KEYS, *f_k1 = f_k0 + SLIP_PAT_CAP;
     const uint32_t *f_meta = lds + SLIP_LDS_DIROFF, *f_npi = lds + SLIP_LDS_ROWS;
-    uint32_t *pk = P.pkg.at() + (int64_t)(k % P.nworkers) * SLIP_PKG_WORDS;
+    uint32_t *pk = slip_pkg_slot(P, k);
     const int nrows = sv[SV_NROWS], nnp = sv[SV_PPF];
     const uint32_t ver = ((uint32_t) sv[SV_PKGVER] | 1u) + 1u;
     if (tid == 0) { slip_st_u64((uint64_t *)(pk + SLIP_PKG_HDR), ((uint64_t)(ver - 1u) << 32) | (uint32_t)(k + 1)); slip_vm_drain(); }
@@ -143,7 +202,7 @@ SLIP_DEV void slip_export_full(const SlipParams &P, const int k, uint32_t *lds, 
         slip_st_u32(pk + SLIP_PKG_STAMP, (uint32_t) Fl); slip_st_u32(pk + SLIP_PKG_STAMP0, (uint32_t) F0);
         slip_st_u32(pk + SLIP_PKG_NROWS, (uint32_t) nrows); slip_st_u32(pk + SLIP_PKG_VER, ver); slip_st_u32(pk + SLIP_PKG_WORKER, (uint32_t) P.worker);
         slip_st_u32(pk + SLIP_PKG_KIND, 1u); slip_st_u32(pk + SLIP_PKG_NFULL, (uint32_t) nnp);
-        slip_st_u32(P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) P.worker * SLIP_MBOX_WORDS + SLIP_PKG_OUT, 0u);
+        slip_st_u32(slip_mailbox(P, P.worker) + MB_VERDICT, 0u);
     }
     slip_vm_drain();
     slip_block_sync();
@@ -157,7 +216,7 @@ SLIP_DEV void slip_export_full(const SlipParams &P, const int k, uint32_t *lds, 
 /* the worker's side: the package no longer describes the rows (thread 0) */
 SLIP_DEV void slip_retract_package(const SlipParams &P, const int k, volatile int32_t *sv)
 {
-    uint32_t *pk = P.pkg.at() + (int64_t)(k % P.nworkers) * SLIP_PKG_WORDS;
+    uint32_t *pk = slip_pkg_slot(P, k);
     const uint32_t ver = (uint32_t) sv[SV_PKGVER] | 1u;
     slip_st_u64((uint64_t *)(pk + SLIP_PKG_HDR), ((uint64_t) ver << 32) | (uint32_t)(k + 1));
     sv[SV_PKGVER] = (int32_t) ver; sv[SV_PKGX] = 0;
@@ -206,8 +265,24 @@ SLIP_DEV int slip_tol_small(uint64_t tol_m, int te, uint64_t num, uint64_t den)
     return lhs >= rhs ? 1 : 0;
 }
 
+/* The diagonal preference between one-limb magnitudes (slip_get_pivot.c:68-76, 89-118, 126-146): the diagonal row's value
+ * `diag` against the best candidate `best`.  best_negative: 1 / 0, or -1 when the sign is not known yet -- scheme 4 lets a
+ * negative largest candidate yield to the diagonal, so a caller that passes -1 decides a SLIP_DIAG_KEEP of scheme 4
+ * again once it knows.  SLIP_DIAG_UNDECIDED: the tolerance test does not fit 128 bits. */
+enum { SLIP_DIAG_UNDECIDED = -1, SLIP_DIAG_KEEP = 0, SLIP_DIAG_TAKE = 1 };
+SLIP_DEV int slip_diag_small(int scheme, int tol_mode, uint64_t tol_m, int tol_e, uint64_t best, uint64_t diag, int best_negative)
+{
+    if (scheme == 1 || tol_mode == 0) return SLIP_DIAG_TAKE;
+    if (scheme == 4 && best_negative > 0) return SLIP_DIAG_TAKE;
+    static_assert(SLIP_DIAG_TAKE == 1 && SLIP_DIAG_KEEP == 0 && SLIP_DIAG_UNDECIDED == -1, "slip_tol_small's answers");
+    return slip_tol_small(tol_m, tol_e, scheme == 3 ? best : diag, scheme == 3 ? diag : best);
+}
+
 /* a pivot of the committer's ring: one-limb pivots keep what the in-lane arithmetic needs */
 struct SlipSmallPiv { uint64_t lo, inv; int ctz, sgn, small, bits; };
+/* ... its meta word: ctz, sign, one-limb flag, bits (of a one-limb pivot) */
+SLIP_DEV uint32_t slip_pring_meta_pack(int ctz, int neg, int small, int bits) { return (uint32_t)(ctz & 0xFF) | (neg ? 1u << 8 : 0u) | (small ? 1u << 9 : 0u) | ((uint32_t)(small ? bits : 0) << 16); }
+SLIP_DEV void slip_pring_meta_unpack(uint32_t m, SlipSmallPiv *p) { p->ctz = (int)(m & 0xFFu); p->sgn = (m >> 8) & 1u ? -1 : 1; p->small = (int)((m >> 9) & 1u); p->bits = (int)(m >> 16); }
 
 /* the run: rho[kc-1] (lm digits in LDS) times Pw (la digits, chunk 0) -> the stage slot (at least two digits, whole limbs);
  * its length, bit count and low limb (what slip_commit_mul gives) */
@@ -253,8 +328,8 @@ SLIP_DEVN int slip_commit_run_out(const SlipParams *Pg, uint32_t *lds, const int
     SlipPiv *Mrec = (SlipPiv *)(lds + SLIP_LDS_SCAN);
     /* lane e: column kc + e's words from the load step */
     const uint32_t *ce = cbuf + (lane < nb ? lane : 0) * SLIP_CBW;
-    const bool ok = lane < nb && ce[18] == 0u && ce[21] == 0u && !(ce[24] & 0x700u) && ce[30] == 0u;
-    const uint32_t ra0 = ce[26], ra1 = ce[27], rax = ce[28];
+    const bool ok = lane < nb && ce[CBH_REJ] == 0u && ce[CBH_KIND] == 0u && !(ce[CBH_CHOICE] & SLIP_CH_MASK) && ce[CBH_UNK] == 0u;
+    const uint32_t ra0 = ce[CBH_A0], ra1 = ce[CBH_A1], rax = ce[CBH_AUX];
     const int lm0 = slip_abs(Mrec->len), neg0 = Mrec->len < 0, brho0 = Mrec->bits;
     int r = slip_ctz64(~slip_ballot(ok));
     if (lm0 < 1 || lm0 > SLIP_CB_SLOTW - 6) r = 0;
@@ -268,7 +343,7 @@ SLIP_DEVN int slip_commit_run_out(const SlipParams *Pg, uint32_t *lds, const int
                 const uint32_t a0 = slip_readlane(ra0, e), a1 = slip_readlane(ra1, e), ax = slip_readlane(rax, e);
                 WR<1> A; A.d[0] = lane == 0 ? a0 : lane == 1 ? a1 : 0u;
                 Pw = wr_mul<1>(A, 2, Pw);
-                neg ^= (int)((ax >> 14) & 1u);
+                neg ^= (int) slip_aux_neg(ax);
             }
             done = i;
             const int la = wr_len<1>(Pw), tot = lm0 + la;
@@ -278,9 +353,9 @@ SLIP_DEVN int slip_commit_run_out(const SlipParams *Pg, uint32_t *lds, const int
             else if (tot <= 128) slip_run_rho<2>(Ms, lm0, Pw, la, sl, &len, &bits, &lo);
             else if (tot <= 192) slip_run_rho<3>(Ms, lm0, Pw, la, sl, &len, &bits, &lo);
             else if (tot <= 256) slip_run_rho<4>(Ms, lm0, Pw, la, sl, &len, &bits, &lo);
-            uint32_t *pb = pub + i * SLIP_PUBW;                         /* words 22..26: rho[kc+i] for the step below */
+            uint32_t *pb = pub + i * SLIP_PUBW;                         /* PUB_R_*: rho[kc+i] for the step below */
             const uint32_t w_ = lane == 0 ? (uint32_t) len : lane == 1 ? (uint32_t) bits : lane == 2 ? (uint32_t) lo : lane == 3 ? (uint32_t)(lo >> 32) : (uint32_t) neg;
-            if (lane < 5) pb[22 + lane] = w_;
+            if (lane <= PUB_R_NEG - PUB_R_LEN) pb[PUB_R_LEN + lane] = w_;
         }
     }
     slip_block_sync();
@@ -288,31 +363,16 @@ SLIP_DEVN int slip_commit_run_out(const SlipParams *Pg, uint32_t *lds, const int
     /* (c0.2) wave 0, lane i: column kc + i's sizes from rho[kc+i-1]'s length and bits (slip_committer's kind-0 step) */
     const bool in = lane < r;
     const uint32_t *pm = pub + (in ? lane : 0) * SLIP_PUBW, *pp = pub + (in && lane > 0 ? lane - 1 : 0) * SLIP_PUBW;
-    const int lp_ = (int) pm[22], pbits = (int) pm[23], pneg = (int) pm[26];
-    const uint64_t plo = (uint64_t) pm[24] | ((uint64_t) pm[25] << 32);
-    const int lm = lane == 0 ? lm0 : (int) pp[22], brho = lane == 0 ? brho0 : (int) pp[23];
-    const int nrows = (int) ce[16], nS = (int) ce[2], nB = (int) ce[6], nUc_all = (int) ce[3];
-    const uint64_t U_l = (uint64_t) ce[4];
-    const int nA = lm > 2 ? nS : 0, slot = (lm + 3) >> 1, slotw = (lm + 5) & ~1;
-    const int maxc = (int) ce[9] - SLIP_PP_BIAS + brho;
-    const int maxub_all = maxc > (int) ce[10] ? maxc : (int) ce[10];
-    const uint64_t L_b = (uint64_t) ce[5] + (uint64_t) nB * (uint64_t)((brho + 63) >> 6) + (lm <= 2 ? 2ull * (uint64_t) nS : 0ull);
-    const uint64_t preserve = (uint64_t)((maxub_all + 63) >> 6) + 1;
-    const uint64_t Lb_total = (uint64_t) nA * (uint64_t) slot + preserve + L_b, Ub_total = U_l + preserve;
-    const int nLc = nrows - nUc_all;
+    const int lp_ = (int) pm[PUB_R_LEN], pbits = (int) pm[PUB_R_BITS], pneg = (int) pm[PUB_R_NEG];
+    const uint64_t plo = (uint64_t) pm[PUB_R_LO] | ((uint64_t) pm[PUB_R_LO + 1] << 32);
+    const int lm = lane == 0 ? lm0 : (int) pp[PUB_R_LEN], brho = lane == 0 ? brho0 : (int) pp[PUB_R_BITS];
+    const SlipColSizes Z = slip_col_sizes([&](int w) -> int { return (int) ce[w]; }, (int) ce[CBH_NROWS], lm, brho);
+    const int nA = Z.nA, slot = Z.slot, nUc_all = Z.nUc, nLc = Z.nLc;
+    const uint64_t U_l = (uint64_t) ce[PP_UL], Lb_total = Z.Lb_total;
     const uint64_t plimbs = (uint64_t)((lp_ + 1) >> 1);
-    const int64_t poff_rel = lm > 2 ? (int64_t)(rax & 0x3FFu) * slot : (int64_t) nA * slot;
+    const int64_t poff_rel = lm > 2 ? (int64_t) slip_aux_slot(rax) * slot : (int64_t) nA * slot;
     const uint64_t lalloc = (uint64_t) nA * (uint64_t) slot + (lm > 2 ? 0ull : plimbs);
-    int bad = lp_ < 1 || lm < 1;
-    {
-        const bool A_ok = lm + 2 <= P.xcap && lm + 2 <= 256;
-        if (lm > SLIP_CB_SLOTW - 6 || slotw > SLIP_CB_SLOTW || (lm > 2 && !A_ok)) bad = 1;
-        if (nB > 0) {
-            const int Wn = (((int) ce[7] - SLIP_PP_BIAS + brho + 31) >> 5) + (((int) ce[8] + 31) >> 5) + 1;
-            if (Wn > P.wcap || Wn > P.xcap || Wn > P.invcap) bad = 1;
-        }
-        if (P.limb_cap > 0 && (int)((maxub_all + 63) >> 6) > P.limb_cap) bad = 1;
-    }
+    int bad = lp_ < 1 || lm < 1 || lm > SLIP_CB_SLOTW - 6 || Z.slotw > SLIP_CB_SLOTW;
     /* the cursors before each column: an exclusive prefix sum over the run */
     const int64_t dLnz = in ? (int64_t) nLc : 0, dLnl = in ? (int64_t) Lb_total : 0, dUnz = in ? (int64_t) nUc_all + 1 : 0, dUnl = in ? (int64_t)(U_l + plimbs) : 0;
     int64_t Lnz_ = sv64[SV_LNZ / 2], Lnl_ = sv64[SV_LNL / 2], Unz_ = sv64[SV_UNZ / 2], Unl_ = sv64[SV_UNL / 2];
@@ -321,16 +381,15 @@ SLIP_DEVN int slip_commit_run_out(const SlipParams *Pg, uint32_t *lds, const int
         const int64_t x0 = rl64(dLnz, e), x1 = rl64(dLnl, e), x2 = rl64(dUnz, e), x3 = rl64(dUnl, e);
         if (e < lane) { Lnz_ += x0; Lnl_ += x1; Unz_ += x2; Unl_ += x3; }
     }
-    if (Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) bad = 1;
-    if (Unz_ + nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t) Ub_total > P.Ucap_nl) bad = 1;
+    if (slip_col_misfit(slip_caps(P), Z, Lnz_, Lnl_, Unz_, Unl_)) bad = 1;
     const int rc = slip_ctz64(~slip_ballot(in && !bad));
     if (rc == 0) return 0;
     /* (c0.3) the swaps, in column order (the row at position j: the last swap of the batch that displaced a row there; the pivot
      * row's position: the last swap that displaced it) */
     uint32_t bs_row = 0xFFFFFFFFu, bs_disp = 0xFFFFFFFFu, bs_opos = 0xFFFFFFFFu;
-    const uint32_t h17 = ce[17], h25 = ce[25], h29 = ce[29];
+    const uint32_t h_rowj = ce[CBH_ROWJ], h_prow = ce[CBH_PROW], h_ppos = ce[CBH_PPOS];
     for (int e = 0; e < rc; e++) {
-        uint32_t im2 = slip_readlane(h17, e), prow = slip_readlane(h25, e), ppos = slip_readlane(h29, e);
+        uint32_t im2 = slip_readlane(h_rowj, e), prow = slip_readlane(h_prow, e), ppos = slip_readlane(h_ppos, e);
         const uint64_t m1 = slip_ballot(lane < e && bs_opos == (uint32_t)(kc + e));
         const uint64_t m2 = slip_ballot(lane < e && bs_disp == prow);
         const uint32_t d1 = slip_readlane(bs_disp, m1 ? 63 - slip_clz64(m1) : 0), o2 = slip_readlane(bs_opos, m2 ? 63 - slip_clz64(m2) : 0);
@@ -349,15 +408,15 @@ SLIP_DEVN int slip_commit_run_out(const SlipParams *Pg, uint32_t *lds, const int
     const int64_t nUnz = Unz_ + nUc_all + 1, nLnz = Lnz_ + nLc, nUnl = Unl_ + (int64_t)(U_l + plimbs), nLnl = Lnl_ + (int64_t) Lb_total;
     if (cm) {
         uint32_t *pb = pub + lane * SLIP_PUBW;
-        pb[0] = bs_row; pb[1] = bs_opos; pb[2] = bs_disp; pb[3] = (uint32_t) pr.len; pb[4] = (uint32_t) pbits; pb[5] = (uint32_t) lp_;
-        pb[6] = 0u; pb[7] = 0u;
-        pb[8] = (uint32_t) pr.off; pb[9] = (uint32_t)((uint64_t) pr.off >> 32); pb[10] = (uint32_t) lalloc; pb[11] = (uint32_t)(lalloc >> 32);
-        pb[12] = (uint32_t) nUnz; pb[13] = (uint32_t)((uint64_t) nUnz >> 32); pb[14] = (uint32_t) nLnz; pb[15] = (uint32_t)((uint64_t) nLnz >> 32);
-        pb[16] = (uint32_t) nUnl; pb[17] = (uint32_t)((uint64_t) nUnl >> 32); pb[18] = (uint32_t) nLnl; pb[19] = (uint32_t)((uint64_t) nLnl >> 32);
-        pb[20] = ce[20]; pb[21] = 0u;
+        pb[PUB_PROW] = bs_row; pb[PUB_PPOS] = bs_opos; pb[PUB_DISP] = bs_disp; pb[PUB_SLEN] = (uint32_t) pr.len; pb[PUB_BITS] = (uint32_t) pbits; pb[PUB_LEN] = (uint32_t) lp_;
+        pb[PUB_NFIN] = 0u; pb[PUB_NLATE] = 0u;
+        pb[PUB_POFF] = (uint32_t) pr.off; pb[PUB_POFF + 1] = (uint32_t)((uint64_t) pr.off >> 32); pb[PUB_LALLOC] = (uint32_t) lalloc; pb[PUB_LALLOC + 1] = (uint32_t)(lalloc >> 32);
+        pb[PUB_UNZ] = (uint32_t) nUnz; pb[PUB_UNZ + 1] = (uint32_t)((uint64_t) nUnz >> 32); pb[PUB_LNZ] = (uint32_t) nLnz; pb[PUB_LNZ + 1] = (uint32_t)((uint64_t) nLnz >> 32);
+        pb[PUB_UNL] = (uint32_t) nUnl; pb[PUB_UNL + 1] = (uint32_t)((uint64_t) nUnl >> 32); pb[PUB_LNL] = (uint32_t) nLnl; pb[PUB_LNL + 1] = (uint32_t)((uint64_t) nLnl >> 32);
+        pb[PUB_WORKER] = ce[CBH_WORKER]; pb[PUB_KIND] = 0u;
         const int small = lp_ <= 2;
         pr_lo0[s_] = (uint32_t) plo; pr_lo1[s_] = (uint32_t)(plo >> 32); pr_inv0[s_] = (uint32_t) pr.inv64; pr_inv1[s_] = (uint32_t)(pr.inv64 >> 32);
-        pr_meta[s_] = (uint32_t)(pr.ctz & 0xFF) | (pneg ? 0x100u : 0u) | (small ? 0x200u : 0u) | ((uint32_t)(small ? pbits : 0) << 16);
+        pr_meta[s_] = slip_pring_meta_pack(pr.ctz, pneg, small, pbits);
         ring_row[s_] = bs_row; ring_disp[s_] = bs_disp; ring_opos[s_] = bs_opos;
         ld_col[s_] = 0xFFFFFFFFu;                                       /* its L values are long: not in the engine's ring */
     }
@@ -453,16 +512,15 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
     /* ring entry of pivot c for the in-lane arithmetic */
     auto pring_get = [&](int c) -> SlipSmallPiv {
         const int s_ = c & (SLIP_CB_RING - 1);
-        SlipSmallPiv p; const uint32_t m = pr_meta[s_];
+        SlipSmallPiv p; slip_pring_meta_unpack(pr_meta[s_], &p);
         p.lo = (uint64_t) pr_lo0[s_] | ((uint64_t) pr_lo1[s_] << 32); p.inv = (uint64_t) pr_inv0[s_] | ((uint64_t) pr_inv1[s_] << 32);
-        p.ctz = (int)(m & 0xFFu); p.sgn = (m >> 8) & 1u ? -1 : 1; p.small = (int)((m >> 9) & 1u); p.bits = (int)(m >> 16);
         return p;
     };
     auto pring_put = [&](int c, const SlipPiv &pv) {                 /* one lane */
         const int s_ = c & (SLIP_CB_RING - 1);
         const int small = slip_abs(pv.len) <= 2 && pv.len != 0;
         pr_lo0[s_] = (uint32_t) pv.lo; pr_lo1[s_] = (uint32_t)(pv.lo >> 32); pr_inv0[s_] = (uint32_t) pv.inv64; pr_inv1[s_] = (uint32_t)(pv.inv64 >> 32);
-        pr_meta[s_] = (uint32_t)(pv.ctz & 0xFF) | (pv.len < 0 ? 0x100u : 0u) | (small ? 0x200u : 0u) | ((uint32_t)(small ? pv.bits : 0) << 16);
+        pr_meta[s_] = slip_pring_meta_pack(pv.ctz, pv.len < 0, small, pv.bits);
     };
     auto est_lookup = [&](uint32_t row) -> int { return (int) slotm[row] - 1; };
     auto est_insert = [&](uint32_t row, int idx) { slotm[row] = (uint8_t)(idx + 1); };
@@ -522,7 +580,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                 if (kc >= P.k_stop || (stop >> 8) <= (int64_t) kc) { go = 0; break; }
                 const int j = kc + lane;
                 uint64_t h = 0;
-                if (lane < SLIP_CB && j < P.k_stop && (stop >> 8) > (int64_t) j) h = slip_ld_u64((const uint64_t *)(P.pkg.at() + (int64_t)(j % P.nworkers) * SLIP_PKG_WORDS + SLIP_PKG_HDR));
+                if (lane < SLIP_CB && j < P.k_stop && (stop >> 8) > (int64_t) j) h = slip_ld_u64((const uint64_t *)(slip_pkg_slot(P, j) + SLIP_PKG_HDR));
                 const uint32_t hw_ = (uint32_t)(h >> 32), hv = hw_ & 0xFFu;        /* version; above it the sizes of the package */
                 const int rdy = (uint32_t) h == (uint32_t)(j + 1) && hv >= 2u && !(hv & 1u) && !(j == sv[C_REJ] && hv == (uint32_t) sv[C_REJV]);
                 if (lane < SLIP_CB) { hver[lane] = hv; hver[SLIP_CB + lane] = hw_; }
@@ -542,37 +600,37 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
         /* (b) the packages into LDS (one wave per column) and what can be said about each by itself */
         for (int i = wave; i < nb; i += nw) {
             const int j = kc + i;
-            const uint32_t *pk = P.pkg.at() + (int64_t)(j % P.nworkers) * SLIP_PKG_WORDS;
+            const uint32_t *pk = slip_pkg_slot(P, j);
             uint32_t *cb = cbuf + i * SLIP_CBW;
             if (lane < SLIP_PP_WORDS) cb[lane] = slip_ld_u32(pk + SLIP_PKG_SUMS + lane);
-            else if (lane == 14) cb[14] = slip_ld_u32(pk + SLIP_PKG_STAMP);
-            else if (lane == 15) cb[15] = slip_ld_u32(pk + SLIP_PKG_STAMP0);
-            else if (lane == 16) cb[16] = slip_ld_u32(pk + SLIP_PKG_NROWS);
-            else if (lane == 17) cb[17] = (uint32_t) slip_ld_i32(P.row_perm.at(j));
-            else if (lane == 18) cb[18] = 0u;
-            else if (lane == 19) cb[19] = slip_ld_u32(pk + SLIP_PKG_VER);
-            else if (lane == 20) cb[20] = slip_ld_u32(pk + SLIP_PKG_WORKER);
-            else if (lane == 21) cb[21] = slip_ld_u32(pk + SLIP_PKG_KIND);
-            else if (lane == 22) cb[22] = slip_ld_u32(pk + SLIP_PKG_NFULL);
+            else if (lane == CBH_STAMP) cb[CBH_STAMP] = slip_ld_u32(pk + SLIP_PKG_STAMP);
+            else if (lane == CBH_STAMP0) cb[CBH_STAMP0] = slip_ld_u32(pk + SLIP_PKG_STAMP0);
+            else if (lane == CBH_NROWS) cb[CBH_NROWS] = slip_ld_u32(pk + SLIP_PKG_NROWS);
+            else if (lane == CBH_ROWJ) cb[CBH_ROWJ] = (uint32_t) slip_ld_i32(P.row_perm.at(j));
+            else if (lane == CBH_REJ) cb[CBH_REJ] = 0u;
+            else if (lane == CBH_VER) cb[CBH_VER] = slip_ld_u32(pk + SLIP_PKG_VER);
+            else if (lane == CBH_WORKER) cb[CBH_WORKER] = slip_ld_u32(pk + SLIP_PKG_WORKER);
+            else if (lane == CBH_KIND) cb[CBH_KIND] = slip_ld_u32(pk + SLIP_PKG_KIND);
+            else if (lane == CBH_NFULL) cb[CBH_NFULL] = slip_ld_u32(pk + SLIP_PKG_NFULL);
             {
                 const uint32_t hw_ = hver[SLIP_CB + i];
-                int nload = (int)((hw_ >> 8) & 0x3FFu), ncl = 6 * (int)((hw_ >> 18) & 0x1Fu);
-                if (nload > 512) nload = 512;
-                if (ncl > 6 * SLIP_PKG_CANDS) ncl = 6 * SLIP_PKG_CANDS;
-                for (int c = lane; c < ncl; c += SLIP_WAVE) cb[32 + c] = slip_ld_u32(pk + SLIP_PKG_CAND + c);
-                for (int c = lane; c < nload; c += SLIP_WAVE) cb[128 + c] = slip_ld_u32(pk + SLIP_PKG_ROWS + c);
+                int nload = (int)((hw_ >> 8) & 0x3FFu), ncl = SLIP_CAND_WORDS * (int)((hw_ >> 18) & 0x1Fu);
+                if (nload > SLIP_CB_ROWW) nload = SLIP_CB_ROWW;
+                if (ncl > SLIP_CAND_WORDS * SLIP_PKG_CANDS) ncl = SLIP_CAND_WORDS * SLIP_PKG_CANDS;
+                for (int c = lane; c < ncl; c += SLIP_WAVE) cb[SLIP_CB_CANDS + c] = slip_ld_u32(pk + SLIP_PKG_CAND + c);
+                for (int c = lane; c < nload; c += SLIP_WAVE) cb[SLIP_CB_ROWS + c] = slip_ld_u32(pk + SLIP_PKG_ROWS + c);
             }
             /* the header again, behind the contents (seqlock): a package that is being rewritten is offered again later */
             const uint64_t h2 = slip_ld_u64((const uint64_t *)(pk + SLIP_PKG_HDR));
             slip_wave_sync_lds();
-            const int kindp = (int) cb[21];
-            const int nrows = (int) cb[16], ncand = (int) cb[1], stamp = (int) cb[14], stamp0 = (int) cb[15];
-            int hit = (uint32_t) h2 != (uint32_t)(j + 1) || (uint32_t)(h2 >> 32) != hver[SLIP_CB + i] || cb[19] != hver[i] || cb[20] >= (uint32_t) P.nworkers
+            const int kindp = (int) cb[CBH_KIND];
+            const int nrows = (int) cb[CBH_NROWS], ncand = (int) cb[PP_NCAND], stamp = (int) cb[CBH_STAMP], stamp0 = (int) cb[CBH_STAMP0];
+            int hit = (uint32_t) h2 != (uint32_t)(j + 1) || (uint32_t)(h2 >> 32) != hver[SLIP_CB + i] || cb[CBH_VER] != hver[i] || cb[CBH_WORKER] >= (uint32_t) P.nworkers
                       || stamp < stamp0 || stamp > j || stamp0 < sv[C_RING0] || j - stamp0 > SLIP_CB_RING - SLIP_CB - 1;
             if (kindp == 0) {
-                if (nrows < 1 || nrows > SLIP_PKG_NROWMAX || ncand < 1 || ncand > SLIP_PKG_CANDS || cb[12] != 0 || (hver[SLIP_CB + i] >> 8) != (uint32_t)(nrows | (ncand << 10))) hit = 1;
-                if (!hit && lane < ncand && cb[32 + 6 * lane + 5] != hver[i]) hit = 1;
-                const uint32_t *rows = cb + 128;
+                if (nrows < 1 || nrows > SLIP_PKG_NROWMAX || ncand < 1 || ncand > SLIP_PKG_CANDS || cb[PP_NONS] != 0 || (hver[SLIP_CB + i] >> 8) != (uint32_t)(nrows | (ncand << 10))) hit = 1;
+                if (!hit && lane < ncand && cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_VER] != hver[i]) hit = 1;
+                const uint32_t *rows = cb + SLIP_CB_ROWS;
                 if (!hit) {
                     /* the rows against the pivots its worker has not seen (those committed before this batch) */
                     if (mirror) {
@@ -595,7 +653,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                     /* for the serial step: every candidate's ROW and its position as the reference has it at column kc (the mirror,
                      * or the value the worker read at frontier stamp0 and where the LAST swap since then that displaced the row put
                      * it); which candidate is the diagonal row */
-                    const uint32_t myrow = lane < ncand ? rows[cb[32 + 6 * lane]] : 0xFFFFFFFFu;
+                    const uint32_t myrow = lane < ncand ? rows[cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_T]] : 0xFFFFFFFFu;
                     uint32_t mypos = 0x7FFFFFFFu;
                     if (mirror) { if (lane < ncand) mypos = (uint32_t) pinvm[myrow]; }
                     else {
@@ -608,58 +666,55 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                 if (m && lane == c) last = e0 + 63 - slip_clz64(m);
                             }
                         }
-                        if (lane < ncand) mypos = last >= 0 ? ring_opos[last & (SLIP_CB_RING - 1)] : cb[32 + 6 * lane + 4];
+                        if (lane < ncand) mypos = last >= 0 ? ring_opos[last & (SLIP_CB_RING - 1)] : cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_POS];
                     }
-                    const int diag_t = (int) cb[13] - 1;
-                    const uint64_t dm = slip_ballot(lane < ncand && (int) cb[32 + 6 * lane] == diag_t);
+                    const int diag_t = (int) cb[PP_DIAG] - 1;
+                    const uint64_t dm = slip_ballot(lane < ncand && (int) cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_T] == diag_t);
                     slip_wave_sync_lds();
-                    if (lane < ncand) { cb[32 + 6 * lane] = myrow; cb[32 + 6 * lane + 4] = mypos; }
-                    const int dc = diag_t < 0 ? 0xFF : (dm ? slip_ctz64(dm) : 0xFE);      /* 0xFF: no diagonal row; 0xFE: it is not among the candidates */
-                    if (lane == 0) cb[23] = (uint32_t) dc;
+                    if (lane < ncand) { cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_T] = myrow; cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_POS] = mypos; }
+                    const int dc = diag_t < 0 ? SLIP_DC_NONE : (dm ? slip_ctz64(dm) : SLIP_DC_NOTSENT);
+                    if (lane == 0) cb[CBH_DIAGC] = (uint32_t) dc;
                     /* the choice itself, HERE, side by side for the columns of the batch: every comparison slip_get_pivot makes
                      * is among this column's own candidates (class S: a * rho[j-1] with one rho for all, so |a| decides,
                      * slip_get_smallest_pivot.c:58-101 / slip_get_largest_pivot.c; the diagonal rule, slip_get_pivot.c:68-146, is a
                      * ratio of two of them).  Only a tie is broken by positions, which a swap earlier in this batch may still
-                     * change: such a column is chosen again in the serial step (word 24, bit 8). */
+                     * change: such a column is chosen again in the serial step (CBH_CHOICE: SLIP_CH_TIE). */
                     {
                         const bool isc = lane < ncand;
-                        const uint32_t c_a0 = isc ? cb[32 + 6 * lane + 1] : 0u, c_a1 = isc ? cb[32 + 6 * lane + 2] : 0u, c_ax = isc ? cb[32 + 6 * lane + 3] : 0u;
+                        const uint32_t c_a0 = isc ? cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_A0] : 0u, c_a1 = isc ? cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_A1] : 0u, c_ax = isc ? cb[SLIP_CB_CANDS + SLIP_CAND_WORDS * lane + CAND_AUX] : 0u;
                         const uint64_t av = (uint64_t) c_a0 | ((uint64_t) c_a1 << 32);
                         const uint64_t mykey = isc ? (kind == 0 ? av : ~av) : ~0ull;
-                        const uint32_t mh = slip_wave_min_u32((uint32_t)(mykey >> 32));
-                        const uint32_t ml = slip_wave_min_u32((uint32_t)(mykey >> 32) == mh ? (uint32_t) mykey : 0xFFFFFFFFu);
-                        const uint64_t mk = ((uint64_t) mh << 32) | ml;
+                        const uint64_t mk = slip_wave_min_u64(mykey);
                         const uint64_t tie = slip_ballot(isc && mykey == mk);
                         uint32_t spec = 0;
                         int bc = 0;
-                        if (slip_popc64(tie) > 1) spec = 0x100u;
-                        else if (!tie) spec = 0x400u;
+                        if (slip_popc64(tie) > 1) spec = SLIP_CH_TIE;
+                        else if (!tie) spec = SLIP_CH_NONE;
                         else {
                             bc = slip_ctz64(tie);
-                            if (diagpref && dc != 0xFF && dc != bc) {
-                                if (dc == 0xFE) spec = 0x200u;               /* the diagonal row is not among the candidates sent: the worker decides */
-                                else if (scheme == 1 || P.tol_mode == 0) bc = dc;
+                            if (diagpref && dc != SLIP_DC_NONE && dc != bc) {
+                                if (dc == SLIP_DC_NOTSENT) spec = SLIP_CH_WORKER;               /* the diagonal row is not among the candidates sent: the worker decides */
                                 else {
                                     const uint64_t ab = (uint64_t) slip_readlane(c_a0, bc) | ((uint64_t) slip_readlane(c_a1, bc) << 32);
                                     const uint64_t ad = (uint64_t) slip_readlane(c_a0, dc) | ((uint64_t) slip_readlane(c_a1, dc) << 32);
-                                    const int tk = slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? ab : ad, scheme == 3 ? ad : ab);
-                                    if (tk < 0) spec = 0x200u; else if (tk) bc = dc;
-                                    /* scheme 4 takes the diagonal when the largest candidate a*rho[j-1] is negative; rho[j-1]'s
-                                     * sign is known in the serial step only: the column is chosen again there */
-                                    else if (scheme == 4) spec = 0x100u;
+                                    /* (the best candidate's sign, a's times rho[j-1]'s, is known in the serial step only: when scheme 4
+                                     * keeps it, the column is chosen again there) */
+                                    const int tk = slip_diag_small(scheme, P.tol_mode, P.tol_m, P.tol_e, ab, ad, -1);
+                                    if (tk == SLIP_DIAG_UNDECIDED) spec = SLIP_CH_WORKER; else if (tk == SLIP_DIAG_TAKE) bc = dc;
+                                    else if (scheme == 4) spec = SLIP_CH_TIE;
                                     SLIP_TRACE_L0("diag col %d site batch: tk %d spec %x\n", j, tk, spec);
                                 }
                             }
                         }
                         const uint32_t s_row = slip_readlane(myrow, bc), s_a0 = slip_readlane(c_a0, bc), s_a1 = slip_readlane(c_a1, bc);
                         const uint32_t s_ax = slip_readlane(c_ax, bc), s_pos = slip_readlane(mypos, bc);
-                        if (lane == 0) { cb[24] = spec | (uint32_t) bc; cb[25] = s_row; cb[26] = s_a0; cb[27] = s_a1; cb[28] = s_ax; cb[29] = s_pos; }
+                        if (lane == 0) { cb[CBH_CHOICE] = spec | (uint32_t) bc; cb[CBH_PROW] = s_row; cb[CBH_A0] = s_a0; cb[CBH_A1] = s_a1; cb[CBH_AUX] = s_ax; cb[CBH_PPOS] = s_pos; }
                     }
                 }
             } else if (kindp == 1) {
-                if (!mirror || (int) cb[22] < 1 || (int) cb[22] > SLIP_PKG_FULLMAX || stamp0 < 1 || stamp0 - 1 < sv[C_PR0] || (hver[SLIP_CB + i] >> 8) != (uint32_t)(4 * (int) cb[22]) + (1u << 15)) hit = 1;
+                if (!mirror || (int) cb[CBH_NFULL] < 1 || (int) cb[CBH_NFULL] > SLIP_PKG_FULLMAX || stamp0 < 1 || stamp0 - 1 < sv[C_PR0] || (hver[SLIP_CB + i] >> 8) != (uint32_t)(4 * (int) cb[CBH_NFULL]) + (1u << 15)) hit = 1;
             } else hit = 1;
-            if (slip_ballot(hit) && lane == 0) cb[18] = 1u;
+            if (slip_ballot(hit) && lane == 0) cb[CBH_REJ] = SLIP_REJ_AGAIN;
         }
         if (!have) {
             if (tid == T - 1) sv64[SV_LNZ / 2] = slip_ld_i64(&P.Lp[kc]);
@@ -672,20 +727,20 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
         /* (b2) a row of the pattern that becomes pivotal earlier in this batch sends the package back (the pivots before the batch
          * were checked above).  The pivots chosen above are the ones the serial step commits -- or the batch ends before this column
          * -- so each wave checks its column against them; columns whose pivot is not known yet (a tie, a full package) are left to
-         * the serial step (word 30: their mask) */
+         * the serial step (CBH_UNK: their mask) */
         for (int i = wave; i < nb; i += nw) {
             uint32_t *cb = cbuf + i * SLIP_CBW;
             uint32_t unk = 0;
-            if (!cb[18] && cb[21] == 0u) {
-                const int nrows = (int) cb[16];
-                const uint32_t *rows = cb + 128;
+            if (!cb[CBH_REJ] && cb[CBH_KIND] == 0u) {
+                const int nrows = (int) cb[CBH_NROWS];
+                const uint32_t *rows = cb + SLIP_CB_ROWS;
                 uint32_t rr[SLIP_PKG_NROWMAX / SLIP_WAVE];
 #pragma unroll
                 for (int q = 0; q < SLIP_PKG_NROWMAX / SLIP_WAVE; q++) rr[q] = lane + 64 * q < nrows ? rows[lane + 64 * q] : 0xFFFFFFFFu;
                 /* lane e: column kc + e's state */
                 const uint32_t *ce = cbuf + (lane < nb ? lane : 0) * SLIP_CBW;
-                const uint32_t e_pre = ce[18], e_kind = ce[21], e_spec = ce[24], e_row = ce[25];
-                const uint64_t known = slip_ballot(lane < i && !e_pre && e_kind == 0u && !(e_spec & 0x700u));
+                const uint32_t e_pre = ce[CBH_REJ], e_kind = ce[CBH_KIND], e_spec = ce[CBH_CHOICE], e_row = ce[CBH_PROW];
+                const uint64_t known = slip_ballot(lane < i && !e_pre && e_kind == 0u && !(e_spec & SLIP_CH_MASK));
                 unk = (uint32_t)(slip_ballot(lane < i && !e_pre) & ~known);
                 int hit = 0;
                 for (int e = 0; e < i; e++) {
@@ -697,9 +752,9 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                 }
                 const uint64_t anyhit = slip_ballot(hit);
                 slip_wave_sync_lds();
-                if (anyhit && lane == 0) cb[18] = 1u;
+                if (anyhit && lane == 0) cb[CBH_REJ] = SLIP_REJ_AGAIN;
             }
-            if (lane == 0) cb[30] = unk;
+            if (lane == 0) cb[CBH_UNK] = unk;
         }
         slip_block_sync();
         SLIP_CT(1);                                  /* 1: the packages into LDS */
@@ -723,49 +778,41 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
             SlipPiv M = *Mrec;
             /* (the swaps of the run: its publish records) */
             const uint32_t *pr_ = pub + (lane < nbc ? lane : 0) * SLIP_PUBW;
-            uint32_t bs_row = lane < nbc ? pr_[0] : 0xFFFFFFFFu, bs_disp = lane < nbc ? pr_[2] : 0xFFFFFFFFu, bs_opos = lane < nbc ? pr_[1] : 0xFFFFFFFFu;
-            const int xcap_ = P.xcap, wcapP = P.wcap, invcap_ = P.invcap, limb_cap_ = P.limb_cap, nworkers_ = P.nworkers;
-            const int64_t Lcap_nz_ = P.Lcap_nz, Lcap_nl_ = P.Lcap_nl, Ucap_nz_ = P.Ucap_nz, Ucap_nl_ = P.Ucap_nl;
-            uint32_t *const mbox0 = P.pkg.at() + (int64_t) nworkers_ * SLIP_PKG_WORDS;
+            uint32_t bs_row = lane < nbc ? pr_[PUB_PROW] : 0xFFFFFFFFu, bs_disp = lane < nbc ? pr_[PUB_DISP] : 0xFFFFFFFFu, bs_opos = lane < nbc ? pr_[PUB_PPOS] : 0xFFFFFFFFu;
+            const int nworkers_ = P.nworkers;
+            const SlipCaps caps = slip_caps(P);             /* (in registers along the chain: no LDS or scalar reloads per column) */
+            uint32_t *const mbox0 = slip_mailbox(P, 0);
             for (int i = nbc; i < nb; i++) {
                 const int j = kc + i;
                 uint32_t *cb = cbuf + i * SLIP_CBW;
                 uint32_t *pb = pub + i * SLIP_PUBW;
-                const uint32_t *cands = cb + 32, *rows = cb + 128;
+                const uint32_t *cands = cb + SLIP_CB_CANDS, *rows = cb + SLIP_CB_ROWS;
                 /* the header in one read; its fields through the scalar unit */
-                const uint32_t hdr = lane < 32 ? cb[lane] : 0u;
+                const uint32_t hdr = lane < SLIP_CB_HDRW ? cb[lane] : 0u;
 #define HF(w) ((int) slip_readlane(hdr, (w)))
-                const int nrows = HF(16), ncand = HF(1), stamp0 = HF(15), kindp = HF(21);
-                uint32_t *mbx = mbox0 + (int64_t)((uint32_t) HF(20) < (uint32_t) nworkers_ ? HF(20) : 0) * SLIP_MBOX_WORDS;     /* the worker's mailbox */
-                const int lm = slip_abs(M.len), brho = M.bits, slot = (lm + 3) >> 1;
-                const int slotw = (lm + 5) & ~1;
+                const int nrows = HF(CBH_NROWS), ncand = HF(PP_NCAND), stamp0 = HF(CBH_STAMP0), kindp = HF(CBH_KIND);
+                uint32_t *mbx = mbox0 + (int64_t)((uint32_t) HF(CBH_WORKER) < (uint32_t) nworkers_ ? HF(CBH_WORKER) : 0) * SLIP_MBOX_WORDS;     /* the worker's mailbox */
+                const int lm = slip_abs(M.len), brho = M.bits;
                 dig_t *sl = stage + i * SLIP_CB_SLOTW;
-                int reject = HF(18);                            /* 1: offered again / the worker's business; 2: for good */
+                int reject = HF(CBH_REJ);                            /* SLIP_REJ_* */
                 /* what both kinds leave for the publish step */
                 int e_pivrow = 0, e_pivpos = 0, lp_ = 0, pneg = 0, pbits = 0, nUc_all = 0, nLc = 0, nfin = 0, nlate = 0;
                 uint64_t U_l = 0, Lb_total = 0, plimbs = 0, lalloc = 0, plo = 0; int64_t poff = 0;
                 unsigned long long ec_src = 0, ec_read = 0, ec_str = 0, ec_upd = 0, ec_mac = 0;
                 /* the row at position j (the one the pivot changes places with): as loaded at the start of the batch, or the row a
                  * swap of this batch displaced to j */
-                int intermed2 = HF(17);
+                int intermed2 = HF(CBH_ROWJ);
                 { const uint64_t pm_ = slip_ballot(lane < i && bs_opos == (uint32_t) j); if (pm_) intermed2 = (int) slip_readlane(bs_disp, 63 - slip_clz64(pm_)); }      /* (the last such swap counts) */
                 SLIP_CT(10);
                 if (!reject && kindp == 0) {
                     /* ---- kind 0: candidates only ---- */
-                    const int nS = HF(2), nB = HF(6);
-                    nUc_all = HF(3); U_l = (uint64_t)(uint32_t) HF(4);
-                    const int nA = lm > 2 ? nS : 0;
-                    const int maxc = HF(9) - SLIP_PP_BIAS + brho;
-                    const int maxub_all = maxc > HF(10) ? maxc : HF(10);
-                    const uint64_t L_b = (uint64_t)(uint32_t) HF(5) + (uint64_t) nB * (uint64_t)((brho + 63) >> 6) + (lm <= 2 ? 2ull * (uint64_t) nS : 0ull);
-                    const uint64_t preserve = (uint64_t)((maxub_all + 63) >> 6) + 1;
-                    Lb_total = (uint64_t) nA * (uint64_t) slot + preserve + L_b;
-                    const uint64_t Ub_total = U_l + preserve;
-                    nLc = nrows - nUc_all;
-                    /* the choice was made when the package was loaded (word 24; bit 8: a tie, decided below by positions as they
+                    const SlipColSizes Z = slip_col_sizes([&](int w) -> int { return HF(w); }, nrows, lm, brho);
+                    const int nA = Z.nA, slot = Z.slot;
+                    nUc_all = Z.nUc; U_l = (uint64_t)(uint32_t) HF(PP_UL); Lb_total = Z.Lb_total; nLc = Z.nLc;
+                    /* the choice was made when the package was loaded (CBH_CHOICE; SLIP_CH_TIE: a tie, decided below by positions as they
                      * are NOW), and the pattern was checked against the pivots of this batch that were known then; the others
-                     * (word 30: ties, full packages) are checked here */
-                    const uint32_t spec = (uint32_t) HF(24), unk = (uint32_t) HF(30);
+                     * (CBH_UNK: ties, full packages) are checked here */
+                    const uint32_t spec = (uint32_t) HF(CBH_CHOICE), unk = (uint32_t) HF(CBH_UNK);
                     if (unk) {
                         uint32_t rr[SLIP_PKG_NROWMAX / SLIP_WAVE];
 #pragma unroll
@@ -778,66 +825,52 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                 for (int q = 0; q < SLIP_PKG_NROWMAX / SLIP_WAVE; q++) if (rr[q] == r) hit = 1;
                             }
                         }
-                        if (slip_ballot(hit)) reject = 1;
+                        if (slip_ballot(hit)) reject = SLIP_REJ_AGAIN;
                     }
                     SLIP_CT(11);
-                    if (!reject) {
-                        const bool A_ok = lm + 2 <= xcap_ && lm + 2 <= 256;
-                        if (lm > SLIP_CB_SLOTW - 6 || slotw > SLIP_CB_SLOTW || (lm > 2 && !A_ok)) reject = 2;
-                        if (nB > 0) {
-                            const int Wn = ((HF(7) - SLIP_PP_BIAS + brho + 31) >> 5) + ((HF(8) + 31) >> 5) + 1;
-                            if (Wn > wcapP || Wn > xcap_ || Wn > invcap_) reject = 2;
-                        }
-                        if (Lnz_ + nLc > Lcap_nz_ || Lnl_ + (int64_t) Lb_total > Lcap_nl_) reject = 2;
-                        if (Unz_ + nUc_all + 1 > Ucap_nz_ || Unl_ + (int64_t) Ub_total > Ucap_nl_) reject = 2;
-                        if (limb_cap_ > 0 && (int)((maxub_all + 63) >> 6) > limb_cap_) reject = 2;
-                    }
+                    if (!reject && (lm > SLIP_CB_SLOTW - 6 || Z.slotw > SLIP_CB_SLOTW || slip_col_misfit(caps, Z, Lnz_, Lnl_, Unz_, Unl_))) reject = SLIP_REJ_FINAL;
                     SLIP_CT(12);
-                    uint32_t a0 = (uint32_t) HF(26), a1 = (uint32_t) HF(27), ax = (uint32_t) HF(28);
-                    e_pivrow = HF(25); e_pivpos = HF(29);
-                    if (!reject && (spec & 0x100u)) {
+                    uint32_t a0 = (uint32_t) HF(CBH_A0), a1 = (uint32_t) HF(CBH_A1), ax = (uint32_t) HF(CBH_AUX);
+                    e_pivrow = HF(CBH_PROW); e_pivpos = HF(CBH_PPOS);
+                    if (!reject && (spec & SLIP_CH_TIE)) {
                         /* a tie: equal values by pattern position (slip_get_smallest_pivot.c:58-101), the positions as the swaps of
                          * this batch have left them; then the diagonal preference as above */
                         const bool isc = lane < ncand;
-                        const uint32_t c_row = isc ? cands[6 * lane] : 0xFFFFFFFFu, c_a0 = isc ? cands[6 * lane + 1] : 0u, c_a1 = isc ? cands[6 * lane + 2] : 0u;
-                        const uint32_t c_ax = isc ? cands[6 * lane + 3] : 0u;
-                        uint32_t mypos = isc ? cands[6 * lane + 4] : BIG;
+                        const uint32_t c_row = isc ? cands[SLIP_CAND_WORDS * lane + CAND_T] : 0xFFFFFFFFu, c_a0 = isc ? cands[SLIP_CAND_WORDS * lane + CAND_A0] : 0u, c_a1 = isc ? cands[SLIP_CAND_WORDS * lane + CAND_A1] : 0u;
+                        const uint32_t c_ax = isc ? cands[SLIP_CAND_WORDS * lane + CAND_AUX] : 0u;
+                        uint32_t mypos = isc ? cands[SLIP_CAND_WORDS * lane + CAND_POS] : BIG;
                         for (int e = 0; e < i; e++) {
                             const uint32_t d = slip_readlane(bs_disp, e), o = slip_readlane(bs_opos, e);
                             if (c_row == d) mypos = o;
                         }
                         const uint64_t av = (uint64_t) c_a0 | ((uint64_t) c_a1 << 32);
                         const uint64_t mykey = isc ? (kind == 0 ? av : ~av) : ~0ull;
-                        const uint32_t mh = slip_wave_min_u32((uint32_t)(mykey >> 32));
-                        const uint32_t ml = slip_wave_min_u32((uint32_t)(mykey >> 32) == mh ? (uint32_t) mykey : 0xFFFFFFFFu);
-                        const uint64_t mk = ((uint64_t) mh << 32) | ml;
+                        const uint64_t mk = slip_wave_min_u64(mykey);
                         const uint64_t tie = slip_ballot(isc && mykey == mk);
                         int est = 0, bc = 0;
                         const uint32_t bp = slip_wave_min_u32(((tie >> lane) & 1ull) ? mypos : BIG);
                         const uint64_t bm_ = slip_ballot(((tie >> lane) & 1ull) && mypos == bp);
                         est = bm_ ? 0 : SLIPDEV_INTERNAL;
                         bc = bm_ ? slip_ctz64(bm_) : 0;
-                        const int dc = HF(23);
-                        if (!est && diagpref && dc != 0xFF && dc != bc) {
-                            if (dc == 0xFE) est = -1;                   /* not among the candidates it sent: the worker decides */
-                            else if (scheme == 1 || P.tol_mode == 0) bc = dc;
+                        const int dc = HF(CBH_DIAGC);
+                        if (!est && diagpref && dc != SLIP_DC_NONE && dc != bc) {
+                            if (dc == SLIP_DC_NOTSENT) est = -1;                   /* not among the candidates it sent: the worker decides */
                             else {
                                 const uint64_t ab = (uint64_t) slip_readlane(c_a0, bc) | ((uint64_t) slip_readlane(c_a1, bc) << 32);
                                 const uint64_t ad = (uint64_t) slip_readlane(c_a0, dc) | ((uint64_t) slip_readlane(c_a1, dc) << 32);
-                                /* scheme 4: a negative largest candidate yields to the diagonal; its sign is a's times rho[j-1]'s */
-                                const int neg = scheme == 4 && (int)((slip_readlane(c_ax, bc) >> 14) & 1u) != (M.len < 0);
-                                const int tk = neg ? 1 : slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? ab : ad, scheme == 3 ? ad : ab);
+                                const int neg = (int) slip_aux_neg(slip_readlane(c_ax, bc)) != (M.len < 0);        /* the best candidate's sign: a's times rho[j-1]'s */
+                                const int tk = slip_diag_small(scheme, P.tol_mode, P.tol_m, P.tol_e, ab, ad, neg);
                                 SLIP_TRACE_L0("diag col %d site serial: best negative %d take %d\n", j, neg, tk);
-                                if (tk < 0) est = -1; else if (tk) bc = dc;
+                                if (tk == SLIP_DIAG_UNDECIDED) est = -1; else if (tk == SLIP_DIAG_TAKE) bc = dc;
                             }
                         }
-                        if (est > 0) { if (lane == 0) { if (!st->dbg_who) { st->dbg_who = 120; st->dbg_k = j; st->dbg_a = ncand; st->dbg_b = (int32_t) tie; } slip_raise_stop(st, 0, SLIPDEV_INTERNAL); } reject = 2; }
-                        else if (est < 0) reject = 2;
+                        if (est > 0) { if (lane == 0) { if (!st->dbg_who) { st->dbg_who = 120; st->dbg_k = j; st->dbg_a = ncand; st->dbg_b = (int32_t) tie; } slip_raise_stop(st, 0, SLIPDEV_INTERNAL); } reject = SLIP_REJ_FINAL; }
+                        else if (est < 0) reject = SLIP_REJ_FINAL;
                         a0 = slip_readlane(c_a0, bc); a1 = slip_readlane(c_a1, bc); ax = slip_readlane(c_ax, bc);
                         e_pivrow = (int) slip_readlane(c_row, bc); e_pivpos = (int) slip_readlane(mypos, bc);
                     } else if (!reject) {
-                        if (spec & 0x400u) { if (lane == 0) { if (!st->dbg_who) { st->dbg_who = 120; st->dbg_k = j; st->dbg_a = ncand; st->dbg_b = (int32_t) spec; } slip_raise_stop(st, 0, SLIPDEV_INTERNAL); } reject = 2; }
-                        else if (spec & 0x200u) reject = 2;
+                        if (spec & SLIP_CH_NONE) { if (lane == 0) { if (!st->dbg_who) { st->dbg_who = 120; st->dbg_k = j; st->dbg_a = ncand; st->dbg_b = (int32_t) spec; } slip_raise_stop(st, 0, SLIPDEV_INTERNAL); } reject = SLIP_REJ_FINAL; }
+                        else if (spec & SLIP_CH_WORKER) reject = SLIP_REJ_FINAL;
                         else {
                             /* the pivot row may have been displaced by a swap of this batch: the last one counts */
                             const uint64_t dm_ = slip_ballot(lane < i && bs_disp == (uint32_t) e_pivrow);
@@ -847,7 +880,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                     SLIP_CT(13);
                     if (!reject) {
                         /* rho[j] = the pivot's one-limb value times rho[j-1]: into the stage slot (for the publish step) and into Ms */
-                        const int nd = (int)((ax >> 12) & 3u);
+                        const int nd = slip_aux_nd(ax);
                         if (lm <= 2) {
                             const slip_u128 y = (slip_u128)((uint64_t) a0 | ((uint64_t) a1 << 32)) * M.lo;
                             pbits = slip_bits128(y); lp_ = (pbits + 31) >> 5; plo = (uint64_t) y;
@@ -862,22 +895,22 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                             if (kind == 1) key = ~key;
                             pbits = (int)(key >> 40); lp_ = len;
                         }
-                        pneg = (int)((ax >> 14) & 1u) ^ (M.len < 0);
+                        pneg = (int) slip_aux_neg(ax) ^ (M.len < 0);
                         plimbs = (uint64_t)((lp_ + 1) >> 1);
-                        poff = lm > 2 ? Lnl_ + (int64_t)(ax & 0x3FFu) * slot : Lnl_ + (int64_t) nA * slot;
+                        poff = lm > 2 ? Lnl_ + (int64_t) slip_aux_slot(ax) * slot : Lnl_ + (int64_t) nA * slot;
                         lalloc = (uint64_t) nA * (uint64_t) slot + (lm > 2 ? 0ull : plimbs);
                         if (lane == 0) ld_col[j & (SLIP_CB_RING - 1)] = 0xFFFFFFFFu;     /* its L values are long: not in the engine's ring */
                     }
                     SLIP_CT(15);
                 } else if (!reject && kindp == 1) {
                     /* ---- kind 1: the chain engine ---- */
-                    const int nfull = (int) cb[22];
-                    const uint32_t *prow = cb + 128, *pvlo = prow + nfull, *pvhi = pvlo + nfull, *pmeta = pvhi + nfull;
+                    const int nfull = (int) cb[CBH_NFULL];
+                    const uint32_t *prow = cb + SLIP_CB_ROWS, *pvlo = prow + nfull, *pvhi = pvlo + nfull, *pmeta = pvhi + nfull;
                     const int pr0 = sv[C_PR0];
                     uint32_t lw = (uint32_t) sv[C_LW];
                     const int col = P.q[j];
                     SlipSmallPiv Mp; Mp.lo = M.lo; Mp.inv = M.inv64; Mp.ctz = M.ctz; Mp.sgn = M.len < 0 ? -1 : 1; Mp.small = lm <= 2 && lm >= 1; Mp.bits = M.bits;
-                    if (!Mp.small) reject = 2;
+                    if (!Mp.small) reject = SLIP_REJ_FINAL;
                     int nst = nfull;
                     uint32_t lsrc[4] = {BIG, BIG, BIG, BIG};
                     if (!reject) {
@@ -912,16 +945,16 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                         const int ol = slip_ctz64(ob);
                         const int jt = ol + 64 * (int) slip_readlane((uint32_t)(oq < 0 ? 0 : oq), ol);
                         const int cs = c & (SLIP_CB_RING - 1);
-                        if (c - 1 < pr0) { reject = 1; break; }
+                        if (c - 1 < pr0) { reject = SLIP_REJ_AGAIN; break; }
                         if (ld_col[cs] != (uint32_t) c || (int32_t) ld_cnt[cs] < 0 || (uint32_t)(lw - ld_start[cs]) > (uint32_t) SLIP_LRING) {
                             /* L(:,c) is not in the ring (its worker committed it, or it was pushed out): from memory if its worker has
                              * published it (stage 2, Lready[c]) -- otherwise the package goes back and its worker waits for that */
                             int rdy = 0;
                             if (lane == 0) rdy = slip_agent_load_i32(P.Lready.at(c));
                             rdy = (int) slip_bcast0_u32((uint32_t) rdy);
-                            if (!rdy) { reject = 1; break; }
+                            if (!rdy) { reject = SLIP_REJ_AGAIN; break; }
                             const int64_t m0 = slip_ld_i64(&P.Lp[c]), m1 = slip_ld_i64(&P.Lp[c + 1]);
-                            if (m1 - m0 > (int64_t) SLIP_ENG_ROWS || m1 < m0) { reject = 2; break; }
+                            if (m1 - m0 > (int64_t) SLIP_ENG_ROWS || m1 < m0) { reject = SLIP_REJ_FINAL; break; }
                             const int cnt = (int)(m1 - m0);
                             int bad = 0;
                             for (int e0 = 0; e0 < cnt; e0 += SLIP_WAVE) {
@@ -936,13 +969,13 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                     lring[at] = (uint32_t) ri | (le.len < 0 ? 0x80000000u : 0u); lring[at + 1] = (uint32_t) v; lring[at + 2] = (uint32_t)(v >> 32);
                                 }
                             }
-                            if (slip_ballot(bad)) { reject = 2; break; }
+                            if (slip_ballot(bad)) { reject = SLIP_REJ_FINAL; break; }
                             if (lane == 0) { ld_start[cs] = lw; ld_cnt[cs] = (uint32_t) cnt; ld_col[cs] = (uint32_t) c; }
                             lw += (uint32_t) cnt;
                             slip_wave_sync_lds();
                         }
                         const SlipSmallPiv R = pring_get(c), Dv = pring_get(c - 1);
-                        if (!R.small || !Dv.small) { reject = 2; break; }
+                        if (!R.small || !Dv.small) { reject = SLIP_REJ_FINAL; break; }
                         const uint32_t jrow = est_row[jt];
                         uint64_t xj = (uint64_t) est_vlo[jt] | ((uint64_t) est_vhi[jt] << 32);
                         const uint32_t mj = est_meta[jt];
@@ -953,10 +986,10 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                             const slip_u128 y = (slip_u128) xj * Dv.lo; sj *= Dv.sgn;
                             if (hj >= 0) {
                                 const SlipSmallPiv H = pring_get(hj);
-                                if (hj < pr0 || !H.small || slip_bits128(y) - H.bits + 1 > 64) { reject = 2; break; }
+                                if (hj < pr0 || !H.small || slip_bits128(y) - H.bits + 1 > 64) { reject = SLIP_REJ_FINAL; break; }
                                 xj = slip_divexact_to64(y, H.ctz, H.inv); sj *= H.sgn;      /* the quotient fits one limb: one multiply */
                             } else {
-                                if ((uint64_t)(y >> 64)) { reject = 2; break; }
+                                if ((uint64_t)(y >> 64)) { reject = SLIP_REJ_FINAL; break; }
                                 xj = (uint64_t) y;
                             }
                         }
@@ -977,7 +1010,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                             const int fresh = has && idx < 0;
                             const uint64_t fm = slip_ballot(fresh);
                             const int nf = slip_popc64(fm);
-                            if (nst + nf > SLIP_ENG_ROWS - 1) { reject = 2; break; }       /* places travel as bytes: 255 rows */
+                            if (nst + nf > SLIP_ENG_ROWS - 1) { reject = SLIP_REJ_FINAL; break; }       /* places travel as bytes: 255 rows */
                             if (fresh) {
                                 /* structural discovery (what the reference's DFS does): a row the column did not hold yet */
                                 idx = nst + slip_popc64(fm & ((1ull << lane) - 1ull));
@@ -1032,7 +1065,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                 const uint64_t um = slip_ballot(upd), xm = slip_ballot(upd && had_x);
                                 ec_upd += (unsigned long long) slip_popc64(um); ec_mac += (unsigned long long)(slip_popc64(um) + slip_popc64(xm));
                             }
-                            if (slip_ballot(ovf)) { reject = 2; break; }
+                            if (slip_ballot(ovf)) { reject = SLIP_REJ_FINAL; break; }
                             slip_wave_sync_lds();
                             if (nf)
 #pragma unroll
@@ -1070,7 +1103,7 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                 }
                             }
                         }
-                        if (slip_ballot(ovf)) reject = 2;
+                        if (slip_ballot(ovf)) reject = SLIP_REJ_FINAL;
                         if (!reject) {
                             uint64_t Lex = 0; int nLl = 0;
                             uint64_t kmin = ~0ull;
@@ -1081,10 +1114,8 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                 const uint64_t key = (isL[q] && fin[q]) ? (kind == 0 ? fin[q] : ~fin[q]) : ~0ull;
                                 if (key < kmin) kmin = key;
                             }
-                            const uint32_t mh = slip_wave_min_u32((uint32_t)(kmin >> 32));
-                            const uint32_t ml = slip_wave_min_u32((uint32_t)(kmin >> 32) == mh ? (uint32_t) kmin : 0xFFFFFFFFu);
-                            const uint64_t mk = ((uint64_t) mh << 32) | ml;
-                            if (mk == ~0ull) reject = 2;            /* no nonzero non-pivotal row: the worker reports the singular column */
+                            const uint64_t mk = slip_wave_min_u64(kmin);
+                            if (mk == ~0ull) reject = SLIP_REJ_FINAL;            /* no nonzero non-pivotal row: the worker reports the singular column */
                             else {
                                 /* equal values: the earlier pattern position wins (slip_get_smallest_pivot.c:79) */
                                 uint32_t bpos = BIG; int bq = -1;
@@ -1106,24 +1137,20 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                                         const uint64_t dv = (uint64_t) est_vlo[dt] | ((uint64_t) est_vhi[dt] << 32);
                                         const uint64_t bv = (uint64_t) est_vlo[pt] | ((uint64_t) est_vhi[pt] << 32);
                                         if (dv != 0) {
-                                            if (scheme == 1 || P.tol_mode == 0) pt = dt;
-                                            else {
-                                                /* scheme 4: a negative largest candidate yields to the diagonal */
-                                                const int neg = scheme == 4 && (est_meta[pt] >> 31);
-                                                const int tk = neg ? 1 : slip_tol_small(P.tol_m, P.tol_e, scheme == 3 ? bv : dv, scheme == 3 ? dv : bv);
-                                                SLIP_TRACE_L0("diag col %d site engine: best negative %d take %d\n", j, neg, tk);
-                                                if (tk < 0) reject = 2; else if (tk) pt = dt;
-                                            }
+                                            const int neg = (int)(est_meta[pt] >> 31);
+                                            const int tk = slip_diag_small(scheme, P.tol_mode, P.tol_m, P.tol_e, bv, dv, neg);
+                                            SLIP_TRACE_L0("diag col %d site engine: best negative %d take %d\n", j, neg, tk);
+                                            if (tk == SLIP_DIAG_UNDECIDED) reject = SLIP_REJ_FINAL; else if (tk == SLIP_DIAG_TAKE) pt = dt;
                                         }
                                     }
                                 }
                             }
                             /* E5: the sums of stage 1 */
                             if (!reject) {
-                                nUc_all = (int) cb[3] + nlate; U_l = (uint64_t) cb[4] + (uint64_t) ulate; nLc = nLl;
+                                nUc_all = (int) cb[PP_NUC] + nlate; U_l = (uint64_t) cb[PP_UL] + (uint64_t) ulate; nLc = nLl;
                                 Lb_total = Lex; plimbs = 1; lalloc = 1; poff = Lnl_;
-                                if (Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) reject = 2;
-                                if (Unz_ + nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t)(U_l + plimbs) > P.Ucap_nl) reject = 2;
+                                if (Lnz_ + nLc > P.Lcap_nz || Lnl_ + (int64_t) Lb_total > P.Lcap_nl) reject = SLIP_REJ_FINAL;
+                                if (Unz_ + nUc_all + 1 > P.Ucap_nz || Unl_ + (int64_t)(U_l + plimbs) > P.Ucap_nl) reject = SLIP_REJ_FINAL;
                             }
                             if (!reject) {
                                 const uint64_t pv = (uint64_t) est_vlo[pt] | ((uint64_t) est_vhi[pt] << 32);
@@ -1165,10 +1192,10 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                     for (int q = 0; q < 4 && 64 * q < nst; q++) { const int t = lane + 64 * q; if (t < nst) slotm[est_row[t]] = 0; }
                     SLIP_CT(19);
                     if (lane == 0) sv[C_LW] = (int32_t) lw;                                                   /* (columns fetched from memory stay in the ring also when this package goes back) */
-                    if (reject && lane == 0) slip_st_u32(mbx + SLIP_PKG_OUT + 1, (uint32_t) reject);      /* why it goes back (1: try again later) */
+                    if (reject && lane == 0) slip_st_u32(mbx + MB_PROW, (uint32_t) reject);      /* why it goes back */
                 }
                 slip_wave_sync_lds();
-                SLIP_TRACE_L0("committer: col %d kind %d reject %d pre %d (stamp0 %d nfull %d nrows %d nlate %d pr0 %d ring0 %d)\n", j, kindp, reject, (int) cb[18], stamp0, (int) cb[22], nrows, nlate, sv[C_PR0], sv[C_RING0]);
+                SLIP_TRACE_L0("committer: col %d kind %d reject %d pre %d (stamp0 %d nfull %d nrows %d nlate %d pr0 %d ring0 %d)\n", j, kindp, reject, (int) cb[CBH_REJ], stamp0, (int) cb[CBH_NFULL], nrows, nlate, sv[C_PR0], sv[C_RING0]);
                 if (reject) { rej = j; break; }
                 /* ---- the column is committed: what the next one needs stays in registers; the rings and the publish record in LDS ---- */
                 {
@@ -1195,21 +1222,21 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                     /* the publish record: lane w writes word w */
                     {
                         uint32_t v = 0;
-                        const uint32_t wk_ = (uint32_t) HF(20);
+                        const uint32_t wk_ = (uint32_t) HF(CBH_WORKER);
                         switch (lane) {
-                            case 0: v = (uint32_t) e_pivrow; break; case 1: v = (uint32_t) e_pivpos; break; case 2: v = (uint32_t) intermed2; break;
-                            case 3: v = (uint32_t)(pneg ? -lp_ : lp_); break; case 4: v = (uint32_t) pbits; break; case 5: v = (uint32_t) lp_; break;
-                            case 6: v = (uint32_t) nfin; break; case 7: v = (uint32_t) nlate; break;
-                            case 8: v = (uint32_t) poff; break; case 9: v = (uint32_t)((uint64_t) poff >> 32); break;
-                            case 10: v = (uint32_t) lalloc; break; case 11: v = (uint32_t)(lalloc >> 32); break;
-                            case 12: v = (uint32_t) nUnz; break; case 13: v = (uint32_t)((uint64_t) nUnz >> 32); break;
-                            case 14: v = (uint32_t) nLnz; break; case 15: v = (uint32_t)((uint64_t) nLnz >> 32); break;
-                            case 16: v = (uint32_t) nUnl; break; case 17: v = (uint32_t)((uint64_t) nUnl >> 32); break;
-                            case 18: v = (uint32_t) nLnl; break; case 19: v = (uint32_t)((uint64_t) nLnl >> 32); break;
-                            case 20: v = wk_; break; case 21: v = (uint32_t) kindp; break;
+                            case PUB_PROW: v = (uint32_t) e_pivrow; break; case PUB_PPOS: v = (uint32_t) e_pivpos; break; case PUB_DISP: v = (uint32_t) intermed2; break;
+                            case PUB_SLEN: v = (uint32_t)(pneg ? -lp_ : lp_); break; case PUB_BITS: v = (uint32_t) pbits; break; case PUB_LEN: v = (uint32_t) lp_; break;
+                            case PUB_NFIN: v = (uint32_t) nfin; break; case PUB_NLATE: v = (uint32_t) nlate; break;
+                            case PUB_POFF: v = (uint32_t) poff; break; case PUB_POFF + 1: v = (uint32_t)((uint64_t) poff >> 32); break;
+                            case PUB_LALLOC: v = (uint32_t) lalloc; break; case PUB_LALLOC + 1: v = (uint32_t)(lalloc >> 32); break;
+                            case PUB_UNZ: v = (uint32_t) nUnz; break; case PUB_UNZ + 1: v = (uint32_t)((uint64_t) nUnz >> 32); break;
+                            case PUB_LNZ: v = (uint32_t) nLnz; break; case PUB_LNZ + 1: v = (uint32_t)((uint64_t) nLnz >> 32); break;
+                            case PUB_UNL: v = (uint32_t) nUnl; break; case PUB_UNL + 1: v = (uint32_t)((uint64_t) nUnl >> 32); break;
+                            case PUB_LNL: v = (uint32_t) nLnl; break; case PUB_LNL + 1: v = (uint32_t)((uint64_t) nLnl >> 32); break;
+                            case PUB_WORKER: v = wk_; break; case PUB_KIND: v = (uint32_t) kindp; break;
                             default: break;
                         }
-                        if (lane < 22) pb[lane] = v;
+                        if (lane < PUB_R_LEN) pb[lane] = v;
                     }
                     /* the permutation swap (slip_get_pivot.c:164-176) is stored HERE, by this one wave, column after column:
                      * successive columns of a batch write the same words (a row displaced to position p, the next pivot taken from
@@ -1257,11 +1284,11 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
             const int j = kc + i;
             const uint32_t *pb = pub + i * SLIP_PUBW;
             const dig_t *src = stage + i * SLIP_CB_SLOTW;
-            uint32_t *mbx = P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) pb[20] * SLIP_MBOX_WORDS;
-            const int e_pivrow = (int) pb[0], e_pivpos = (int) pb[1], intermed2 = (int) pb[2], lp_ = (int) pb[5];
-            const int64_t poff = (int64_t)((uint64_t) pb[8] | ((uint64_t) pb[9] << 32));
+            uint32_t *mbx = slip_mailbox(P, pb[PUB_WORKER]);
+            const int e_pivrow = (int) pb[PUB_PROW], e_pivpos = (int) pb[PUB_PPOS], intermed2 = (int) pb[PUB_DISP], lp_ = (int) pb[PUB_LEN];
+            const int64_t poff = (int64_t)((uint64_t) pb[PUB_POFF] | ((uint64_t) pb[PUB_POFF + 1] << 32));
             const int z = slip_publish_digits((dig_t *)(P.Llimbs + poff), src, 0, lp_);
-            SlipPiv pr; pr.off = poff; pr.len = (int32_t) pb[3]; pr.bits = (int32_t) pb[4]; pr.ctz = z; pr.invlen = 0;
+            SlipPiv pr; pr.off = poff; pr.len = (int32_t) pb[PUB_SLEN]; pr.bits = (int32_t) pb[PUB_BITS]; pr.ctz = z; pr.invlen = 0;
             pr.lo = *(const uint64_t *) src; pr.inv64 = 0; pr.pad = 0;
             if (lp_ <= 2) pr.inv64 = slip_inv64(pr.lo >> z);
             /* every lane computes the same values; lane q issues store q: two store instructions instead of twenty-odd */
@@ -1274,12 +1301,12 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
                     case 2: a8 = pw + 2; v8 = pr.lo; break;
                     case 3: a8 = pw + 3; v8 = (uint64_t)(uint32_t) pr.ctz; break;
                     case 4: a8 = pw + 4; v8 = pr.inv64; break;
-                    case 5: a8 = (uint64_t *) &P.Up[j + 1]; v8 = (uint64_t) pb[12] | ((uint64_t) pb[13] << 32); break;
-                    case 6: a8 = (uint64_t *) &P.Lp[j + 1]; v8 = (uint64_t) pb[14] | ((uint64_t) pb[15] << 32); break;
-                    case 7: a8 = (uint64_t *) &P.Uo[j + 1]; v8 = (uint64_t) pb[16] | ((uint64_t) pb[17] << 32); break;
-                    case 8: a8 = (uint64_t *) &P.Lo[j + 1]; v8 = (uint64_t) pb[18] | ((uint64_t) pb[19] << 32); break;
-                    case 9: a8 = (uint64_t *)(mbx + SLIP_PKG_OUT + 6); v8 = (uint64_t) poff; break;
-                    case 10: a8 = (uint64_t *)(mbx + SLIP_PKG_OUT + 8); v8 = (uint64_t) pb[10] | ((uint64_t) pb[11] << 32); break;
+                    case 5: a8 = (uint64_t *) &P.Up[j + 1]; v8 = (uint64_t) pb[PUB_UNZ] | ((uint64_t) pb[PUB_UNZ + 1] << 32); break;
+                    case 6: a8 = (uint64_t *) &P.Lp[j + 1]; v8 = (uint64_t) pb[PUB_LNZ] | ((uint64_t) pb[PUB_LNZ + 1] << 32); break;
+                    case 7: a8 = (uint64_t *) &P.Uo[j + 1]; v8 = (uint64_t) pb[PUB_UNL] | ((uint64_t) pb[PUB_UNL + 1] << 32); break;
+                    case 8: a8 = (uint64_t *) &P.Lo[j + 1]; v8 = (uint64_t) pb[PUB_LNL] | ((uint64_t) pb[PUB_LNL + 1] << 32); break;
+                    case 9: a8 = (uint64_t *)(mbx + MB_POFF); v8 = (uint64_t) poff; break;
+                    case 10: a8 = (uint64_t *)(mbx + MB_LALLOC); v8 = (uint64_t) pb[PUB_LALLOC] | ((uint64_t) pb[PUB_LALLOC + 1] << 32); break;
                     case 11: a8 = pw + 5; v8 = 0ull; break;                   /* (nobody has divided by this pivot yet) */
                     default: break;
                 }
@@ -1294,12 +1321,12 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
 #endif
                     case 4: a4 = (uint32_t *) P.sw_row.at(j); v4 = (uint32_t) intermed2; break;
                     case 5: a4 = (uint32_t *) P.sw_pos.at(j); v4 = (uint32_t) e_pivpos; break;
-                    case 6: a4 = mbx + SLIP_PKG_OUT + 1; v4 = (uint32_t) e_pivrow; break;
-                    case 7: a4 = mbx + SLIP_PKG_OUT + 2; v4 = (uint32_t) e_pivpos; break;
-                    case 8: a4 = mbx + SLIP_PKG_OUT + 3; v4 = pb[3]; break;
-                    case 9: a4 = mbx + SLIP_PKG_OUT + 4; v4 = pb[4]; break;
-                    case 10: a4 = mbx + SLIP_PKG_OUT + 5; v4 = pb[6]; break;
-                    case 11: a4 = mbx + SLIP_PKG_OUT + 10; v4 = pb[7]; break;
+                    case 6: a4 = mbx + MB_PROW; v4 = (uint32_t) e_pivrow; break;
+                    case 7: a4 = mbx + MB_PPOS; v4 = (uint32_t) e_pivpos; break;
+                    case 8: a4 = mbx + MB_SLEN; v4 = pb[PUB_SLEN]; break;
+                    case 9: a4 = mbx + MB_BITS; v4 = pb[PUB_BITS]; break;
+                    case 10: a4 = mbx + MB_NFIN; v4 = pb[PUB_NFIN]; break;
+                    case 11: a4 = mbx + MB_NLATE; v4 = pb[PUB_NLATE]; break;
                     default: break;
                 }
                 if (a4) slip_st_u32(a4, v4);
@@ -1311,13 +1338,13 @@ SLIP_DEV void slip_committer(const SlipParams &P, SlipState *st, uint32_t *lds)
         /* (e) the verdicts and the frontier */
         if (wave == 0) {
             slip_vm_drain();
-            if (lane < nbc) slip_st_u32(P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t)(pub + lane * SLIP_PUBW)[20] * SLIP_MBOX_WORDS + SLIP_PKG_OUT, (hver[lane] << 24) | (uint32_t)(kc + lane + 1));
+            if (lane < nbc) slip_st_u32(slip_mailbox(P, (pub + lane * SLIP_PUBW)[PUB_WORKER]) + MB_VERDICT, (hver[lane] << 24) | (uint32_t)(kc + lane + 1));
             SLIP_TL(lane < nbc, kc + lane, 2);   /* time line 2: committed by the committer */
             if (lane == 0) {
                 if (rej >= 0) {
                     const uint32_t rv = hver[rej - kc];
-                    const uint32_t rw = (cbuf + (rej - kc) * SLIP_CBW)[20];
-                    if (rw < (uint32_t) P.nworkers) slip_st_u32(P.pkg.at() + (int64_t) P.nworkers * SLIP_PKG_WORDS + (int64_t) rw * SLIP_MBOX_WORDS + SLIP_PKG_OUT, (uint32_t)(-(int32_t)((rv << 24) | (uint32_t)(rej + 1))));
+                    const uint32_t rw = (cbuf + (rej - kc) * SLIP_CBW)[CBH_WORKER];
+                    if (rw < (uint32_t) P.nworkers) slip_st_u32(slip_mailbox(P, rw) + MB_VERDICT, (uint32_t)(-(int32_t)((rv << 24) | (uint32_t)(rej + 1))));
                     sv[C_REJ] = rej; sv[C_REJV] = (int32_t) rv;
                 }
                 if (nbc > 0) {
