@@ -16,7 +16,8 @@
  * The same function is also exported as SLIP_hip_LU_factorize, for processes
  * that load both libraries and want to call either explicitly (the tests do).
  *
- * SLIP_LU_solve (SLIP_LU.h:941-949) is served the same way (SLIP_hip_LU_solve below).
+ * SLIP_LU_solve (SLIP_LU.h:941-949) is served the same way (SLIP_hip_LU_solve below), and so is SLIP_solve_double of the
+ * simple interface (SLIP_hip_solve_double below), which never leaves the device between the factorisation and the doubles.
  *
  * When the reference's SLIP_LU.h has been included first, this header only adds
  * the aliases; otherwise it declares layout-compatible mirrors of the four types
@@ -71,6 +72,8 @@ SLIP_info SLIP_LU_solve(mpq_t **x, SLIP_dense *b, const mpz_t *rhos, const SLIP_
 
 SLIP_info SLIP_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, SLIP_LU_analysis *S,
                             mpz_t *rhos, int32_t *pinv, SLIP_options *option);
+
+SLIP_info SLIP_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
 #endif
 
 SLIP_info SLIP_hip_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, SLIP_LU_analysis *S,
@@ -82,6 +85,14 @@ SLIP_info SLIP_hip_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, 
  * error codes as the reference; also exported under the reference's own name. */
 SLIP_info SLIP_hip_LU_solve(mpq_t **x, SLIP_dense *b, const mpz_t *rhos, const SLIP_sparse *L,
                             const SLIP_sparse *U, const int32_t *pinv);
+
+/* SLIP_solve_double (SLIP_LU/Source/SLIP_solve_double.c:41-104) on the GPU, with its prototype, argument checks (:53-57) and
+ * error codes: factorisation, substitution, SLIP_permute_x, SLIP_scale_x (times A->scale, over b->scale, a scale of 1 or 0
+ * left out as SLIP_scale_x.c:29-31, :43-45 do) and SLIP_get_double_soln all run on the device (slip_hip_factor_solve_double):
+ * x_doub[i][j], allocated by the caller (n rows of b->n doubles), receives entry i of the solution of right-hand side j, the
+ * exact rational truncated toward zero as mpq_get_d returns it.  Only those doubles cross back: no L, U, rhos or numerator
+ * is downloaded.  Also exported under the reference's own name. */
+SLIP_info SLIP_hip_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
 
 #ifdef __cplusplus
 }

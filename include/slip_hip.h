@@ -17,6 +17,8 @@
  *        SLIP_LU/Source/SLIP_LU_solve.c:41-86 (slip_forward_sub.c, slip_array_mul.c, slip_back_sub.c)
  *   slip_hip_factor_check,               <->  SLIP_check_solution (integer form)
  *   slip_hip_check_solution                   SLIP_LU/Source/SLIP_check_solution.c:31-113, SLIP_LU.h:988-993
+ *   slip_hip_factor_solve_double,        <->  the rest of SLIP_solve_double: SLIP_permute_x, SLIP_scale_x, SLIP_get_double_soln
+ *   slip_hip_solution_to_double               SLIP_LU/Source/SLIP_solve_double.c:84-100, SLIP_gmp.c:1063 (mpq_get_d)
  *   slip_hip_factor_solve_transpose,     <->  no counterpart: the reference solves A x = b only (KLU's klu_tsolve,
  *   slip_hip_factor_check_transpose           UMFPACK's A' system are the transposed solves of other sparse LUs)
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
@@ -129,7 +131,7 @@ int slip_hip_factor_download(const slip_hip_factor *f,
  * factorisation (K == n).  b is dense, nrhs columns of n entries in ORIGINAL row order:
  * blen[c*n+i] = signed limb count, limbs back to back in blimbs in that order.  The result is
  * what SLIP_LU_solve leaves in x before SLIP_permute_x / the division by det*scale
- * (SLIP_solve_double etc. do those on the host): integer numerators over det, entry c*n+p for
+ * (slip_hip_factor_solve_double below does those on the device too): integer numerators over det, entry c*n+p for
  * pivot POSITION p (x_final[q[p]] = xnum[p] / det), same signed-limb-slab form.  *xlen_out and
  * *xlimbs_out are malloc'ed; release with slip_hip_free. */
 int slip_hip_factor_solve(slip_hip_factor *f, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
@@ -202,6 +204,41 @@ int slip_hip_factor_check_transpose(slip_hip_factor *f, int32_t nrhs,
                                     int32_t *first_bad_pos, int64_t *bad_pos, void *stream);
 /* device ms of the last transposed solve's substitution kernels; *view_ms (may be NULL): the view build of that call, 0 if reused */
 double slip_hip_factor_solve_transpose_ms(const slip_hip_factor *f, double *view_ms);
+
+/* Solve straight to doubles: the tail of SLIP_solve_double (SLIP_LU/Source/SLIP_solve_double.c:84-100: SLIP_permute_x,
+ * SLIP_scale_x, SLIP_get_double_soln -> mpq_get_d per entry, SLIP_gmp.c:1063) on the device, after the substitution of
+ * slip_hip_factor_solve (transpose = 0) or slip_hip_factor_solve_transpose (transpose != 0), whose numerators never leave it.
+ *
+ * Every result is the EXACT rational truncated toward zero onto the double grid, bit for bit what mpq_get_d returns: 53
+ * significant bits in the normal range, never rounded up ((2^1024 - 1) / 1 -> 0x1.fffffffffffffp+1023); below 2^-1022 a
+ * multiple of 2^-1074 with the sign kept (-3 / 2^1075 -> -0x0.0000000000001p-1022); +0.0 when |q| < 2^-1074 or the numerator is
+ * zero (the sign is dropped); +-inf from 2^1024 on.  A quotient that lies exactly on the grid (integer and dyadic solutions)
+ * comes back exactly: the kernel settles what the leading bits leave open with one exact big-integer comparison.
+ *
+ * slip_hip_factor_solve_double: b as slip_hip_factor_solve (transpose = 0) or slip_hip_factor_solve_transpose (transpose != 0)
+ * takes it.  scale = snum / sden is applied before the ONE truncation: x = trunc(xnum * snum / (det * sden)); each part as a
+ * signed limb count and its limbs, a NULL limb pointer meaning 1 (then the count is ignored); a negative part carries its
+ * sign.  x_out[nrhs * n], allocated by the caller, is all that comes back: for the plain solve in ORIGINAL column order,
+ * x_out[c*n + q[p]] for pivot position p (SLIP_permute_x applied), for the transposed solve by original row id, as
+ * slip_hip_factor_solve_transpose returns its numerators.  Statuses as slip_hip_factor_solve; SLIP_HIP_INCORRECT_INPUT also for
+ * a scale part that is zero and for a plain (transpose = 0) call on a handle from slip_hip_factor_from_factors, which holds
+ * no q (the transposed call works there).  slip_hip_factor_solve / _solve_transpose afterwards return what they always did.
+ *
+ * slip_hip_solution_to_double: no handle; numerators x (n per right-hand side) and one nonzero denominator d_c per right-hand
+ * side, in the (x, d) form of slip_hip_check_solution; out[nrhs * n] in the order of the input.  Limb arrays travel with
+ * their capacities (x_limbs, d_limbs), high zero limbs are allowed.  For solutions the caller holds: a handle around given
+ * factors, rescaled output.  SLIP_HIP_INCORRECT_INPUT: nrhs < 1, a limb array longer than its capacity, d_c == 0.
+ *
+ * No CPU fallback: without a device the result is SLIP_HIP_DEVICE_ERROR. */
+int slip_hip_factor_solve_double(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                 int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
+                                 double *x_out, void *stream);
+int slip_hip_solution_to_double(int32_t n, int32_t nrhs, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs, double *out, void *stream);
+/* device ms of the conversion kernel of the last slip_hip_factor_solve_double; how many of its entries the kernel's lane pass
+ * (leading bits only) left to the exact wave pass */
+double slip_hip_factor_to_double_ms(const slip_hip_factor *f);
+int64_t slip_hip_factor_to_double_slow(const slip_hip_factor *f);
 
 /* Subtree farm (no counterpart in the reference, which has no parallelism): multiply the K committed
  * columns by per-column scales on the device -- L(:,k) and rho[k] by scale[k], an entry of U in the row whose pivot sits

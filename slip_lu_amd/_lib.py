@@ -36,7 +36,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_phase_cycles", "slip_hip_factor_solve", "slip_hip_factor_solve_ms",
            "slip_hip_factor_from_factors", "slip_hip_factor_rescale", "slip_hip_factor_set_prefix", "slip_hip_pool_release", "slip_hip_read_triplet", "slip_hip_write_triplet",
            "slip_hip_factor_check", "slip_hip_check_solution", "slip_hip_factor_check_ms",
-           "slip_hip_factor_solve_transpose", "slip_hip_factor_check_transpose", "slip_hip_factor_solve_transpose_ms")
+           "slip_hip_factor_solve_transpose", "slip_hip_factor_check_transpose", "slip_hip_factor_solve_transpose_ms",
+           "slip_hip_factor_solve_double", "slip_hip_solution_to_double", "slip_hip_factor_to_double_ms",
+           "slip_hip_factor_to_double_slow")
 
 _libs = {}
 
@@ -98,5 +100,13 @@ def load(path=None):
     lib.slip_hip_factor_check_transpose.restype = C.c_int
     lib.slip_hip_factor_solve_transpose_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.slip_hip_factor_solve_transpose_ms.restype = C.c_double
+    lib.slip_hip_factor_solve_double.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    lib.slip_hip_factor_solve_double.restype = C.c_int
+    lib.slip_hip_solution_to_double.argtypes = [C.c_int32, C.c_int32, vp, vp, i64, vp, vp, i64, vp, vp]
+    lib.slip_hip_solution_to_double.restype = C.c_int
+    lib.slip_hip_factor_to_double_ms.argtypes = [vp]
+    lib.slip_hip_factor_to_double_ms.restype = C.c_double
+    lib.slip_hip_factor_to_double_slow.argtypes = [vp]
+    lib.slip_hip_factor_to_double_slow.restype = C.c_int64
     _libs[path] = lib
     return lib

@@ -81,6 +81,32 @@ def check_solution(n, Ap, Ai, Alen, Alimbs, blen, blimbs, xlen, xlimbs, dlen, dl
     return _check_result(rc, "slip_hip_check_solution", first[:nrhs], bad[:nrhs])
 
 
+def _int_limbs(v):
+    """a Python int -> (signed limb count, limbs)"""
+    a, limbs = abs(int(v)), []
+    while a:
+        limbs.append(a & (2 ** 64 - 1)); a >>= 64
+    return (-len(limbs) if v < 0 else len(limbs)), np.array(limbs if limbs else [0], np.uint64)
+
+
+def solution_to_double(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, lib_path=None):
+    """Numerators over one nonzero denominator per right-hand side -> float64[nrhs, n] on the device
+    (slip_hip_solution_to_double): every entry is the exact rational truncated toward zero onto the double grid, bit for bit
+    what mpq_get_d returns.  x as limb slabs (n entries per right-hand side), output in the order of the input."""
+    lib = _lib.load(lib_path)
+    n, nrhs = int(n), int(nrhs)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
+    if nrhs >= 1 and (xlen.size != n * nrhs or dlen.size != nrhs):
+        raise ValueError("solution_to_double: xlen needs n*nrhs entries, dlen nrhs")
+    out = np.zeros((max(nrhs, 1), max(n, 1)), np.float64)
+    rc = lib.slip_hip_solution_to_double(n, nrhs, xlen.ctypes.data, xlimbs.ctypes.data, xcap, dlen.ctypes.data, dlimbs.ctypes.data,
+                                         dcap, out.ctypes.data, None)
+    if rc:
+        raise SlipError(rc, "slip_hip_solution_to_double")
+    return out[:nrhs, :n]
+
+
 def matgen(n, density, bits, seed, lib_path=None):
     """The benchmark's synthetic CSC (slip_matgen.h) -> Ap, Ai, Ax (int64 values)."""
     lib = _lib.load(lib_path)
@@ -266,6 +292,41 @@ class Factorization:
         self.lib.slip_hip_free(pl)
         self.lib.slip_hip_free(px)
         return xlen, xlimbs
+
+    def solve_double(self, blen, blimbs, nrhs=1, transpose=False, scale=None, stream=None):
+        """Solve and convert on the device (slip_hip_factor_solve_double): float64[nrhs, n], every entry the exact rational
+        scale * xnum / det truncated toward zero onto the double grid (what SLIP_solve_double returns through mpq_get_d).
+        Only the doubles come back.  b as `solve` takes it, the result in ORIGINAL column order (x[c, q[p]]); with
+        transpose=True b as `solve_transpose` takes it, the result by original row id.  scale: a pair (num, den) of Python
+        ints or a Fraction, both parts nonzero."""
+        blen = np.ascontiguousarray(blen, dtype=np.int32)
+        blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
+        nrhs = int(nrhs)
+        if nrhs >= 1 and blen.size != self.n * nrhs:
+            raise ValueError("blen must hold n*nrhs entries")
+        if blimbs.size == 0:
+            blimbs = np.zeros(1, dtype=np.uint64)
+        if scale is None:
+            sn = sd = (0, None)
+        else:
+            num, den = (scale.numerator, scale.denominator) if hasattr(scale, "numerator") else scale
+            sn, sd = _int_limbs(num), _int_limbs(den)
+        out = np.zeros((max(nrhs, 1), self.n), np.float64)
+        rc = self.lib.slip_hip_factor_solve_double(self.h, int(bool(transpose)), nrhs, blen.ctypes.data, blimbs.ctypes.data,
+                                                   sn[0], None if sn[1] is None else sn[1].ctypes.data,
+                                                   sd[0], None if sd[1] is None else sd[1].ctypes.data,
+                                                   out.ctypes.data, C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_solve_double")
+        return out[:nrhs]
+
+    def to_double_ms(self):
+        """device ms of the conversion kernel of the last solve_double"""
+        return self.lib.slip_hip_factor_to_double_ms(self.h)
+
+    def to_double_slow(self):
+        """entries of the last solve_double that the lane pass left to the exact wave pass"""
+        return self.lib.slip_hip_factor_to_double_slow(self.h)
 
     def check(self, blen, blimbs, xlen, xlimbs, nrhs=1, stream=None):
         """Exact check of a solve on the device (slip_hip_factor_check): A(:,q) xnum_c == det b_c, with b as `solve` takes

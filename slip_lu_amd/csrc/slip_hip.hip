@@ -124,6 +124,27 @@ template <int D> SLIP_DEV void slip_rescale_entry_reg(const dig_t *a, int la, co
     *len_out = len; *top_out = len ? wr_digit<D>(Y, len - 1) : 0u;
 }
 
+/* out = a * b, written as whole limbs (la + lb digits rounded up to even; nothing is written for la == 0): registers up to
+ * 256 digits, wb_mul_lo above.  *len_out = the product's significant digits, *top_out = the highest of them. */
+SLIP_DEV void slip_mul_entry(const dig_t *a, int la, const dig_t *b, int lb, dig_t *out, int *len_out, uint32_t *top_out)
+{
+    int len = 0; uint32_t top = 0;
+    if (la != 0) {
+        const int W = la + lb;
+        if (W <= 64) slip_rescale_entry_reg<1>(a, la, b, lb, out, W, &len, &top);
+        else if (W <= 128) slip_rescale_entry_reg<2>(a, la, b, lb, out, W, &len, &top);
+        else if (W <= 192) slip_rescale_entry_reg<3>(a, la, b, lb, out, W, &len, &top);
+        else if (W <= 256) slip_rescale_entry_reg<4>(a, la, b, lb, out, W, &len, &top);
+        else {
+            const int Wp = (W + 1) & ~1;
+            wb_mul_lo(out, a, la, b, lb, Wp);
+            len = wb_len(out, Wp);
+            top = len ? out[len - 1] : 0u;
+        }
+    }
+    *len_out = len; *top_out = top;
+}
+
 #ifndef SLIP_EMULATE
 __global__ void __launch_bounds__(256)
 slip_rescale_kernel(SlipRescaleArgs A)
@@ -148,20 +169,7 @@ static void slip_rescale_body(SlipRescaleArgs A)
         SlipEnt o = A.oent[e];
         dig_t *out = (dig_t *)(A.olimbs + o.off);
         int len = 0; uint32_t top = 0;
-        if (la == 0) { len = 0; }
-        else {
-            const int W = la + lb;
-            if (W <= 64) slip_rescale_entry_reg<1>(a, la, b, lb, out, W, &len, &top);
-            else if (W <= 128) slip_rescale_entry_reg<2>(a, la, b, lb, out, W, &len, &top);
-            else if (W <= 192) slip_rescale_entry_reg<3>(a, la, b, lb, out, W, &len, &top);
-            else if (W <= 256) slip_rescale_entry_reg<4>(a, la, b, lb, out, W, &len, &top);
-            else {
-                const int Wp = (W + 1) & ~1;
-                wb_mul_lo(out, a, la, b, lb, Wp);
-                len = wb_len(out, Wp);
-                top = len ? out[len - 1] : 0u;
-            }
-        }
+        slip_mul_entry(a, la, b, lb, out, &len, &top);
         if (lane == 0) {
             o.len = (slip_sgn(en.len) * slip_sgn(sl)) < 0 ? -len : len;
             o.bits = len ? 32 * len - slip_clz32(top) : 0;
@@ -291,6 +299,208 @@ static void slip_check_body(SlipCheckArgs A)
             slip_atomic_add_i32(&A.nbad[c], 1);
         }
     }
+}
+
+/* A scale applied to a solution before it is converted (slip_hip_factor_solve_double): out[t] = src[t] * s for one
+ * multiplier s, one wavefront per entry, through slip_mul_entry (the product path of slip_rescale_kernel).  The host laid the
+ * destination offsets out from the operands' lengths; the kernel writes the product's signed digit count. */
+struct SlipScaleArgs {
+    int64_t count;
+    const int32_t *len; const int64_t *off; const uint64_t *limbs;                 /* source: signed digit counts, limb offsets */
+    int32_t slen; const uint64_t *slimbs;                                          /* the multiplier: signed digit count        */
+    int32_t *olen; const int64_t *ooff; uint64_t *olimbs;                          /* destination                               */
+};
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_scale_kernel(SlipScaleArgs A)
+#else
+static void slip_scale_body(SlipScaleArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    for (int64_t e = wave0; e < A.count; e += nwaves) {
+        const int32_t sa = A.len[e];
+        int len = 0; uint32_t top = 0;
+        slip_mul_entry((const dig_t *)(A.limbs + A.off[e]), slip_abs(sa), (const dig_t *) A.slimbs, slip_abs(A.slen),
+                       (dig_t *)(A.olimbs + A.ooff[e]), &len, &top);
+        if (lane == 0) A.olen[e] = (sa < 0) != (A.slen < 0) ? -len : len;
+    }
+}
+
+/* Solution to doubles (slip_hip_factor_solve_double, slip_hip_solution_to_double): out = trunc(N / D) onto the double grid,
+ * toward zero, for every numerator N of a solution over its right-hand side's denominator D -- bit for bit what mpq_get_d
+ * returns (SLIP_get_double_soln -> SLIP_gmp.c:1063).  Magnitudes below; the sign is that of N * D, dropped when the result is 0.
+ *
+ * Lane pass, one lane per entry.  n64, d64: the leading 64 bits of N and D, left-aligned (bn, bd their bit lengths), so
+ *     N * 2^(64-bn) in [n64, n64 + 1),   D * 2^(64-bd) in [d64, d64 + 1),   2^63 <= n64, d64 < 2^64.
+ * k = 64 when n64 < d64, else 63; X = n64 * 2^k / d64 then lies in [2^63, 2^64) and Q = floor(X) is one 128-by-64 division.
+ * T = (N / D) * 2^(k - bn + bd) is the true quotient on that scale, and
+ *     T > n64 * 2^k / (d64 + 1) = X - X / (d64 + 1) > X - 2^64 / 2^63 = X - 2 >= Q - 2,
+ *     T < (n64 + 1) * 2^k / d64 = X + 2^k / d64 <= X + 2 < Q + 3,
+ * so floor(T) is one of Q-2 .. Q+2 (and equals Q when bn, bd <= 64: both leading parts are then the whole numbers).  The
+ * double keeps the top 53 bits: r = 11 bits of T are dropped, more when the grid 2^G of the result, G = r - k + bn - bd,
+ * would be finer than the subnormal spacing 2^-1074 (then r grows until G = -1074).  With m_lo = (Q-2) >> r and
+ * m_hi = (Q+2) >> r the answer is trunc = m * 2^G for m = floor(T) >> r in [m_lo, m_hi].  If m_lo * 2^G and m_hi * 2^G are the
+ * same double (slip_double_bits: also both +0.0, both inf) the lane stores it.  (T in [2^63, 2^64) is what makes 2^G the
+ * double's own grid; Q-2 < 2^63 or Q+2 >= 2^64 leave the exponent open too, and slip_double_bits names the two candidates
+ * of those cases: they are neighbouring doubles again.)
+ *
+ * Wave pass.  THE INVARIANT: r >= 11, so the five values Q-2 .. Q+2 cross at most one multiple of 2^r and m_hi - m_lo <= 1:
+ * when the lane pass does not decide, the answer is m_hi * 2^G if m_hi * 2^G <= N / D and m_lo * 2^G = (m_hi - 1) * 2^G
+ * otherwise -- two candidates, never more, and one exact comparison picks:  m_hi * 2^G * D <= N.  This is the case of every
+ * quotient that lies ON the grid (integer and dyadic solutions: T is a multiple of 2^r, Q-2 is below it), where leading
+ * bits alone would land one step low.  Undecided lanes are ballotted and the wave takes them one at a time: with
+ * G = 32 * Gd + gb, 0 <= gb < 32, the product P = (m_hi << gb) * D is a three-digit by ld-digit wb_mul_lo into this wave's
+ * scratch, and P * B^Gd <= N is a comparison of digit strings at an offset: no big shift is ever formed.
+ *   Gd >= 0:  P <= floor(N / B^Gd), the digits of N from Gd up (false when N has none there, since P >= 1);
+ *   Gd <  0:  P <= N * B^-Gd: true when P has at most -Gd digits (P * B^Gd < 1 <= N), else compare the digits of P from -Gd up
+ *             with N; if those are equal, P <= N * B^-Gd exactly when the low -Gd digits of P are all zero.
+ * The kernel never aborts: zero numerators give +0.0, a zero denominator (refused by the host) gives +0.0 as well. */
+struct SlipToDoubleArgs {
+    int32_t n, nrhs;
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* N: entry c*n + p, signed digit counts, limb offsets */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* D: one per right-hand side                         */
+    const int32_t *oidx;                                                           /* entry p goes to out[c*n + oidx[p]]; null: to p     */
+    int32_t flip;                                                                  /* negate every result (the sign of a scale)          */
+    double *out;
+    dig_t *scratch; int32_t wcap;                                                  /* wave pass: 4 + wcap digits per wave                */
+    unsigned long long *nslow;                                                     /* entries that took the wave pass                     */
+};
+
+/* the leading 64 bits of a normalised la-digit number (la >= 1, top digit nonzero), left-aligned */
+SLIP_DEV uint64_t slip_lead64(const dig_t *x, int la)
+{
+    const int z = slip_clz32(x[la - 1]);
+    const uint64_t v = ((uint64_t) x[la - 1] << 32) | (la >= 2 ? x[la - 2] : 0u);
+    return z ? (v << z) | ((uint64_t)(la >= 3 ? x[la - 3] : 0u) >> (32 - z)) : v;
+}
+
+/* floor((u1 * 2^64 + u0) / v) for u1 < v and v >= 2^63: Knuth's algorithm D in base 2^32, two quotient digits */
+SLIP_DEV uint64_t slip_div128by64(uint64_t u1, uint64_t u0, uint64_t v)
+{
+    const uint64_t b = 1ull << 32, v1 = v >> 32, v0 = v & 0xFFFFFFFFull, u01 = u0 >> 32, u00 = u0 & 0xFFFFFFFFull;
+    uint64_t q1 = u1 / v1, rh = u1 - q1 * v1;
+    while (q1 >= b || q1 * v0 > b * rh + u01) { q1--; rh += v1; if (rh >= b) break; }
+    const uint64_t u21 = u1 * b + u01 - q1 * v;
+    uint64_t q0 = u21 / v1;
+    rh = u21 - q0 * v1;
+    while (q0 >= b || q0 * v0 > b * rh + u00) { q0--; rh += v1; if (rh >= b) break; }
+    return q1 * b + q0;
+}
+
+/* the bits of the candidate double of mantissa m on the grid 2^G, 0 <= m <= 2^53, G >= -1074: m * 2^G, inf from 2^1024 on.
+ * On a normal grid (G > -1074, so r = 11) m >= 2^52 except for the lower candidate m_lo = 2^52 - 1 of Q < 2^63 + 2: there T may
+ * lie below 2^63, the double then has the next lower exponent and keeps one more bit of T, and T > 2^63 - 2 makes that
+ * floor(T / 2^10) = 2^53 - 1 on the grid 2^(G-1): the double just below the upper candidate 2^52 * 2^G. */
+SLIP_DEV uint64_t slip_double_bits(uint64_t m, int64_t G)
+{
+    if (m == 0) return 0;
+    if (m >> 53) { m >>= 1; G++; }                                   /* 2^53 = 2^52 * 2 */
+    if (m < (1ull << 52) && G > -1074) { m = 2 * m + 1; G--; }       /* m = 2^52 - 1 (see above): 2^53 - 1 on the finer grid */
+    if (G == -1074) return m;                                        /* subnormals, and exponent field 1 when m >= 2^52 */
+    if (G + 1075 >= 2047) return 0x7FF0000000000000ull;
+    return ((uint64_t)(G + 1075) << 52) | (m - (1ull << 52));
+}
+
+/* number of significant digits of x[0..la) seen by one lane (records from the solve are normalised; this keeps any input safe) */
+SLIP_DEV int slip_trim_digits(const dig_t *x, int la)
+{
+    while (la > 0 && x[la - 1] == 0) la--;
+    return la;
+}
+
+/* the wave pass for entry `it` (all arguments wave-uniform): is m * 2^G * |D| <= |N| ? */
+SLIP_DEV int slip_todouble_exact(const SlipToDoubleArgs &A, int64_t it, uint64_t m, int64_t G, dig_t *scr)
+{
+    const int lane = slip_lane();
+    const int c = (int)(it / A.n);
+    const dig_t *x = (const dig_t *)(A.xlimbs + A.xoff[it]), *d = (const dig_t *)(A.dlimbs + A.doff[c]);
+    const int la = slip_trim_digits(x, slip_abs(A.xlen[it])), ld = slip_trim_digits(d, slip_abs(A.dlen[c]));
+    const int gb = (int)(((G % 32) + 32) % 32);
+    const int64_t Gd = (G - gb) / 32;
+    const uint64_t mlo = m << gb, mtop = gb ? m >> (64 - gb) : 0;    /* m << gb: at most 54 + 31 bits, three digits */
+    dig_t *md = scr, *P = scr + 4;
+    if (lane < 4) md[lane] = lane == 0 ? (dig_t) mlo : (lane == 1 ? (dig_t)(mlo >> 32) : (lane == 2 ? (dig_t) mtop : 0u));
+    slip_wave_sync();
+    const int W = ld + 3 <= A.wcap ? ld + 3 : A.wcap;                /* ld + 3 <= wcap: the host sized it */
+    wb_mul_lo(P, md, 3, d, ld, W);
+    const int lp = wb_len(P, W);
+    int ok;
+    if (Gd >= 0) ok = Gd < la && wb_cmp(P, lp, x + Gd, la - (int) Gd) <= 0;
+    else if (lp <= -Gd) ok = 1;
+    else {
+        const int k = (int) -Gd, cm = wb_cmp(P + k, lp - k, x, la);
+        ok = cm < 0;
+        if (cm == 0) {
+            int low = 0;
+            for (int base = 0; base < k; base += SLIP_WAVE) low |= slip_ballot(base + lane < k && P[base + lane] != 0) != 0;
+            ok = !low;
+        }
+    }
+    slip_wave_sync();
+    return ok;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_todouble_kernel(SlipToDoubleArgs A)
+#else
+static void slip_todouble_body(SlipToDoubleArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    dig_t *scr = A.scratch + wave0 * (4 + (int64_t) A.wcap);
+    const int64_t items = (int64_t) A.n * A.nrhs;
+    unsigned long long slow_total = 0;
+    for (int64_t base = wave0 * SLIP_WAVE; base < items; base += nwaves * SLIP_WAVE) {
+        const int64_t it = base + lane;
+        uint64_t lo = 0, hi = 0, mhi = 0;
+        int64_t G = 0;
+        int neg = 0;
+        if (it < items) {
+            const int c = (int)(it / A.n);
+            const int32_t sx = A.xlen[it], sd = A.dlen[c];
+            const dig_t *x = (const dig_t *)(A.xlimbs + A.xoff[it]), *d = (const dig_t *)(A.dlimbs + A.doff[c]);
+            const int la = slip_trim_digits(x, slip_abs(sx)), ld = slip_trim_digits(d, slip_abs(sd));
+            neg = ((sx < 0) != (sd < 0)) != (A.flip != 0);
+            if (la > 0 && ld > 0) {
+                const int64_t bn = 32 * (int64_t) la - slip_clz32(x[la - 1]), bd = 32 * (int64_t) ld - slip_clz32(d[ld - 1]);
+                const uint64_t n64 = slip_lead64(x, la), d64 = slip_lead64(d, ld);
+                const int k = n64 < d64 ? 64 : 63;
+                const uint64_t Q = k == 64 ? slip_div128by64(n64, 0, d64) : slip_div128by64(n64 >> 1, n64 << 63, d64);
+                int64_t r = 11;
+                G = r - k + bn - bd;
+                if (G < -1074) { r += -1074 - G; G = -1074; }
+                if (r < 66) {                                        /* else T < 2^64 + 3 < 2^r: +0.0 */
+                    const int whole = bn <= 64 && bd <= 64;          /* T = X exactly */
+                    const uint64_t qlo = whole ? Q : Q - 2, qhi = whole ? Q : Q + 2, carry = qhi < Q;      /* Q + 2 may reach 2^64 */
+                    mhi = r < 64 ? (qhi >> r) | (carry << (64 - r)) : (r == 64 ? carry : 0);
+                    lo = slip_double_bits(r < 64 ? qlo >> r : 0, G);
+                    hi = slip_double_bits(mhi, G);
+                }
+            }
+        }
+        uint64_t pend = slip_ballot(lo != hi);
+        slow_total += (unsigned long long) slip_popc64(pend);
+        while (pend) {
+            const int src = slip_ctz64(pend);
+            pend &= pend - 1;
+            const uint64_t m_src = slip_shfl_u64(mhi, src);
+            const int64_t G_src = (int64_t) slip_shfl_u64((uint64_t) G, src);
+            const int ok = slip_todouble_exact(A, base + src, m_src, G_src, scr);
+            if (lane == src) lo = ok ? hi : lo;
+        }
+        if (it < items) {
+            const int c = (int)(it / A.n), p = (int)(it - (int64_t) c * A.n);
+            union { uint64_t u; double f; } v;
+            v.u = lo | (lo != 0 && neg ? 0x8000000000000000ull : 0ull);
+            A.out[(int64_t) c * A.n + (A.oidx ? A.oidx[p] : p)] = v.f;
+        }
+    }
+    if (lane == 0 && slow_total) slip_atomic_add_u64(A.nslow, slow_total);
 }
 
 /* The transposed view of complete factors (slip_hip_factor_solve_transpose).  With M = A(row_perm, q) the matrix that was
@@ -523,6 +733,8 @@ struct slip_hip_factor {
     /* slip_hip_factor_check_transpose: the column view of A in q order (row k of the check = column q[k]), built on the first
      * transposed check */
     int64_t *chkt_rp, *chkt_re; int32_t *chkt_rx;
+    /* slip_hip_factor_solve_double: device time of the last conversion kernel, entries of it that took the wave pass */
+    double todouble_ms; int64_t todouble_slow;
 };
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -1632,17 +1844,21 @@ static SlipParams tview_params(const slip_hip_factor *f)
     return P;
 }
 
-/* slip_hip_factor_solve (transpose 0) and slip_hip_factor_solve_transpose (1): the launches, the grow-and-relaunch loop and
- * the gather are one; the transposed solve runs on the view and gathers its output by row id, x[i] = y[pinv[i]] */
-static int solve_core(slip_hip_factor *f, int transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
-                      int32_t **xlen_out, uint64_t **xlimbs_out, int64_t *xnl_out, void *stream_v)
+/* the substitution's output while it is still on the device: per entry (rhs c, position p) at c*n + p a signed digit count
+ * and a limb offset into olimbs, where every right-hand side owns `ostride` limbs */
+struct SlipSolveOut { int32_t *olen; int64_t *ooff; uint64_t *olimbs; int64_t ostride; };
+static void solve_out_free(SlipSolveOut *o) { dev_free(o->olen); dev_free(o->ooff); dev_free(o->olimbs); memset(o, 0, sizeof *o); }
+
+/* slip_hip_factor_solve (transpose 0), slip_hip_factor_solve_transpose (1) and slip_hip_factor_solve_double (either): the
+ * launches and the grow-and-relaunch loop are one; the transposed solve runs on the view.  The output stays on the device. */
+static int solve_device(slip_hip_factor *f, int transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                        hipStream_t stream, SlipSolveOut *out)
 {
-    if (!f || nrhs <= 0 || !blen || !blimbs || !xlen_out || !xlimbs_out || !xnl_out) return SLIP_HIP_INCORRECT_INPUT;
-    *xlen_out = NULL; *xlimbs_out = NULL; *xnl_out = 0;
+    memset(out, 0, sizeof *out);
+    if (!f || nrhs <= 0 || !blen || !blimbs) return SLIP_HIP_INCORRECT_INPUT;
     const int32_t n = f->n;
     if (f->hs.F != n) return SLIP_HIP_INCORRECT_INPUT;          /* needs the complete factorisation */
     if (!f->P.xd || !f->P.xrow) return SLIP_HIP_OUT_OF_MEMORY;
-    hipStream_t stream = (hipStream_t) stream_v;
     SlipParams *P = &f->P;
     double *ms = transpose ? &f->tsolve_ms : &f->solve_ms;
     if (transpose) {
@@ -1657,7 +1873,7 @@ static int solve_core(slip_hip_factor *f, int transpose, int32_t nrhs, const int
     const int32_t maxdig = bs.maxdig > 1 ? bs.maxdig : 1;
     SlipSolveArgs A; memset(&A, 0, sizeof A);
     int32_t *dblen = NULL, *dolen = NULL, *ddone = NULL; int64_t *dboff = NULL, *dooff = NULL; uint64_t *dbl = NULL, *dol = NULL;
-    int32_t *xl = NULL, *hdone = NULL; uint64_t *xlimbs = NULL, *raw = NULL; int64_t *hooff = NULL;
+    int32_t *hdone = NULL;
     int rc = 0;
     /* x grows to about |b| * det: make room once (the kernel still reports GROW_X if this is short) */
     {
@@ -1702,13 +1918,33 @@ static int solve_core(slip_hip_factor *f, int transpose, int32_t nrhs, const int
             }
         }
     }
-    if (!rc) {
+    slab_free(&bs); free(hdone);
+    dev_free(dblen); dev_free(dboff); dev_free(dbl); dev_free(ddone);
+    if (rc) { dev_free(dolen); dev_free(dooff); dev_free(dol); return rc; }
+    out->olen = dolen; out->ooff = dooff; out->olimbs = dol; out->ostride = ostride;
+    return SLIP_HIP_OK;
+}
+
+/* the numerators as the ABI returns them: the per-right-hand-side regions gathered into one dense slab; the transposed solve
+ * gathers its output by row id, x[i] = y[pinv[i]] */
+static int solve_core(slip_hip_factor *f, int transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                      int32_t **xlen_out, uint64_t **xlimbs_out, int64_t *xnl_out, void *stream_v)
+{
+    if (!f || nrhs <= 0 || !blen || !blimbs || !xlen_out || !xlimbs_out || !xnl_out) return SLIP_HIP_INCORRECT_INPUT;
+    *xlen_out = NULL; *xlimbs_out = NULL; *xnl_out = 0;
+    SlipSolveOut o;
+    TRY_(solve_device(f, transpose, nrhs, blen, blimbs, (hipStream_t) stream_v, &o));
+    const int32_t n = f->n;
+    const int64_t ne = (int64_t) n * nrhs, ostride = o.ostride;
+    int32_t *xl = NULL; uint64_t *xlimbs = NULL, *raw = NULL; int64_t *hooff = NULL;
+    int rc = 0;
+    {
         /* gather the per-right-hand-side regions into the dense (rhs, position) slab of the ABI */
         xl = (int32_t *) malloc((size_t) ne * 4);
         hooff = (int64_t *) malloc((size_t) ne * 8);
         raw = (uint64_t *) malloc((size_t)(ostride * nrhs) * 8);
         if (!xl || !hooff || !raw) rc = SLIP_HIP_OUT_OF_MEMORY;
-        DOWN_(xl, dolen, (size_t) ne * 4); DOWN_(hooff, dooff, (size_t) ne * 8); DOWN_(raw, dol, (size_t)(ostride * nrhs) * 8);
+        DOWN_(xl, o.olen, (size_t) ne * 4); DOWN_(hooff, o.ooff, (size_t) ne * 8); DOWN_(raw, o.olimbs, (size_t)(ostride * nrhs) * 8);
         if (!rc) {
             int64_t nl = 0;
             for (int64_t t = 0; t < ne; t++) { const int32_t d = xl[t]; nl += ((d < 0 ? -d : d) + 1) >> 1; }
@@ -1731,8 +1967,8 @@ static int solve_core(slip_hip_factor *f, int transpose, int32_t nrhs, const int
             if (transpose) free(ol);
         }
     }
-    free(xl); free(xlimbs); slab_free(&bs); free(hdone); free(raw); free(hooff);
-    dev_free(dblen); dev_free(dboff); dev_free(dbl); dev_free(dolen); dev_free(dooff); dev_free(dol); dev_free(ddone);
+    free(xl); free(xlimbs); free(raw); free(hooff);
+    solve_out_free(&o);
     return rc;
 }
 
@@ -1754,6 +1990,178 @@ extern "C" double slip_hip_factor_solve_transpose_ms(const slip_hip_factor *f, d
 {
     if (view_ms) *view_ms = f ? f->tview_ms : 0.0;
     return f ? f->tsolve_ms : 0.0;
+}
+
+/* ---- solutions as doubles (SLIP_solve_double's tail: SLIP_permute_x, SLIP_scale_x, SLIP_get_double_soln; kernels:
+ * slip_todouble_kernel, slip_scale_kernel) ---- */
+
+/* one conversion on the device: numerators (entry c*n + p) and one denominator per right-hand side, all device arrays of signed
+ * digit counts, limb offsets and limbs; dmaxdig: digits of the widest denominator; doidx: where entry p of a right-hand side
+ * goes (device, n entries; NULL: to p).  out (host) receives n * nrhs doubles and nothing else comes back. */
+static int to_double_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int64_t *dxoff, const uint64_t *dxlimbs,
+                          const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
+                          const int32_t *doidx, int flip, double *out, hipStream_t stream, double *ms_out, int64_t *slow_out)
+{
+    const int64_t ne = (int64_t) n * nrhs, wcap = (int64_t) dmaxdig + 4;      /* the wave pass forms a product of dmaxdig + 3 digits */
+    if (wcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
+#ifndef SLIP_EMULATE
+    const int64_t waves_per_block = 4;
+    int64_t blocks = (ne + 64 * waves_per_block - 1) / (64 * waves_per_block);
+    if (blocks > 4096) blocks = 4096;
+    const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * (4 + wcap) * 4);      /* at most 256 MiB of scratch */
+    if (blocks > fit) blocks = fit;
+    if (blocks < 1) blocks = 1;
+#else
+    const int64_t blocks = 2, waves_per_block = 2;
+#endif
+    double *dout = NULL; dig_t *dscr = NULL; unsigned long long *dslow = NULL, hslow = 0;
+    hipEvent_t ev0 = NULL, ev1 = NULL;
+    int rc = 0;
+    A_(dev_alloc(&dout, ne)); A_(dev_alloc(&dscr, blocks * waves_per_block * (4 + wcap))); A_(dev_alloc(&dslow, 1));
+    HIP_(hipMemsetAsync(dslow, 0, 8, stream));
+    HIP_(hipEventCreate(&ev0)); HIP_(hipEventCreate(&ev1));
+    if (!rc) {
+        SlipToDoubleArgs A; memset(&A, 0, sizeof A);
+        A.n = n; A.nrhs = nrhs; A.xlen = dxlen; A.xoff = dxoff; A.xlimbs = dxlimbs; A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
+        A.oidx = doidx; A.flip = flip; A.out = dout; A.scratch = dscr; A.wcap = (int32_t) wcap; A.nslow = dslow;
+        HIP_(hipEventRecord(ev0, stream));
+#ifndef SLIP_EMULATE
+        if (!rc) {
+            hipLaunchKernelGGL(slip_todouble_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
+            HIP_(hipGetLastError());
+        }
+#else
+        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_todouble_body(A); }, 256 * 1024, 1);
+#endif
+        HIP_(hipEventRecord(ev1, stream)); HIP_(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIP_(hipEventElapsedTime(&ms, ev0, ev1));
+        if (ms_out) *ms_out = ms;
+    }
+    DOWN_(out, dout, (size_t) ne * 8); DOWN_(&hslow, dslow, 8);
+    if (!rc && slow_out) *slow_out = (int64_t) hslow;
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    dev_free(dout); dev_free(dscr); dev_free(dslow);
+    return rc;
+}
+
+/* one launch of slip_scale_kernel: count entries times the multiplier (device, signed digit count slen) */
+static int scale_launch(int64_t count, const int32_t *dlen, const int64_t *doff, const uint64_t *dlimbs, int32_t slen, const uint64_t *dsl,
+                        int32_t *dolen, const int64_t *dooff, uint64_t *dolimbs, hipStream_t stream)
+{
+    SlipScaleArgs A; memset(&A, 0, sizeof A);
+    A.count = count; A.len = dlen; A.off = doff; A.limbs = dlimbs; A.slen = slen; A.slimbs = dsl; A.olen = dolen; A.ooff = dooff; A.olimbs = dolimbs;
+#ifndef SLIP_EMULATE
+    int64_t blocks = (count + 3) / 4; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(slip_scale_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, A);
+    CK(hipGetLastError());
+#else
+    emu::launch(2, 128, [A]() { slip_scale_body(A); }, 256 * 1024, 1);
+#endif
+    CK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+/* one part of a scale: NULL limbs mean 1; *dig = its signed digit count (0: the part is zero, which the callers refuse) */
+static void scale_part(int32_t len, const uint64_t *limbs, int32_t *dig)
+{
+    if (!limbs) { *dig = 1; return; }
+    const int32_t d = limb_digits(limbs, len < 0 ? -(int64_t) len : len);
+    *dig = len < 0 ? -d : d;
+}
+static int scale_is_unit(int32_t dig, const uint64_t *limbs) { return !limbs || ((dig == 1 || dig == -1) && limbs[0] == 1); }
+
+extern "C" int slip_hip_factor_solve_double(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                            int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
+                                            double *x_out, void *stream_v)
+{
+    if (!f || nrhs < 1 || !blen || !blimbs || !x_out) return SLIP_HIP_INCORRECT_INPUT;
+    int32_t sndig, sddig;
+    scale_part(snlen, snlimbs, &sndig); scale_part(sdlen, sdlimbs, &sddig);
+    if (sndig == 0 || sddig == 0) return SLIP_HIP_INCORRECT_INPUT;                  /* a zero scale part */
+    if (!transpose && f->factors_only) return SLIP_HIP_INCORRECT_INPUT;             /* no q behind such a handle */
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipSolveOut o;
+    TRY_(solve_device(f, transpose, nrhs, blen, blimbs, stream, &o));
+    const int32_t n = f->n;
+    const int64_t ne = (int64_t) n * nrhs;
+    SlipParams *P = &f->P;
+    const int flip = (sndig < 0) != (sddig < 0);
+    const int32_t snabs = sndig < 0 ? -sndig : sndig, sdabs = sddig < 0 ? -sddig : sddig;
+    int32_t *ddlen = NULL, *doidx = NULL, *dplen = NULL, *dxlen2 = NULL; int64_t *ddoff = NULL, *dxoff2 = NULL; uint64_t *dsl = NULL, *dprod = NULL, *dxl2 = NULL;
+    int32_t *hl = (int32_t *) malloc((size_t)(ne > nrhs ? ne : nrhs) * 4); int64_t *ho = (int64_t *) malloc((size_t)(ne > nrhs ? ne : nrhs) * 8);
+    int rc = !hl || !ho ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    /* D = det = rho[n-1], read in place from the L slab through its pivot record (32 bytes; no limb of it is downloaded) */
+    SlipPiv pr; memset(&pr, 0, sizeof pr);
+    DOWN_(&pr, P->piv.p_ + (n - 1), sizeof pr);
+    int32_t ddig = pr.len < 0 ? -pr.len : pr.len;
+    if (!rc && (pr.len == 0 || pr.off < 0 || pr.off + ((ddig + 1) >> 1) > P->Lcap_nl)) rc = SLIP_HIP_DEVICE_ERROR;
+    const uint64_t *dden = P->Llimbs; int64_t denoff = pr.off; int32_t denlen = pr.len;
+    A_(dev_alloc(&ddlen, nrhs)); A_(dev_alloc(&ddoff, nrhs));
+    /* det * |sden|, once per call, on one wave */
+    if (!rc && !scale_is_unit(sddig, sdlimbs)) {
+        const int64_t zero = 0;
+        A_(dev_alloc(&dsl, (sdabs + 1) >> 1)); A_(dev_alloc(&dprod, (ddig + sdabs + 1) / 2 + 1)); A_(dev_alloc(&dplen, 1));
+        UP_(dsl, sdlimbs, (size_t)((sdabs + 1) >> 1) * 8);
+        UP_(ddlen, &pr.len, 4); UP_(ddoff, &pr.off, 8);                             /* the source record; rewritten below */
+        int64_t *dzero = NULL;
+        A_(dev_alloc(&dzero, 1)); UP_(dzero, &zero, 8);
+        A_(scale_launch(1, ddlen, ddoff, P->Llimbs, sdabs, dsl, dplen, dzero, dprod, stream));
+        DOWN_(&denlen, dplen, 4);
+        dev_free(dzero); dev_free(dsl); dsl = NULL;
+        dden = dprod; denoff = 0; ddig = denlen < 0 ? -denlen : denlen;
+    }
+    if (!rc) for (int32_t c = 0; c < nrhs; c++) { hl[c] = denlen; ho[c] = denoff; }
+    UP_(ddlen, hl, (size_t) nrhs * 4); UP_(ddoff, ho, (size_t) nrhs * 8);
+    /* xnum * |snum| per entry, only when |snum| != 1: the counts come down (4 bytes an entry) to lay the products out */
+    const int32_t *nlen = o.olen; const int64_t *noff = o.ooff; const uint64_t *nlimbs = o.olimbs;
+    if (!rc && !scale_is_unit(sndig, snlimbs)) {
+        DOWN_(hl, o.olen, (size_t) ne * 4);
+        int64_t total = 0;
+        if (!rc) for (int64_t t = 0; t < ne; t++) { ho[t] = total; total += ((hl[t] < 0 ? -hl[t] : hl[t]) + snabs + 1) / 2 + 1; }
+        A_(dev_alloc(&dsl, (snabs + 1) >> 1)); A_(dev_alloc(&dxlen2, ne)); A_(dev_alloc(&dxoff2, ne)); A_(dev_alloc(&dxl2, total));
+        UP_(dsl, snlimbs, (size_t)((snabs + 1) >> 1) * 8); UP_(dxoff2, ho, (size_t) ne * 8);
+        A_(scale_launch(ne, o.olen, o.ooff, o.olimbs, snabs, dsl, dxlen2, dxoff2, dxl2, stream));
+        nlen = dxlen2; noff = dxoff2; nlimbs = dxl2;
+    }
+    /* where position p goes: column q[p] (SLIP_permute_x); the transposed solve's position p is row i with pinv[i] = p */
+    if (!rc && transpose) {
+        for (int32_t i = 0; i < n; i++) hl[f->tpinv[i]] = i;
+        A_(dev_alloc(&doidx, n)); UP_(doidx, hl, (size_t) n * 4);
+    }
+    f->todouble_ms = 0; f->todouble_slow = 0;
+    A_(to_double_core(n, nrhs, nlen, noff, nlimbs, ddlen, ddoff, dden, ddig, transpose ? doidx : f->dq, flip, x_out, stream,
+                      &f->todouble_ms, &f->todouble_slow));
+    free(hl); free(ho);
+    dev_free(ddlen); dev_free(ddoff); dev_free(doidx); dev_free(dplen); dev_free(dxlen2); dev_free(dxoff2); dev_free(dsl); dev_free(dprod); dev_free(dxl2);
+    solve_out_free(&o);
+    return rc;
+}
+
+extern "C" double slip_hip_factor_to_double_ms(const slip_hip_factor *f) { return f ? f->todouble_ms : 0.0; }
+extern "C" int64_t slip_hip_factor_to_double_slow(const slip_hip_factor *f) { return f ? f->todouble_slow : 0; }
+
+extern "C" int slip_hip_solution_to_double(int32_t n, int32_t nrhs, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                           const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs, double *out, void *stream_v)
+{
+    if (n <= 0 || nrhs < 1 || !xlen || !xlimbs || !dlen || !dlimbs || !out) return SLIP_HIP_INCORRECT_INPUT;
+    TRY_(need_device());
+    const int64_t ne = (int64_t) n * nrhs;
+    SlipSlab xs, ds;
+    memset(&ds, 0, sizeof ds);
+    int rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
+    if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
+    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no number */
+    int32_t *dxl = NULL, *ddl = NULL; int64_t *dxo = NULL, *ddo = NULL; uint64_t *dxv = NULL, *ddv = NULL;
+    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total));
+    A_(dev_alloc(&ddl, nrhs)); A_(dev_alloc(&ddo, nrhs)); A_(dev_alloc(&ddv, ds.total));
+    UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
+    UP_(ddl, ds.dig, (size_t) nrhs * 4); UP_(ddo, ds.off, (size_t) nrhs * 8); UP_(ddv, dlimbs, (size_t) ds.total * 8);
+    A_(to_double_core(n, nrhs, dxl, dxo, dxv, ddl, ddo, ddv, ds.maxdig, NULL, 0, out, (hipStream_t) stream_v, NULL, NULL));
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
+    slab_free(&xs); slab_free(&ds);
+    return rc;
 }
 
 /* ---- exact solution check (SLIP_check_solution.c:31-113 as one integer test; kernel: slip_check_kernel) ---- */

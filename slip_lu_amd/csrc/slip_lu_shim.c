@@ -64,6 +64,50 @@ static SLIP_info build_factor(SLIP_sparse *M, int32_t n, int64_t nz, const int64
     return SLIP_OK;
 }
 
+/* the caller's mpz_t CSC as the arrays slip_hip_factor_create takes (malloc'ed; 0 or SLIP_OUT_OF_MEMORY with all three NULL) */
+static int matrix_to_slab(const SLIP_sparse *A, int32_t n, int64_t **Ap_out, int32_t **Alen_out, uint64_t **Alimbs_out)
+{
+    const int64_t annz = A->p[n];
+    int64_t nl = 0;
+    for (int64_t t = 0; t < annz; t++) nl += (int64_t) mpz_size(A->x[t]);
+    int64_t *Ap = (int64_t *) malloc(((size_t) n + 1) * 8);
+    int32_t *Alen = (int32_t *) malloc((size_t) annz * 4);
+    uint64_t *Alimbs = (uint64_t *) malloc((size_t)(nl ? nl : 1) * 8);
+    *Ap_out = NULL; *Alen_out = NULL; *Alimbs_out = NULL;
+    if (!Ap || !Alen || !Alimbs) { free(Ap); free(Alen); free(Alimbs); return SLIP_OUT_OF_MEMORY; }
+    for (int32_t j = 0; j <= n; j++) Ap[j] = A->p[j];
+    int64_t o = 0;
+    for (int64_t t = 0; t < annz; t++) {
+        size_t l = mpz_size(A->x[t]);
+        if (l) memcpy(Alimbs + o, mpz_limbs_read(A->x[t]), l * 8);
+        Alen[t] = mpz_sgn(A->x[t]) < 0 ? -(int32_t) l : (int32_t) l;
+        o += (int64_t) l;
+    }
+    *Ap_out = Ap; *Alen_out = Alen; *Alimbs_out = Alimbs;
+    return 0;
+}
+
+/* b: dense, right-hand side k, row i at k*n+i (b->x[i][k], SLIP_LU_solve.c:68-75), as a limb slab (malloc'ed) */
+static int dense_to_slab(const SLIP_dense *b, int32_t n, int32_t nrhs, int32_t **blen_out, uint64_t **blimbs_out)
+{
+    int64_t nl = 0;
+    for (int32_t i = 0; i < n; i++) for (int32_t k = 0; k < nrhs; k++) nl += (int64_t) mpz_size(b->x[i][k]);
+    int32_t *blen = (int32_t *) malloc((size_t) n * nrhs * 4);
+    uint64_t *blimbs = (uint64_t *) malloc((size_t)(nl ? nl : 1) * 8);
+    *blen_out = NULL; *blimbs_out = NULL;
+    if (!blen || !blimbs) { free(blen); free(blimbs); return SLIP_OUT_OF_MEMORY; }
+    int64_t o = 0;
+    for (int32_t k = 0; k < nrhs; k++)
+        for (int32_t i = 0; i < n; i++) {
+            size_t l = mpz_size(b->x[i][k]);
+            if (l) memcpy(blimbs + o, mpz_limbs_read(b->x[i][k]), l * 8);
+            blen[(int64_t) k * n + i] = mpz_sgn(b->x[i][k]) < 0 ? -(int32_t) l : (int32_t) l;
+            o += (int64_t) l;
+        }
+    *blen_out = blen; *blimbs_out = blimbs;
+    return 0;
+}
+
 SLIP_info SLIP_hip_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, SLIP_LU_analysis *S,
                                 mpz_t *rhos, int32_t *pinv, SLIP_options *option)
 {
@@ -71,7 +115,6 @@ SLIP_info SLIP_hip_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, 
         return SLIP_INCORRECT_INPUT;
     const int32_t n = A->n;
     if (n <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
-    const int64_t annz = A->p[n];
     SLIP_info ret = SLIP_OUT_OF_MEMORY;
     slip_hip_factor *f = NULL;
     int64_t *Ap = NULL, *Lp = NULL, *Up = NULL;
@@ -85,22 +128,7 @@ SLIP_info SLIP_hip_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, 
     struct timespec t0_, t1_, t2_, t3_, t4_;
     clock_gettime(CLOCK_MONOTONIC, &t0_);
     /* ---- A: mpz_t -> limb slab ---- */
-    int64_t nl = 0;
-    for (int64_t t = 0; t < annz; t++) nl += (int64_t) mpz_size(A->x[t]);
-    Ap = (int64_t *) malloc(((size_t) n + 1) * 8);
-    Alen = (int32_t *) malloc((size_t) annz * 4);
-    Alimbs = (uint64_t *) malloc((size_t)(nl ? nl : 1) * 8);
-    if (!Ap || !Alen || !Alimbs) goto done;
-    for (int32_t j = 0; j <= n; j++) Ap[j] = A->p[j];
-    {
-        int64_t o = 0;
-        for (int64_t t = 0; t < annz; t++) {
-            size_t l = mpz_size(A->x[t]);
-            if (l) memcpy(Alimbs + o, mpz_limbs_read(A->x[t]), l * 8);
-            Alen[t] = mpz_sgn(A->x[t]) < 0 ? -(int32_t) l : (int32_t) l;
-            o += (int64_t) l;
-        }
-    }
+    if (matrix_to_slab(A, n, &Ap, &Alen, &Alimbs)) goto done;
 
     clock_gettime(CLOCK_MONOTONIC, &t1_);
     /* ---- factorise on the GPU ---- */
@@ -216,22 +244,7 @@ SLIP_info SLIP_hip_LU_solve(mpq_t **x, SLIP_dense *b, const mpz_t *rhos, const S
     rc = sparse_to_slab(L, n, rowperm, &Lp, &Li, &Llen, &Llimbs);
     if (!rc) rc = sparse_to_slab(U, n, rowperm, &Up, &Ui, &Ulen, &Ulimbs);
     if (rc) { if (rc == 2) ret = SLIP_INCORRECT_INPUT; goto done; }
-    /* b: dense, right-hand side k, row i at k*n+i (b->x[i][k], SLIP_LU_solve.c:68-75) */
-    {
-        int64_t nl = 0;
-        for (int32_t i = 0; i < n; i++) for (int32_t k = 0; k < nrhs; k++) nl += (int64_t) mpz_size(b->x[i][k]);
-        blen = (int32_t *) malloc((size_t) n * nrhs * 4);
-        blimbs = (uint64_t *) malloc((size_t)(nl ? nl : 1) * 8);
-        if (!blen || !blimbs) goto done;
-        int64_t o = 0;
-        for (int32_t k = 0; k < nrhs; k++)
-            for (int32_t i = 0; i < n; i++) {
-                size_t l = mpz_size(b->x[i][k]);
-                if (l) memcpy(blimbs + o, mpz_limbs_read(b->x[i][k]), l * 8);
-                blen[(int64_t) k * n + i] = mpz_sgn(b->x[i][k]) < 0 ? -(int32_t) l : (int32_t) l;
-                o += (int64_t) l;
-            }
-    }
+    if (dense_to_slab(b, n, nrhs, &blen, &blimbs)) goto done;
     rc = slip_hip_factor_from_factors(&f, n, Lp, Li, Llen, Llimbs, Up, Ui, Ulen, Ulimbs, pinv, NULL);
     if (rc == SLIP_HIP_OK) rc = slip_hip_factor_solve(f, nrhs, blen, blimbs, &xlen, &xlimbs, &xnl, NULL);
     if (rc != SLIP_HIP_OK) { ret = rc == SLIP_HIP_INCORRECT_INPUT ? SLIP_INCORRECT_INPUT : SLIP_OUT_OF_MEMORY; goto done; }
@@ -257,6 +270,73 @@ done:
     slip_hip_free(xlen); slip_hip_free(xlimbs);
     free(rowperm); free(blen); free(blimbs); free(Lp); free(Li); free(Llen); free(Llimbs); free(Up); free(Ui); free(Ulen); free(Ulimbs);
     return ret;
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * SLIP_solve_double (SLIP_LU/Include/SLIP_LU.h, SLIP_LU/Source/SLIP_solve_double.c:41-104) on the GPU:
+ * factorise, substitute, permute (SLIP_permute_x), scale (SLIP_scale_x.c:28-54: times A->scale, over
+ * b->scale, each only when it is neither 1 nor 0) and convert (SLIP_get_double_soln: mpq_get_d per
+ * entry) without leaving the device: slip_hip_factor_solve_double returns the n * numRHS doubles and
+ * nothing else -- no L, U, rho or numerator is downloaded, no mpz_t is built.  x_doub[i][j] (allocated
+ * by the caller, as for the reference) = entry i of the solution of right-hand side j.
+ * ------------------------------------------------------------------------------------------------ */
+/* *len, *limbs (malloc'ed) = the limb slab of z */
+static int mpz_to_limbs(const mpz_t z, int32_t *len, uint64_t **limbs)
+{
+    const size_t l = mpz_size(z);
+    *limbs = (uint64_t *) malloc((l ? l : 1) * 8);
+    if (!*limbs) return SLIP_OUT_OF_MEMORY;
+    (*limbs)[0] = 0;
+    if (l) memcpy(*limbs, mpz_limbs_read(z), l * 8);
+    *len = mpz_sgn(z) < 0 ? -(int32_t) l : (int32_t) l;
+    return 0;
+}
+
+SLIP_info SLIP_hip_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
+{
+    if (!x_doub || !A || !A->p || !A->i || !A->x || !S || !S->q || !b || !b->x || !option)
+        return SLIP_INCORRECT_INPUT;                      /* SLIP_solve_double.c:53-57 */
+    const int32_t n = A->n, nrhs = b->n;
+    if (n <= 0 || nrhs <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
+    SLIP_info ret = SLIP_OUT_OF_MEMORY;
+    slip_hip_factor *f = NULL;
+    int64_t *Ap = NULL; int32_t *Alen = NULL, *blen = NULL, snlen = 0, sdlen = 0;
+    uint64_t *Alimbs = NULL, *blimbs = NULL, *snl = NULL, *sdl = NULL;
+    double *xd = (double *) malloc((size_t) n * nrhs * sizeof(double));
+    slip_hip_options opt;
+    mpz_t sn, sd;
+    int rc;
+    /* scale = A->scale / b->scale, a part that is 1 or 0 left out (SLIP_scale_x.c:29-31, :43-45) */
+    mpz_init_set_ui(sn, 1); mpz_init_set_ui(sd, 1);
+    if (mpq_sgn(A->scale) != 0 && mpq_cmp_ui(A->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_numref(A->scale)); mpz_mul(sd, sd, mpq_denref(A->scale)); }
+    if (mpq_sgn(b->scale) != 0 && mpq_cmp_ui(b->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_denref(b->scale)); mpz_mul(sd, sd, mpq_numref(b->scale)); }
+    if (!xd || mpz_to_limbs(sn, &snlen, &snl) || mpz_to_limbs(sd, &sdlen, &sdl)) goto done;
+    if (matrix_to_slab(A, n, &Ap, &Alen, &Alimbs) || dense_to_slab(b, n, nrhs, &blen, &blimbs)) goto done;
+    slip_hip_default_options(&opt);
+    opt.pivot = (int32_t) option->pivot;
+    opt.tol = option->tol;
+    opt.lnz_hint = S->lnz; opt.unz_hint = S->unz;
+    rc = slip_hip_factor_create(&f, n, Ap, A->i, Alen, Alimbs, S->q, &opt);
+    if (rc == SLIP_HIP_OK) rc = slip_hip_factor_run(f, 0, NULL);
+    if (rc == SLIP_HIP_OK) rc = slip_hip_factor_solve_double(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl, xd, NULL);
+    if (rc != SLIP_HIP_OK) {
+        ret = rc == SLIP_HIP_SINGULAR ? SLIP_SINGULAR
+            : rc == SLIP_HIP_INCORRECT_INPUT ? SLIP_INCORRECT_INPUT : SLIP_OUT_OF_MEMORY;
+        goto done;
+    }
+    for (int32_t i = 0; i < n; i++)
+        for (int32_t j = 0; j < nrhs; j++) x_doub[i][j] = xd[(int64_t) j * n + i];
+    ret = SLIP_OK;
+done:
+    if (f) slip_hip_factor_destroy(f);
+    mpz_clear(sn); mpz_clear(sd);
+    free(xd); free(Ap); free(Alen); free(Alimbs); free(blen); free(blimbs); free(snl); free(sdl);
+    return ret;
+}
+
+SLIP_info SLIP_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
+{
+    return SLIP_hip_solve_double(x_doub, A, S, b, option);
 }
 
 SLIP_info SLIP_LU_solve(mpq_t **x, SLIP_dense *b, const mpz_t *rhos, const SLIP_sparse *L,
