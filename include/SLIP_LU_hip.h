@@ -17,7 +17,8 @@
  * that load both libraries and want to call either explicitly (the tests do).
  *
  * SLIP_LU_solve (SLIP_LU.h:941-949) is served the same way (SLIP_hip_LU_solve below), and so is SLIP_solve_double of the
- * simple interface (SLIP_hip_solve_double below), which never leaves the device between the factorisation and the doubles.
+ * simple interface (SLIP_hip_solve_double below), which never leaves the device between the factorisation and the doubles,
+ * and SLIP_solve_mpq (SLIP_hip_solve_mpq below), which brings back nothing but the reduced fractions.
  *
  * When the reference's SLIP_LU.h has been included first, this header only adds
  * the aliases; otherwise it declares layout-compatible mirrors of the four types
@@ -74,6 +75,8 @@ SLIP_info SLIP_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, SLIP
                             mpz_t *rhos, int32_t *pinv, SLIP_options *option);
 
 SLIP_info SLIP_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
+
+SLIP_info SLIP_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
 #endif
 
 SLIP_info SLIP_hip_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, SLIP_LU_analysis *S,
@@ -93,6 +96,15 @@ SLIP_info SLIP_hip_LU_solve(mpq_t **x, SLIP_dense *b, const mpz_t *rhos, const S
  * exact rational truncated toward zero as mpq_get_d returns it.  Only those doubles cross back: no L, U, rhos or numerator
  * is downloaded.  Also exported under the reference's own name. */
 SLIP_info SLIP_hip_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
+
+/* SLIP_solve_mpq (SLIP_LU/Source/SLIP_solve_mpq.c:41-97) on the GPU, with its prototype, argument checks (:51-55) and error
+ * codes: factorisation, substitution, the division by det (slip_array_div.c:36-49), SLIP_permute_x and SLIP_scale_x (as above)
+ * all run on the device (slip_hip_factor_solve_rational).  x_mpq[i][j] (n rows of b->n mpq_t, initialised, as
+ * SLIP_create_mpq_mat leaves them) receives entry i of the solution of right-hand side j in GMP's canonical form: lowest
+ * terms, a positive denominator, 0 as 0/1 -- what the reference's mpq_* calls leave.  Only the reduced numerators and
+ * denominators cross back and are copied into the mpq_t limb by limb; no GMP arithmetic runs per entry.  Also exported under
+ * the reference's own name. */
+SLIP_info SLIP_hip_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
 
 #ifdef __cplusplus
 }

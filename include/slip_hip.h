@@ -19,6 +19,8 @@
  *   slip_hip_check_solution                   SLIP_LU/Source/SLIP_check_solution.c:31-113, SLIP_LU.h:988-993
  *   slip_hip_factor_solve_double,        <->  the rest of SLIP_solve_double: SLIP_permute_x, SLIP_scale_x, SLIP_get_double_soln
  *   slip_hip_solution_to_double               SLIP_LU/Source/SLIP_solve_double.c:84-100, SLIP_gmp.c:1063 (mpq_get_d)
+ *   slip_hip_factor_solve_rational,      <->  the rest of SLIP_solve_mpq: the mpq_div of SLIP_LU_solve, SLIP_permute_x, SLIP_scale_x
+ *   slip_hip_solution_to_rational             SLIP_LU/Source/SLIP_solve_mpq.c:74-93, slip_array_div.c:36-49 (mpq_canonicalize per entry)
  *   slip_hip_factor_solve_transpose,     <->  no counterpart: the reference solves A x = b only (KLU's klu_tsolve,
  *   slip_hip_factor_check_transpose           UMFPACK's A' system are the transposed solves of other sparse LUs)
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
@@ -239,6 +241,45 @@ int slip_hip_solution_to_double(int32_t n, int32_t nrhs, const int32_t *xlen, co
  * (leading bits only) left to the exact wave pass */
 double slip_hip_factor_to_double_ms(const slip_hip_factor *f);
 int64_t slip_hip_factor_to_double_slow(const slip_hip_factor *f);
+
+/* Solve to reduced fractions: the tail of SLIP_solve_mpq (SLIP_LU/Source/SLIP_solve_mpq.c:74-93: the mpq_div of SLIP_LU_solve,
+ * slip_array_div.c:36-49, then SLIP_permute_x and SLIP_scale_x, every mpq_* call canonicalising) on the device, after the
+ * substitution of slip_hip_factor_solve (transpose = 0) or slip_hip_factor_solve_transpose (transpose != 0).
+ *
+ * Every result is GMP's canonical form of the exact rational: with g = gcd(|N|, |D|), num = sgn(N * D) * |N| / g and
+ * den = |D| / g -- den > 0, the sign on the numerator, 0 as 0 / 1.
+ *
+ * slip_hip_factor_solve_rational: b, transpose, the scale parts and the statuses exactly as slip_hip_factor_solve_double takes
+ * and returns them (NULL limbs = 1, a zero part is SLIP_HIP_INCORRECT_INPUT, a negative part carries its sign; a plain call
+ * on a handle from slip_hip_factor_from_factors is SLIP_HIP_INCORRECT_INPUT, the transposed call works there).  Entry c*n + j
+ * of the result is the canonical form of xnum * snum / (det * sden) -- SLIP_scale_x applied once, exactly -- with j the
+ * ORIGINAL column for the plain solve (SLIP_permute_x applied: j = q[p] for pivot position p) and the original row id for
+ * the transposed one.  The result is two compact slabs allocated by the library (release each of the four arrays with
+ * slip_hip_free): numlen / denlen hold nrhs * n signed limb counts (numlen 0 for a zero, denlen always >= 1), the limbs lie
+ * back to back in entry order without high zero limbs, *num_limbs_out / *den_limbs_out say how many there are.  Nothing but
+ * these slabs comes back from the device: neither the unreduced numerators nor the factors are downloaded.
+ * slip_hip_factor_solve / _solve_transpose / _solve_double afterwards return what they always did.
+ *
+ * slip_hip_solution_to_rational: no handle; the (x, d) form of slip_hip_check_solution and slip_hip_solution_to_double, one
+ * nonzero denominator per right-hand side, the result in the order of the input.  Limb arrays travel with their capacities,
+ * high zero limbs are allowed.  SLIP_HIP_INCORRECT_INPUT: nrhs < 1, a limb array longer than its capacity, d_c == 0.
+ *
+ * No CPU fallback: without a device the result is SLIP_HIP_DEVICE_ERROR. */
+int slip_hip_factor_solve_rational(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                   int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
+                                   int32_t **numlen_out, uint64_t **numlimbs_out, int64_t *num_limbs_out,
+                                   int32_t **denlen_out, uint64_t **denlimbs_out, int64_t *den_limbs_out, void *stream);
+int slip_hip_solution_to_rational(int32_t n, int32_t nrhs, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                  const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                  int32_t **numlen_out, uint64_t **numlimbs_out, int64_t *num_limbs_out,
+                                  int32_t **denlen_out, uint64_t **denlimbs_out, int64_t *den_limbs_out, void *stream);
+/* device ms of the reduction kernel of the last slip_hip_factor_solve_rational; out[4]: the entries of that call settled by
+ * the kernel's lane pass (a zero numerator, or both parts within 64 bits), by the wave pass in registers (operands of at most
+ * 256 digits of 32 bits) with g = 1 and with g > 1, and by the wave pass through memory (wider operands) */
+double slip_hip_factor_to_rational_ms(const slip_hip_factor *f);
+int    slip_hip_factor_to_rational_paths(const slip_hip_factor *f, int64_t out[4]);
+/* the same four counts for the calling thread's last slip_hip_solution_to_rational */
+int    slip_hip_solution_to_rational_paths(int64_t out[4]);
 
 /* Subtree farm (no counterpart in the reference, which has no parallelism): multiply the K committed
  * columns by per-column scales on the device -- L(:,k) and rho[k] by scale[k], an entry of U in the row whose pivot sits

@@ -38,7 +38,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_check", "slip_hip_check_solution", "slip_hip_factor_check_ms",
            "slip_hip_factor_solve_transpose", "slip_hip_factor_check_transpose", "slip_hip_factor_solve_transpose_ms",
            "slip_hip_factor_solve_double", "slip_hip_solution_to_double", "slip_hip_factor_to_double_ms",
-           "slip_hip_factor_to_double_slow")
+           "slip_hip_factor_to_double_slow",
+           "slip_hip_factor_solve_rational", "slip_hip_solution_to_rational", "slip_hip_factor_to_rational_ms",
+           "slip_hip_factor_to_rational_paths", "slip_hip_solution_to_rational_paths")
 
 _libs = {}
 
@@ -108,5 +110,16 @@ def load(path=None):
     lib.slip_hip_factor_to_double_ms.restype = C.c_double
     lib.slip_hip_factor_to_double_slow.argtypes = [vp]
     lib.slip_hip_factor_to_double_slow.restype = C.c_int64
+    slabs = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)] * 2
+    lib.slip_hip_factor_solve_rational.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp] + slabs + [vp]
+    lib.slip_hip_factor_solve_rational.restype = C.c_int
+    lib.slip_hip_solution_to_rational.argtypes = [C.c_int32, C.c_int32, vp, vp, i64, vp, vp, i64] + slabs + [vp]
+    lib.slip_hip_solution_to_rational.restype = C.c_int
+    lib.slip_hip_factor_to_rational_ms.argtypes = [vp]
+    lib.slip_hip_factor_to_rational_ms.restype = C.c_double
+    lib.slip_hip_factor_to_rational_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_to_rational_paths.restype = C.c_int
+    lib.slip_hip_solution_to_rational_paths.argtypes = [vp]
+    lib.slip_hip_solution_to_rational_paths.restype = C.c_int
     _libs[path] = lib
     return lib

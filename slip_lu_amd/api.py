@@ -107,6 +107,41 @@ def solution_to_double(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, lib_path=None):
     return out[:nrhs, :n]
 
 
+def _take_slab(lib, pl, px, nl, count):
+    """a (counts, limbs) result the library allocated -> numpy copies; the library's arrays are released"""
+    lens = np.ctypeslib.as_array(C.cast(pl, C.POINTER(C.c_int32)), shape=(count,)).copy()
+    limbs = (np.ctypeslib.as_array(C.cast(px, C.POINTER(C.c_uint64)), shape=(nl.value,)).copy()
+             if nl.value else np.zeros(0, np.uint64))
+    lib.slip_hip_free(pl)
+    lib.slip_hip_free(px)
+    return lens, limbs
+
+
+def solution_to_rational(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, lib_path=None):
+    """Numerators over one nonzero denominator per right-hand side -> every entry in lowest terms on the device
+    (slip_hip_solution_to_rational): (numlen, numlimbs, denlen, denlimbs), two compact limb slabs of n * nrhs entries in the
+    order of the input, GMP's canonical form -- den > 0, the sign on num, 0 as 0 / 1."""
+    lib = _lib.load(lib_path)
+    n, nrhs = int(n), int(nrhs)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
+    if nrhs >= 1 and (xlen.size != n * nrhs or dlen.size != nrhs):
+        raise ValueError("solution_to_rational: xlen needs n*nrhs entries, dlen nrhs")
+    pnl, pnx, nnl, pdl, pdx, dnl = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
+    rc = lib.slip_hip_solution_to_rational(n, nrhs, xlen.ctypes.data, xlimbs.ctypes.data, xcap, dlen.ctypes.data, dlimbs.ctypes.data,
+                                           dcap, C.byref(pnl), C.byref(pnx), C.byref(nnl), C.byref(pdl), C.byref(pdx), C.byref(dnl), None)
+    if rc:
+        raise SlipError(rc, "slip_hip_solution_to_rational")
+    return _take_slab(lib, pnl, pnx, nnl, n * nrhs) + _take_slab(lib, pdl, pdx, dnl, n * nrhs)
+
+
+def solution_to_rational_paths(lib_path=None):
+    """entries of this thread's last solution_to_rational by the path that settled them, as Factorization.to_rational_paths"""
+    out = np.zeros(4, np.int64)
+    _lib.load(lib_path).slip_hip_solution_to_rational_paths(out.ctypes.data)
+    return [int(v) for v in out]
+
+
 def matgen(n, density, bits, seed, lib_path=None):
     """The benchmark's synthetic CSC (slip_matgen.h) -> Ap, Ai, Ax (int64 values)."""
     lib = _lib.load(lib_path)
@@ -327,6 +362,44 @@ class Factorization:
     def to_double_slow(self):
         """entries of the last solve_double that the lane pass left to the exact wave pass"""
         return self.lib.slip_hip_factor_to_double_slow(self.h)
+
+    def solve_rational(self, blen, blimbs, nrhs=1, transpose=False, scale=None, stream=None):
+        """Solve and reduce on the device (slip_hip_factor_solve_rational): (numlen, numlimbs, denlen, denlimbs), entry
+        c*n + j the exact rational scale * xnum / det in lowest terms, GMP's canonical form (den > 0, the sign on num, 0 as
+        0 / 1: what SLIP_solve_mpq returns).  Only these two compact slabs come back.  b, transpose, scale and the order of
+        the result as `solve_double`: ORIGINAL column order for the plain solve, original row id for the transposed one."""
+        blen = np.ascontiguousarray(blen, dtype=np.int32)
+        blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
+        nrhs = int(nrhs)
+        if nrhs >= 1 and blen.size != self.n * nrhs:
+            raise ValueError("blen must hold n*nrhs entries")
+        if blimbs.size == 0:
+            blimbs = np.zeros(1, dtype=np.uint64)
+        if scale is None:
+            sn = sd = (0, None)
+        else:
+            num, den = (scale.numerator, scale.denominator) if hasattr(scale, "numerator") else scale
+            sn, sd = _int_limbs(num), _int_limbs(den)
+        pnl, pnx, nnl, pdl, pdx, dnl = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        rc = self.lib.slip_hip_factor_solve_rational(self.h, int(bool(transpose)), nrhs, blen.ctypes.data, blimbs.ctypes.data,
+                                                     sn[0], None if sn[1] is None else sn[1].ctypes.data,
+                                                     sd[0], None if sd[1] is None else sd[1].ctypes.data,
+                                                     C.byref(pnl), C.byref(pnx), C.byref(nnl), C.byref(pdl), C.byref(pdx), C.byref(dnl),
+                                                     C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_solve_rational")
+        return _take_slab(self.lib, pnl, pnx, nnl, self.n * nrhs) + _take_slab(self.lib, pdl, pdx, dnl, self.n * nrhs)
+
+    def to_rational_ms(self):
+        """device ms of the reduction kernel of the last solve_rational"""
+        return self.lib.slip_hip_factor_to_rational_ms(self.h)
+
+    def to_rational_paths(self):
+        """entries of the last solve_rational settled by [the lane pass, the register wave pass with g = 1, the same with
+        g > 1, the memory class]"""
+        out = np.zeros(4, np.int64)
+        self.lib.slip_hip_factor_to_rational_paths(self.h, out.ctypes.data)
+        return [int(v) for v in out]
 
     def check(self, blen, blimbs, xlen, xlimbs, nrhs=1, stream=None):
         """Exact check of a solve on the device (slip_hip_factor_check): A(:,q) xnum_c == det b_c, with b as `solve` takes

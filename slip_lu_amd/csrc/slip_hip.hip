@@ -503,6 +503,416 @@ static void slip_todouble_body(SlipToDoubleArgs A)
     if (lane == 0 && slow_total) slip_atomic_add_u64(A.nslow, slow_total);
 }
 
+/* Solution as reduced fractions (slip_hip_factor_solve_rational, slip_hip_solution_to_rational): per entry the canonical form
+ * of N / D that mpq_canonicalize leaves (SLIP_solve_mpq's output: SLIP_LU_solve's mpq_div, SLIP_permute_x, SLIP_scale_x):
+ *     g = gcd(|N|, |D|),   num = sgn(N * D) * |N| / g,   den = |D| / g > 0,   0 = 0 / 1.
+ *
+ * Lane pass, one lane per entry: N = 0, and every pair that fits 64 bits (a binary gcd and two divisions in the lane).
+ * Wave pass, one wavefront per remaining entry, wave-uniform throughout.  With N = 2^zn * N', D = 2^zd * D' (N', D' odd) and
+ * z = min(zn, zd):  g = 2^z * h,  h = gcd(N', D') odd,  num = (N >> z) / h,  den = (D >> z) / h: the power of two is a shift
+ * and the odd part an exact 2-adic division (Hensel in registers, the Newton inverse of h through memory; nothing when h = 1).
+ *
+ * h = gcd(a, b) of two numbers of which at least one is odd (both, at the start), a >= b (slip_gcd_odd_reg /
+ * slip_reduce_wide).  Every step replaces (a, b) by a pair with the same set of common divisors -- an EXACT invariant, no
+ * factor is ever introduced -- and retires digits, not bits:
+ *   (i)  bits(a) - bits(b) = G >= 8, b odd (an even b has its trailing zeros shifted out first):  t = a * b^-1 mod 2^G,
+ *        a <- |a - t*b| / 2^G.  2^G divides a - t*b by the choice of t; t*b < 2^(G + bits(b)) = 2^bits(a), so the difference
+ *        needs no headroom and a comes down to b's length in ONE step, however many digits apart they were; odd b shares
+ *        no factor with 2^G, so gcd(a', b) = gcd(a, b).  G <= 32: t is one digit (a scalar Newton inverse).  Above,
+ *        b^-1 modulo B^ceil(G/32) is a Newton iteration (wr_inv_extend / wb_inv_extend) and t, t*b are two products.
+ *   (ii) G < 8, Lehmer: ah = floor(a / 2^s), bh = floor(b / 2^s) with s = bits(a) - 62.  Euclid's algorithm runs on (ah, bh)
+ *        while the quotient is the same for both ends of the intervals the leading parts leave open,
+ *            floor((ah + A) / (bh + C)) == floor((ah + B) / (bh + D))              (Knuth 4.5.2, Algorithm L)
+ *        -- then it IS the quotient of the full numbers -- and while the cofactors stay below 2^31.  The wave applies the
+ *        matrix, a' = A*a + B*b, b' = C*a + D*b (determinant +-1: the same common divisors): two consecutive remainders of
+ *        Euclid's sequence for (a, b), both >= 0, so the arithmetic modulo B^W is exact.  About 30 bits go per step.  The
+ *        remainders may be even; h is odd, so at most one of the two is, and (i) and (iii) shift its trailing zeros out
+ *        when they need an odd number (dividing one of the two by 2 leaves an odd gcd what it was).
+ *   (iii) no matrix (the first quotient is already open: a / b within 2^-54 of an integer):  a <- (a - b) >> ctz, both odd.
+ *   When both fit 64 bits the binary gcd of the lane pass finishes.  a == b or b == 0 ends the loop.
+ * Two width classes: max(|N|, |D|) <= 256 digits in registers (WR<1..4>), wider through this wave's scratch in global memory
+ * (five buffers of wcap digits, sized by the host from the widest operand of the call).
+ *
+ * Output: entry (c, p) goes to slot c*n + oidx[p]; the host gave every slot room for |N| and |D| themselves (numoff, denoff:
+ * limb offsets), the kernel writes whole limbs (an odd digit count is padded with a zero digit) and the signed digit counts.
+ * The kernel never aborts: a zero denominator (refused by the host) gives 0 digits of num and den. */
+struct SlipReduceArgs {
+    int32_t n, nrhs;
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* N: entry c*n + p, signed digit counts, limb offsets */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* D: one per right-hand side                         */
+    const int32_t *oidx;                                                           /* entry p goes to slot c*n + oidx[p]; null: to p     */
+    int32_t flip;                                                                  /* negate every result (the sign of a scale)          */
+    int32_t chunk;                                                                 /* entries a wave takes per round, 1..64              */
+    int32_t *numlen, *denlen;                                                      /* per slot: signed digit count of num, digits of den */
+    const int64_t *numoff, *denoff; uint64_t *numlimbs, *denlimbs;                 /* per slot: where its limbs go                       */
+    dig_t *scratch; int32_t wcap;                                                  /* wave pass: 8 + 5 * wcap digits per wave, wcap >= 264 */
+    unsigned long long *paths;                                                     /* entries settled by: lane, reg g = 1, reg g > 1, memory */
+};
+
+/* gcd of two odd 64-bit numbers (binary) */
+SLIP_DEV uint64_t slip_gcd64_odd(uint64_t u, uint64_t v)
+{
+    while (u != v) {
+        if (u < v) { const uint64_t t = u; u = v; v = t; }
+        u -= v;
+        u >>= slip_ctz64(u);
+    }
+    return u;
+}
+
+/* Lehmer's cofactors from the leading parts ah >= bh > 0 (both below 2^62, the same shift of a and b): m = |A|, |B|, |C|, |D|,
+ * each below 2^31; *bneg: B < 0 (then A >= 0: a' = |A|a - |B|b, else |B|b - |A|a), *dpos: D > 0 (b' = |D|b - |C|a, else the
+ * reverse).  0 when the leading parts allow no step. */
+SLIP_DEV int slip_lehmer(uint64_t ah, uint64_t bh, uint32_t *m, int *bneg, int *dpos)
+{
+    const int64_t LIM = 0x7FFFFFFFll;
+    int64_t A = 1, B = 0, C = 0, Dd = 1, a = (int64_t) ah, b = (int64_t) bh;
+    for (;;) {
+        if (b + C <= 0 || b + Dd <= 0) break;
+        const int64_t q = (a + A) / (b + C);
+        if (q != (a + B) / (b + Dd) || q > LIM) break;
+        const int64_t nC = A - q * C, nD = B - q * Dd;
+        if (nC > LIM || nC < -LIM || nD > LIM || nD < -LIM) break;
+        const int64_t t = a - q * b;
+        A = C; C = nC; B = Dd; Dd = nD; a = b; b = t;
+    }
+    if (B == 0) return 0;
+    m[0] = (uint32_t)(A < 0 ? -A : A); m[1] = (uint32_t)(B < 0 ? -B : B);
+    m[2] = (uint32_t)(C < 0 ? -C : C); m[3] = (uint32_t)(Dd < 0 ? -Dd : Dd);
+    *bneg = B < 0; *dpos = Dd > 0;
+    return 1;
+}
+
+/* the 2-adic multiplier of step (i): t = a0 / b0 mod 2^k for odd b0, 1 <= k <= 32 */
+SLIP_DEV uint32_t slip_gcd_quot(uint32_t a0, uint32_t b0, int k)
+{
+    const uint32_t t = a0 * wb_inv32(b0);
+    return k < 32 ? t & ((1u << k) - 1u) : t;
+}
+
+/* digits [0, 64*D) of (p >> shift), p of len digits */
+template <int D> SLIP_DEV WR<D> wr_load_shr(const dig_t *p, int len, int shift)
+{
+    const int lane = slip_lane(), sw = shift >> 5, sb = shift & 31;
+    WR<D> x;
+#pragma unroll
+    for (int q = 0; q < D; q++) {
+        const int idx = 64 * q + lane + sw;
+        const uint32_t lo = idx < len ? p[idx] : 0u, hi = idx + 1 < len ? p[idx + 1] : 0u;
+        x.d[q] = sb ? ((lo >> sb) | (hi << (32 - sb))) : lo;
+    }
+    return x;
+}
+
+/* x modulo 2^K */
+template <int D> SLIP_DEV WR<D> wr_mask_bits(const WR<D> &x, int K)
+{
+    const int lane = slip_lane(), w = K >> 5;
+    const uint32_t top = (K & 31) ? (1u << (K & 31)) - 1u : 0u;
+    WR<D> r;
+#pragma unroll
+    for (int q = 0; q < D; q++) { const int c = 64 * q + lane; r.d[q] = c < w ? x.d[q] : (c == w ? x.d[q] & top : 0u); }
+    return r;
+}
+
+/* x with its trailing zero bits shifted out (0 stays 0); scratch: 64*D + 2 digits */
+template <int D> SLIP_DEV WR<D> wr_strip(const WR<D> &x, dig_t *scratch)
+{
+#pragma unroll
+    for (int q = 0; q < D; q++) {
+        const uint64_t nz = slip_ballot(x.d[q] != 0);
+        if (nz) { const int t = slip_ctz64(nz); return wr_shr<D>(x, 32 * (64 * q + t) + slip_ctz32(slip_readlane(x.d[q], t)), scratch); }
+    }
+    return x;
+}
+
+/* floor(x / 2^s) modulo 2^64 as a wave-uniform value */
+template <int D> SLIP_DEV uint64_t wr_window(const WR<D> &x, int s)
+{
+    const int i = s >> 5, sb = s & 31;
+    const uint64_t lo = (uint64_t) wr_digit<D>(x, i) | ((uint64_t) wr_digit<D>(x, i + 1) << 32);
+    return sb ? (lo >> sb) | ((uint64_t) wr_digit<D>(x, i + 2) << (64 - sb)) : lo;
+}
+
+/* gcd of two numbers of which at least one is odd, in registers (steps (i)-(iii) above); a half that has become narrow enough
+ * goes on in fewer registers */
+template <int D> SLIP_DEV WR<D> slip_gcd_odd_reg(WR<D> a, WR<D> b, dig_t *scratch)
+{
+    int ordered = 0;                                                 /* a > b is known: two consecutive remainders */
+    for (;;) {
+        int la = wr_len<D>(a), lb = wr_len<D>(b);
+        if (lb == 0) return a;
+        if (la == 0) return b;
+        if (!ordered) {
+            const int c = la != lb ? (la > lb ? 1 : -1) : wr_cmp<D>(a, b);
+            if (c == 0) return a;
+            if (c < 0) { const WR<D> t = a; a = b; b = t; const int tl = la; la = lb; lb = tl; }
+        }
+        ordered = 0;
+        if constexpr (D > 1) {
+            if (la <= 64 * (D / 2)) {
+                WR<D / 2> na, nb;
+#pragma unroll
+                for (int q = 0; q < D / 2; q++) { na.d[q] = a.d[q]; nb.d[q] = b.d[q]; }
+                const WR<D / 2> g = slip_gcd_odd_reg<D / 2>(na, nb, scratch);
+                WR<D> r = wr_zero<D>();
+#pragma unroll
+                for (int q = 0; q < D / 2; q++) r.d[q] = g.d[q];
+                return r;
+            }
+        }
+        if (la <= 2) {
+            const uint64_t u = wr_window<D>(a, 0), v = wr_window<D>(b, 0);
+            const uint64_t g = slip_gcd64_odd(u >> slip_ctz64(u), v >> slip_ctz64(v));
+            WR<D> r = wr_zero<D>();
+            if (slip_lane() < 2) r.d[0] = slip_lane() ? (uint32_t)(g >> 32) : (uint32_t) g;
+            return r;
+        }
+        const int ba = 32 * la - slip_clz32(wr_digit<D>(a, la - 1)), bb = 32 * lb - slip_clz32(wr_digit<D>(b, lb - 1));
+        const uint32_t a0 = slip_readlane(a.d[0], 0), b0 = slip_readlane(b.d[0], 0);
+        if (ba - bb >= 8) {
+            if (!(b0 & 1u)) { b = wr_strip<D>(b, scratch); continue; }           /* then a is odd: the gcd stays */
+            const int K = ba - bb, md = (K + 31) >> 5;
+            WR<D> p;
+            if (md == 1) p = wr_mul_digit<D>(slip_gcd_quot(a0, b0, K), b);
+            else p = wr_mul<D>(wr_mask_bits<D>(wr_mul<D>(wr_inv_extend<D>(wr_zero<D>(), 0, md, b), md, a), K), md, b);
+            const int cp = wr_cmp<D>(a, p);
+            if (cp == 0) return b;                                   /* a = t * b */
+            a = wr_shr<D>(cp > 0 ? wr_addsub<D>(a, p, 1) : wr_addsub<D>(p, a, 1), K, scratch);
+            continue;
+        }
+        const int s = ba > 62 ? ba - 62 : 0;
+        uint32_t m[4]; int bneg, dpos;
+        if (slip_lehmer(wr_window<D>(a, s), wr_window<D>(b, s), m, &bneg, &dpos)) {
+            WR<D> pa, pb, pc, pd;
+            wr_mul_digit2<D>(m[0], m[2], a, pa, pc);
+            wr_mul_digit2<D>(m[1], m[3], b, pb, pd);
+            a = bneg ? wr_addsub<D>(pa, pb, 1) : wr_addsub<D>(pb, pa, 1);
+            b = dpos ? wr_addsub<D>(pd, pc, 1) : wr_addsub<D>(pc, pd, 1);
+            ordered = 1;
+        } else if (!(a0 & 1u)) a = wr_strip<D>(a, scratch);
+        else if (!(b0 & 1u)) b = wr_strip<D>(b, scratch);
+        else a = wr_strip<D>(wr_addsub<D>(a, b, 1), scratch);
+    }
+}
+
+/* the wave pass in registers: num and den of (x >> z) / h, (d >> z) / h written as whole limbs; returns 1 when g = 2^z * h > 1 */
+template <int D> SLIP_DEV int slip_reduce_reg(const dig_t *x, int la, int zn, const dig_t *d, int ld, int zd, dig_t *scratch,
+                                              dig_t *onum, dig_t *oden, int *lnum, int *lden)
+{
+    const int z = zn < zd ? zn : zd;
+    const WR<D> h = slip_gcd_odd_reg<D>(wr_load_shr<D>(x, la, zn), wr_load_shr<D>(d, ld, zd), scratch);
+    const int lh = wr_len<D>(h), one = lh == 1 && slip_readlane(h.d[0], 0) == 1u;
+    WR<D> T = wr_load_shr<D>(x, la, z);
+    if (!one) T = wr_div_hensel<D>(T, wr_len<D>(T) - lh + 1, h);
+    *lnum = wr_len<D>(T);
+    wr_store<D>(onum, T, (*lnum + 1) & ~1);
+    T = wr_load_shr<D>(d, ld, z);
+    if (!one) T = wr_div_hensel<D>(T, wr_len<D>(T) - lh + 1, h);
+    *lden = wr_len<D>(T);
+    wr_store<D>(oden, T, (*lden + 1) & ~1);
+    return !one || z > 0;
+}
+
+/* floor(x / 2^s) modulo 2^64 of a number in memory */
+SLIP_DEV uint64_t wb_window(const dig_t *x, int lx, int s)
+{
+    const int i = s >> 5, sb = s & 31;
+    const uint64_t lo = (uint64_t)(i < lx ? x[i] : 0u) | ((uint64_t)(i + 1 < lx ? x[i + 1] : 0u) << 32);
+    return sb ? (lo >> sb) | ((uint64_t)(i + 2 < lx ? x[i + 2] : 0u) << (64 - sb)) : lo;
+}
+
+/* dst = src with its trailing zero bits shifted out; returns its digits (src: ls >= 0 significant digits; no overlap) */
+SLIP_DEV int wb_strip(dig_t *dst, const dig_t *src, int ls)
+{
+    if (ls == 0) return 0;
+    wb_copy_shr(dst, src, ls, wb_ctz(src, ls), ls);
+    return wb_len(dst, ls);
+}
+
+/* the wave pass through memory (operands above 256 digits): the same steps on five buffers of wcap digits; sm: 8 digits */
+SLIP_DEV void slip_reduce_wide(const dig_t *x, int la, int zn, const dig_t *d, int ld, int zd, dig_t *sm, dig_t *buf, int wcap,
+                               dig_t *onum, dig_t *oden, int *lnum, int *lden)
+{
+    const int lane = slip_lane(), z = zn < zd ? zn : zd;
+    dig_t *a = buf, *b = buf + wcap, *P = b + wcap, *Q = P + wcap, *R = Q + wcap;
+    wb_copy_shr(a, x, la, zn, la);
+    wb_copy_shr(b, d, ld, zd, ld);
+    int na = wb_len(a, la), nb = wb_len(b, ld), ordered = 0;
+    for (;;) {
+        if (nb == 0) break;
+        if (!ordered) {
+            const int c = na == 0 ? -1 : wb_cmp(a, na, b, nb);
+            if (c == 0) break;
+            if (c < 0) { dig_t *t = a; a = b; b = t; const int tl = na; na = nb; nb = tl; }
+            if (nb == 0) break;
+        }
+        ordered = 0;
+        if (na <= 2) {
+            const uint64_t u = wb_window(a, na, 0), v = wb_window(b, nb, 0);
+            const uint64_t g = slip_gcd64_odd(u >> slip_ctz64(u), v >> slip_ctz64(v));
+            slip_wave_sync();
+            if (lane < 2) a[lane] = lane ? (uint32_t)(g >> 32) : (uint32_t) g;
+            slip_wave_sync();
+            na = (g >> 32) ? 2 : 1;
+            break;
+        }
+        const int ba = wb_bits(a, na), bb = wb_bits(b, nb);
+        if (ba - bb >= 8) {
+            if (!(b[0] & 1u)) { nb = wb_strip(P, b, nb); dig_t *t = b; b = P; P = t; continue; }      /* then a is odd: the gcd stays */
+            const int K = ba - bb, md = (K + 31) >> 5;
+            wb_inv_extend(P, 0, md, b, nb, Q, R);                            /* 1 / b modulo B^md */
+            wb_mul_lo(Q, a, na, P, md, md);
+            if (lane == 0 && (K & 31)) Q[md - 1] &= (1u << (K & 31)) - 1u;    /* t = a / b modulo 2^K */
+            slip_wave_sync();
+            wb_mul_lo(R, Q, wb_len(Q, md), b, nb, na);
+            const int np = wb_len(R, na), cp = wb_cmp(a, na, R, np);
+            if (cp == 0) { dig_t *u = a; a = b; b = u; na = nb; break; }        /* a = t * b */
+            if (cp > 0) wb_addsub(R, a, na, R, np, na, 1); else wb_addsub(R, R, np, a, na, na, 1);
+            const int nr = wb_len(R, na);
+            wb_copy_shr(a, R, nr, K, nr);
+            na = wb_len(a, nr);
+            continue;
+        }
+        const int s = ba > 62 ? ba - 62 : 0;
+        uint32_t m[4]; int bneg, dpos;
+        if (slip_lehmer(wb_window(a, na, s), wb_window(b, nb, s), m, &bneg, &dpos)) {
+            if (lane < 4) sm[lane] = lane == 0 ? m[0] : (lane == 1 ? m[1] : (lane == 2 ? m[2] : m[3]));
+            slip_wave_sync();
+            const int W = na;
+            wb_mul_lo(P, sm, 1, a, na, W);
+            wb_mul_lo(Q, sm + 1, 1, b, nb, W);
+            if (bneg) wb_addsub(P, P, W, Q, W, W, 1); else wb_addsub(P, Q, W, P, W, W, 1);
+            wb_mul_lo(Q, sm + 2, 1, a, na, W);
+            wb_mul_lo(R, sm + 3, 1, b, nb, W);
+            if (dpos) wb_addsub(Q, R, W, Q, W, W, 1); else wb_addsub(Q, Q, W, R, W, W, 1);
+            dig_t *t = a; a = P; P = t; t = b; b = Q; Q = t;
+            na = wb_len(a, W); nb = wb_len(b, W);
+            ordered = 1;
+        } else if (!(a[0] & 1u)) { na = wb_strip(P, a, na); dig_t *t = a; a = P; P = t; }
+        else if (!(b[0] & 1u)) { nb = wb_strip(P, b, nb); dig_t *t = b; b = P; P = t; }
+        else {
+            wb_addsub(P, a, na, b, nb, na, 1);
+            na = wb_strip(a, P, wb_len(P, na));
+        }
+    }
+    /* h = a[0..na); b, P, Q and R are free */
+    dig_t *T = b;
+    const int one = na == 1 && a[0] == 1u;
+    const int lt = (wb_bits(x, la) - z + 31) >> 5, ltd = (wb_bits(d, ld) - z + 31) >> 5;
+    if (one) {
+        wb_copy_shr(onum, x, la, z, (lt + 1) & ~1);
+        wb_copy_shr(oden, d, ld, z, (ltd + 1) & ~1);
+        *lnum = lt; *lden = ltd;
+        return;
+    }
+    const int qn = lt - na + 1, qd = ltd - na + 1;
+    wb_inv_extend(P, 0, qn > qd ? qn : qd, a, na, Q, R);             /* 1 / h modulo B^max(qn, qd) */
+    wb_copy_shr(T, x, la, z, lt);
+    wb_mul_lo(onum, T, lt, P, qn, qn);                               /* the quotient is below B^qn: exact modulo B^qn */
+    *lnum = wb_len(onum, qn);
+    wb_copy_shr(T, d, ld, z, ltd);
+    wb_mul_lo(oden, T, ltd, P, qd, qd);
+    *lden = wb_len(oden, qd);
+    if (lane == 0) { if (qn & 1) onum[qn] = 0u; if (qd & 1) oden[qd] = 0u; }      /* whole limbs */
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_reduce_kernel(SlipReduceArgs A)
+#else
+static void slip_reduce_body(SlipReduceArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    dig_t *sm = A.scratch + wave0 * (8 + 5 * (int64_t) A.wcap), *buf = sm + 8;
+    const int64_t items = (int64_t) A.n * A.nrhs;
+    unsigned long long cnt0 = 0, cnt1 = 0, cnt2 = 0, cnt3 = 0;
+    for (int64_t base = wave0 * A.chunk; base < items; base += nwaves * A.chunk) {
+        const int64_t it = base + lane;
+        const int mine = lane < A.chunk && it < items;
+        int wide = 0;
+        if (mine) {
+            const int c = (int)(it / A.n), p = (int)(it - (int64_t) c * A.n);
+            const int64_t slot = (int64_t) c * A.n + (A.oidx ? A.oidx[p] : p);
+            const int32_t sx = A.xlen[it], sd = A.dlen[c];
+            const dig_t *x = (const dig_t *)(A.xlimbs + A.xoff[it]), *d = (const dig_t *)(A.dlimbs + A.doff[c]);
+            const int la = slip_trim_digits(x, slip_abs(sx)), ld = slip_trim_digits(d, slip_abs(sd));
+            const int neg = ((sx < 0) != (sd < 0)) != (A.flip != 0);
+            if (ld == 0) { A.numlen[slot] = 0; A.denlen[slot] = 0; }
+            else if (la == 0) {
+                A.numlen[slot] = 0; A.denlen[slot] = 1;
+                A.denlimbs[A.denoff[slot]] = 1ull;
+            } else if (la <= 2 && ld <= 2) {
+                uint64_t u = x[0] | ((uint64_t)(la > 1 ? x[1] : 0u) << 32), v = d[0] | ((uint64_t)(ld > 1 ? d[1] : 0u) << 32);
+                const int zu = slip_ctz64(u), zv = slip_ctz64(v);
+                const uint64_t g = slip_gcd64_odd(u >> zu, v >> zv) << (zu < zv ? zu : zv);
+                u /= g; v /= g;
+                const int lu = (u >> 32) ? 2 : 1;
+                A.numlen[slot] = neg ? -lu : lu; A.denlen[slot] = (v >> 32) ? 2 : 1;
+                A.numlimbs[A.numoff[slot]] = u; A.denlimbs[A.denoff[slot]] = v;
+            } else wide = 1;
+        }
+        uint64_t pend = slip_ballot(wide);
+        cnt0 += (unsigned long long)(slip_popc64(slip_ballot(mine)) - slip_popc64(pend));
+        while (pend) {
+            const int src = slip_ctz64(pend);
+            pend &= pend - 1;
+            const int64_t e = base + src;
+            const int c = (int)(e / A.n), p = (int)(e - (int64_t) c * A.n);
+            const int64_t slot = (int64_t) c * A.n + (A.oidx ? A.oidx[p] : p);
+            const int32_t sx = A.xlen[e], sd = A.dlen[c];
+            const dig_t *x = (const dig_t *)(A.xlimbs + A.xoff[e]), *d = (const dig_t *)(A.dlimbs + A.doff[c]);
+            const int la = slip_trim_digits(x, slip_abs(sx)), ld = slip_trim_digits(d, slip_abs(sd));
+            const int zn = wb_ctz(x, la), zd = wb_ctz(d, ld), need = la > ld ? la : ld;
+            dig_t *onum = (dig_t *)(A.numlimbs + A.numoff[slot]), *oden = (dig_t *)(A.denlimbs + A.denoff[slot]);
+            int lnum = 0, lden = 0, g1 = 0;
+            if (need <= 64) g1 = slip_reduce_reg<1>(x, la, zn, d, ld, zd, buf, onum, oden, &lnum, &lden);
+            else if (need <= 128) g1 = slip_reduce_reg<2>(x, la, zn, d, ld, zd, buf, onum, oden, &lnum, &lden);
+            else if (need <= 192) g1 = slip_reduce_reg<3>(x, la, zn, d, ld, zd, buf, onum, oden, &lnum, &lden);
+            else if (need <= 256) g1 = slip_reduce_reg<4>(x, la, zn, d, ld, zd, buf, onum, oden, &lnum, &lden);
+            else slip_reduce_wide(x, la, zn, d, ld, zd, sm, buf, A.wcap, onum, oden, &lnum, &lden);      /* need + 2 <= wcap: the host sized it */
+            if (need > 256) cnt3++; else if (g1) cnt2++; else cnt1++;
+            if (lane == 0) {
+                A.numlen[slot] = (((sx < 0) != (sd < 0)) != (A.flip != 0)) ? -lnum : lnum;
+                A.denlen[slot] = lden;
+            }
+            slip_wave_sync();
+        }
+    }
+    if (lane == 0) {
+        if (cnt0) slip_atomic_add_u64(A.paths + 0, cnt0);
+        if (cnt1) slip_atomic_add_u64(A.paths + 1, cnt1);
+        if (cnt2) slip_atomic_add_u64(A.paths + 2, cnt2);
+        if (cnt3) slip_atomic_add_u64(A.paths + 3, cnt3);
+    }
+}
+
+/* The reduced fractions packed: slot t's limbs move from where slip_reduce_kernel left them (soff) to their place in the compact
+ * slab the ABI returns (doff), one wavefront per slot.  len: signed digit counts. */
+struct SlipPackArgs {
+    int64_t count;
+    const int32_t *len; const int64_t *soff, *doff; const uint64_t *src; uint64_t *dst;
+};
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_pack_kernel(SlipPackArgs A)
+#else
+static void slip_pack_body(SlipPackArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    for (int64_t t = wave0; t < A.count; t += nwaves) {
+        const int l = (slip_abs(A.len[t]) + 1) >> 1;
+        const uint64_t *s = A.src + A.soff[t];
+        uint64_t *o = A.dst + A.doff[t];
+        for (int k = lane; k < l; k += SLIP_WAVE) o[k] = s[k];
+    }
+}
+
 /* The transposed view of complete factors (slip_hip_factor_solve_transpose).  With M = A(row_perm, q) the matrix that was
  * factorised, every entry of a REF factorisation is a minor of M (L(i,k) = det M[{0..k-1,i},{0..k}], U(k,j) =
  * det M[{0..k},{0..k-1,j}], rho_k = det M[0..k,0..k]); transposing swaps the rows and columns of every minor, so the REF
@@ -735,6 +1145,8 @@ struct slip_hip_factor {
     int64_t *chkt_rp, *chkt_re; int32_t *chkt_rx;
     /* slip_hip_factor_solve_double: device time of the last conversion kernel, entries of it that took the wave pass */
     double todouble_ms; int64_t todouble_slow;
+    /* slip_hip_factor_solve_rational: device time of the last reduction kernel, entries of it by the path that settled them */
+    double torational_ms; int64_t torational_paths[4];
 };
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -2072,24 +2484,41 @@ static void scale_part(int32_t len, const uint64_t *limbs, int32_t *dig)
 }
 static int scale_is_unit(int32_t dig, const uint64_t *limbs) { return !limbs || ((dig == 1 || dig == -1) && limbs[0] == 1); }
 
-extern "C" int slip_hip_factor_solve_double(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
-                                            int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
-                                            double *x_out, void *stream_v)
+/* a solve left on the device with the scale applied, as the conversions take it (slip_hip_factor_solve_double, _solve_rational):
+ * numerators xnum * |snum| by (rhs, position), one denominator det * |sden| for every right-hand side, the sign of the scale
+ * apart (flip), and where position p goes: column q[p] (SLIP_permute_x); the transposed solve's position p is row i with
+ * pinv[i] = p */
+struct SlipScaledSol {
+    const int32_t *nlen; const int64_t *noff; const uint64_t *nlimbs;              /* numerators: entry c*n + p                  */
+    int32_t *ddlen; int64_t *ddoff; const uint64_t *dden; int32_t ddig;            /* denominators: entry c; digits of the one   */
+    const int32_t *doidx; int flip;
+    SlipSolveOut o;                                                                /* owned: the substitution's output ...        */
+    int32_t *own_oidx, *dxlen2; int64_t *dxoff2; uint64_t *dprod, *dxl2;           /* ... and what the scale made                 */
+};
+static void scaled_free(SlipScaledSol *s)
 {
-    if (!f || nrhs < 1 || !blen || !blimbs || !x_out) return SLIP_HIP_INCORRECT_INPUT;
+    dev_free(s->ddlen); dev_free(s->ddoff); dev_free(s->own_oidx); dev_free(s->dxlen2); dev_free(s->dxoff2); dev_free(s->dprod); dev_free(s->dxl2);
+    solve_out_free(&s->o);
+    memset(s, 0, sizeof *s);
+}
+
+static int solve_scaled(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                        int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs, hipStream_t stream, SlipScaledSol *s)
+{
+    memset(s, 0, sizeof *s);
+    if (!f || nrhs < 1 || !blen || !blimbs) return SLIP_HIP_INCORRECT_INPUT;
     int32_t sndig, sddig;
     scale_part(snlen, snlimbs, &sndig); scale_part(sdlen, sdlimbs, &sddig);
     if (sndig == 0 || sddig == 0) return SLIP_HIP_INCORRECT_INPUT;                  /* a zero scale part */
     if (!transpose && f->factors_only) return SLIP_HIP_INCORRECT_INPUT;             /* no q behind such a handle */
-    hipStream_t stream = (hipStream_t) stream_v;
-    SlipSolveOut o;
-    TRY_(solve_device(f, transpose, nrhs, blen, blimbs, stream, &o));
+    TRY_(solve_device(f, transpose, nrhs, blen, blimbs, stream, &s->o));
+    const SlipSolveOut &o = s->o;
     const int32_t n = f->n;
     const int64_t ne = (int64_t) n * nrhs;
     SlipParams *P = &f->P;
-    const int flip = (sndig < 0) != (sddig < 0);
+    s->flip = (sndig < 0) != (sddig < 0);
     const int32_t snabs = sndig < 0 ? -sndig : sndig, sdabs = sddig < 0 ? -sddig : sddig;
-    int32_t *ddlen = NULL, *doidx = NULL, *dplen = NULL, *dxlen2 = NULL; int64_t *ddoff = NULL, *dxoff2 = NULL; uint64_t *dsl = NULL, *dprod = NULL, *dxl2 = NULL;
+    int32_t *dplen = NULL; uint64_t *dsl = NULL;
     int32_t *hl = (int32_t *) malloc((size_t)(ne > nrhs ? ne : nrhs) * 4); int64_t *ho = (int64_t *) malloc((size_t)(ne > nrhs ? ne : nrhs) * 8);
     int rc = !hl || !ho ? SLIP_HIP_OUT_OF_MEMORY : 0;
     /* D = det = rho[n-1], read in place from the L slab through its pivot record (32 bytes; no limb of it is downloaded) */
@@ -2097,45 +2526,59 @@ extern "C" int slip_hip_factor_solve_double(slip_hip_factor *f, int32_t transpos
     DOWN_(&pr, P->piv.p_ + (n - 1), sizeof pr);
     int32_t ddig = pr.len < 0 ? -pr.len : pr.len;
     if (!rc && (pr.len == 0 || pr.off < 0 || pr.off + ((ddig + 1) >> 1) > P->Lcap_nl)) rc = SLIP_HIP_DEVICE_ERROR;
-    const uint64_t *dden = P->Llimbs; int64_t denoff = pr.off; int32_t denlen = pr.len;
-    A_(dev_alloc(&ddlen, nrhs)); A_(dev_alloc(&ddoff, nrhs));
+    s->dden = P->Llimbs; int64_t denoff = pr.off; int32_t denlen = pr.len;
+    A_(dev_alloc(&s->ddlen, nrhs)); A_(dev_alloc(&s->ddoff, nrhs));
     /* det * |sden|, once per call, on one wave */
     if (!rc && !scale_is_unit(sddig, sdlimbs)) {
         const int64_t zero = 0;
-        A_(dev_alloc(&dsl, (sdabs + 1) >> 1)); A_(dev_alloc(&dprod, (ddig + sdabs + 1) / 2 + 1)); A_(dev_alloc(&dplen, 1));
+        A_(dev_alloc(&dsl, (sdabs + 1) >> 1)); A_(dev_alloc(&s->dprod, (ddig + sdabs + 1) / 2 + 1)); A_(dev_alloc(&dplen, 1));
         UP_(dsl, sdlimbs, (size_t)((sdabs + 1) >> 1) * 8);
-        UP_(ddlen, &pr.len, 4); UP_(ddoff, &pr.off, 8);                             /* the source record; rewritten below */
+        UP_(s->ddlen, &pr.len, 4); UP_(s->ddoff, &pr.off, 8);                       /* the source record; rewritten below */
         int64_t *dzero = NULL;
         A_(dev_alloc(&dzero, 1)); UP_(dzero, &zero, 8);
-        A_(scale_launch(1, ddlen, ddoff, P->Llimbs, sdabs, dsl, dplen, dzero, dprod, stream));
+        A_(scale_launch(1, s->ddlen, s->ddoff, P->Llimbs, sdabs, dsl, dplen, dzero, s->dprod, stream));
         DOWN_(&denlen, dplen, 4);
         dev_free(dzero); dev_free(dsl); dsl = NULL;
-        dden = dprod; denoff = 0; ddig = denlen < 0 ? -denlen : denlen;
+        s->dden = s->dprod; denoff = 0; ddig = denlen < 0 ? -denlen : denlen;
     }
+    s->ddig = ddig;
     if (!rc) for (int32_t c = 0; c < nrhs; c++) { hl[c] = denlen; ho[c] = denoff; }
-    UP_(ddlen, hl, (size_t) nrhs * 4); UP_(ddoff, ho, (size_t) nrhs * 8);
+    UP_(s->ddlen, hl, (size_t) nrhs * 4); UP_(s->ddoff, ho, (size_t) nrhs * 8);
     /* xnum * |snum| per entry, only when |snum| != 1: the counts come down (4 bytes an entry) to lay the products out */
-    const int32_t *nlen = o.olen; const int64_t *noff = o.ooff; const uint64_t *nlimbs = o.olimbs;
+    s->nlen = o.olen; s->noff = o.ooff; s->nlimbs = o.olimbs;
     if (!rc && !scale_is_unit(sndig, snlimbs)) {
         DOWN_(hl, o.olen, (size_t) ne * 4);
         int64_t total = 0;
         if (!rc) for (int64_t t = 0; t < ne; t++) { ho[t] = total; total += ((hl[t] < 0 ? -hl[t] : hl[t]) + snabs + 1) / 2 + 1; }
-        A_(dev_alloc(&dsl, (snabs + 1) >> 1)); A_(dev_alloc(&dxlen2, ne)); A_(dev_alloc(&dxoff2, ne)); A_(dev_alloc(&dxl2, total));
-        UP_(dsl, snlimbs, (size_t)((snabs + 1) >> 1) * 8); UP_(dxoff2, ho, (size_t) ne * 8);
-        A_(scale_launch(ne, o.olen, o.ooff, o.olimbs, snabs, dsl, dxlen2, dxoff2, dxl2, stream));
-        nlen = dxlen2; noff = dxoff2; nlimbs = dxl2;
+        A_(dev_alloc(&dsl, (snabs + 1) >> 1)); A_(dev_alloc(&s->dxlen2, ne)); A_(dev_alloc(&s->dxoff2, ne)); A_(dev_alloc(&s->dxl2, total));
+        UP_(dsl, snlimbs, (size_t)((snabs + 1) >> 1) * 8); UP_(s->dxoff2, ho, (size_t) ne * 8);
+        A_(scale_launch(ne, o.olen, o.ooff, o.olimbs, snabs, dsl, s->dxlen2, s->dxoff2, s->dxl2, stream));
+        s->nlen = s->dxlen2; s->noff = s->dxoff2; s->nlimbs = s->dxl2;
     }
-    /* where position p goes: column q[p] (SLIP_permute_x); the transposed solve's position p is row i with pinv[i] = p */
+    s->doidx = f->dq;
     if (!rc && transpose) {
         for (int32_t i = 0; i < n; i++) hl[f->tpinv[i]] = i;
-        A_(dev_alloc(&doidx, n)); UP_(doidx, hl, (size_t) n * 4);
+        A_(dev_alloc(&s->own_oidx, n)); UP_(s->own_oidx, hl, (size_t) n * 4);
+        s->doidx = s->own_oidx;
     }
-    f->todouble_ms = 0; f->todouble_slow = 0;
-    A_(to_double_core(n, nrhs, nlen, noff, nlimbs, ddlen, ddoff, dden, ddig, transpose ? doidx : f->dq, flip, x_out, stream,
-                      &f->todouble_ms, &f->todouble_slow));
     free(hl); free(ho);
-    dev_free(ddlen); dev_free(ddoff); dev_free(doidx); dev_free(dplen); dev_free(dxlen2); dev_free(dxoff2); dev_free(dsl); dev_free(dprod); dev_free(dxl2);
-    solve_out_free(&o);
+    dev_free(dplen); dev_free(dsl);
+    if (rc) scaled_free(s);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_solve_double(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                            int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
+                                            double *x_out, void *stream_v)
+{
+    if (!x_out) return SLIP_HIP_INCORRECT_INPUT;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipScaledSol s;
+    TRY_(solve_scaled(f, transpose, nrhs, blen, blimbs, snlen, snlimbs, sdlen, sdlimbs, stream, &s));
+    f->todouble_ms = 0; f->todouble_slow = 0;
+    const int rc = to_double_core(f->n, nrhs, s.nlen, s.noff, s.nlimbs, s.ddlen, s.ddoff, s.dden, s.ddig, s.doidx, s.flip, x_out, stream,
+                                  &f->todouble_ms, &f->todouble_slow);
+    scaled_free(&s);
     return rc;
 }
 
@@ -2162,6 +2605,213 @@ extern "C" int slip_hip_solution_to_double(int32_t n, int32_t nrhs, const int32_
     dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
     slab_free(&xs); slab_free(&ds);
     return rc;
+}
+
+/* ---- solutions as reduced fractions (SLIP_solve_mpq's tail: mpq_div, SLIP_permute_x, SLIP_scale_x, each canonicalising;
+ * kernels: slip_reduce_kernel, slip_pack_kernel, slip_scale_kernel) ---- */
+
+/* the counts of the last slip_hip_solution_to_rational of this thread (the handle-less entry has nowhere else to keep them) */
+static thread_local int64_t slip_rational_paths_last[4];
+
+/* one slab of the result: the digit counts come down, the compact layout goes up, slip_pack_kernel moves the limbs and the
+ * compact slab is all that is downloaded.  dlen: signed digit counts by slot (device); on return len_out holds signed LIMB counts. */
+static int pack_download(int64_t ne, const int32_t *dlen, const int64_t *dsoff, const uint64_t *dsrc, int min_one,
+                         int32_t **len_out, uint64_t **limbs_out, int64_t *nl_out, hipStream_t stream)
+{
+    int32_t *hl = (int32_t *) malloc((size_t) ne * 4); int64_t *ho = (int64_t *) malloc((size_t) ne * 8);
+    int64_t *dcoff = NULL; uint64_t *dpacked = NULL, *out = NULL;
+    int rc = !hl || !ho ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    DOWN_(hl, dlen, (size_t) ne * 4);
+    int64_t total = 0;
+    if (!rc) for (int64_t t = 0; t < ne; t++) {
+        const int32_t l = ((hl[t] < 0 ? -hl[t] : hl[t]) + 1) >> 1;
+        if (min_one && l < 1) rc = SLIP_HIP_DEVICE_ERROR;                           /* a denominator is never empty */
+        ho[t] = total; total += l;
+    }
+    A_(dev_alloc(&dcoff, ne)); A_(dev_alloc(&dpacked, total));
+    UP_(dcoff, ho, (size_t) ne * 8);
+    if (!rc) {
+        SlipPackArgs A; memset(&A, 0, sizeof A);
+        A.count = ne; A.len = dlen; A.soff = dsoff; A.doff = dcoff; A.src = dsrc; A.dst = dpacked;
+#ifndef SLIP_EMULATE
+        int64_t blocks = (ne + 3) / 4; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(slip_pack_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, A);
+        HIP_(hipGetLastError());
+#else
+        emu::launch(2, 128, [A]() { slip_pack_body(A); }, 256 * 1024, 1);
+#endif
+        HIP_(hipStreamSynchronize(stream));
+    }
+    out = (uint64_t *) malloc((size_t)(total > 0 ? total : 1) * 8);
+    if (!out) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
+    DOWN_(out, dpacked, (size_t) total * 8);
+    if (!rc) {
+        for (int64_t t = 0; t < ne; t++) { const int32_t l = ((hl[t] < 0 ? -hl[t] : hl[t]) + 1) >> 1; hl[t] = hl[t] < 0 ? -l : l; }
+        *len_out = hl; *limbs_out = out; *nl_out = total;
+        hl = NULL; out = NULL;
+    }
+    free(hl); free(ho); free(out);
+    dev_free(dcoff); dev_free(dpacked);
+    return rc;
+}
+
+/* one reduction on the device: numerators (entry c*n + p) and one denominator per right-hand side as to_double_core takes them;
+ * hxdig, hddig: the same digit counts on the host (they size every slot: a fraction in lowest terms is no longer than what it
+ * came from); hoidx / doidx: where entry p goes, host and device copies (both NULL: to p).  The six outputs are compact
+ * malloc'ed slabs in slot order. */
+static int reduce_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int64_t *dxoff, const uint64_t *dxlimbs, const int32_t *hxdig,
+                       const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, const int32_t *hddig,
+                       const int32_t *hoidx, const int32_t *doidx, int flip,
+                       int32_t **numlen_out, uint64_t **numlimbs_out, int64_t *num_limbs_out,
+                       int32_t **denlen_out, uint64_t **denlimbs_out, int64_t *den_limbs_out,
+                       hipStream_t stream, double *ms_out, int64_t *paths_out)
+{
+    const int64_t ne = (int64_t) n * nrhs;
+    int32_t maxdig = 0;
+    int64_t ntotal = 0, dtotal = 0;
+    int64_t *hno = (int64_t *) malloc((size_t) ne * 8), *hdo = (int64_t *) malloc((size_t) ne * 8);
+    if (!hno || !hdo) { free(hno); free(hdo); return SLIP_HIP_OUT_OF_MEMORY; }
+    for (int32_t c = 0; c < nrhs; c++) {
+        const int32_t dd = hddig[c] < 0 ? -hddig[c] : hddig[c];
+        if (dd > maxdig) maxdig = dd;
+        for (int32_t p = 0; p < n; p++) {
+            const int64_t it = (int64_t) c * n + p, slot = (int64_t) c * n + (hoidx ? hoidx[p] : p);
+            const int32_t xd = hxdig[it] < 0 ? -hxdig[it] : hxdig[it];
+            if (xd > maxdig) maxdig = xd;
+            hno[slot] = ntotal; ntotal += (xd + 1) >> 1;
+            hdo[slot] = dtotal; dtotal += (dd + 1) >> 1;
+        }
+    }
+    /* the memory class works on five buffers of the widest operand plus two digits; the register class shifts through 258 */
+    const int64_t wcap = (((int64_t) maxdig + 2 > 264 ? (int64_t) maxdig + 2 : 264) + 1) & ~(int64_t) 1, per_wave = 8 + 5 * wcap;
+    if (wcap > (1 << 28)) { free(hno); free(hdo); return SLIP_HIP_OUT_OF_MEMORY; }
+#ifndef SLIP_EMULATE
+    /* a wave takes `chunk` entries per round: few entries are spread one to a wave, many fill the lanes of 4096 waves */
+    const int64_t waves_per_block = 4;
+    int64_t chunk = (ne + 4095) / 4096;
+    if (chunk > 64) chunk = 64;
+    int64_t blocks = (ne + chunk * waves_per_block - 1) / (chunk * waves_per_block);
+    if (blocks > 1024) blocks = 1024;
+    const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * per_wave * 4);      /* at most 256 MiB of scratch */
+    if (blocks > fit) blocks = fit;
+    if (blocks < 1) blocks = 1;
+#else
+    const int64_t blocks = 2, waves_per_block = 2, chunk = 5;
+#endif
+    int32_t *dnl = NULL, *ddl = NULL; int64_t *dno = NULL, *ddo = NULL; uint64_t *dnv = NULL, *ddv = NULL;
+    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
+    hipEvent_t ev0 = NULL, ev1 = NULL;
+    int rc = 0;
+    A_(dev_alloc(&dnl, ne)); A_(dev_alloc(&ddl, ne)); A_(dev_alloc(&dno, ne)); A_(dev_alloc(&ddo, ne));
+    A_(dev_alloc(&dnv, ntotal)); A_(dev_alloc(&ddv, dtotal));
+    A_(dev_alloc(&dscr, blocks * waves_per_block * per_wave)); A_(dev_alloc(&dpaths, 4));
+    UP_(dno, hno, (size_t) ne * 8); UP_(ddo, hdo, (size_t) ne * 8);
+    HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
+    HIP_(hipEventCreate(&ev0)); HIP_(hipEventCreate(&ev1));
+    if (!rc) {
+        SlipReduceArgs A; memset(&A, 0, sizeof A);
+        A.n = n; A.nrhs = nrhs; A.xlen = dxlen; A.xoff = dxoff; A.xlimbs = dxlimbs; A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
+        A.oidx = doidx; A.flip = flip; A.chunk = (int32_t) chunk; A.numlen = dnl; A.denlen = ddl; A.numoff = dno; A.denoff = ddo;
+        A.numlimbs = dnv; A.denlimbs = ddv; A.scratch = dscr; A.wcap = (int32_t) wcap; A.paths = dpaths;
+        HIP_(hipEventRecord(ev0, stream));
+#ifndef SLIP_EMULATE
+        if (!rc) {
+            hipLaunchKernelGGL(slip_reduce_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
+            HIP_(hipGetLastError());
+        }
+#else
+        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_reduce_body(A); }, 256 * 1024, 1);
+#endif
+        HIP_(hipEventRecord(ev1, stream)); HIP_(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIP_(hipEventElapsedTime(&ms, ev0, ev1));
+        if (ms_out) *ms_out = ms;
+    }
+    DOWN_(hpaths, dpaths, 32);
+    if (!rc && paths_out) for (int t = 0; t < 4; t++) paths_out[t] = (int64_t) hpaths[t];
+    int32_t *nl = NULL, *dl = NULL; uint64_t *nv = NULL, *dv = NULL; int64_t nn = 0, dn = 0;
+    A_(pack_download(ne, dnl, dno, dnv, 0, &nl, &nv, &nn, stream));
+    A_(pack_download(ne, ddl, ddo, ddv, 1, &dl, &dv, &dn, stream));
+    if (!rc) {
+        *numlen_out = nl; *numlimbs_out = nv; *num_limbs_out = nn; *denlen_out = dl; *denlimbs_out = dv; *den_limbs_out = dn;
+        nl = dl = NULL; nv = dv = NULL;
+    }
+    free(nl); free(dl); free(nv); free(dv); free(hno); free(hdo);
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    dev_free(dnl); dev_free(ddl); dev_free(dno); dev_free(ddo); dev_free(dnv); dev_free(ddv); dev_free(dscr); dev_free(dpaths);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_solve_rational(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                              int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
+                                              int32_t **numlen_out, uint64_t **numlimbs_out, int64_t *num_limbs_out,
+                                              int32_t **denlen_out, uint64_t **denlimbs_out, int64_t *den_limbs_out, void *stream_v)
+{
+    if (!numlen_out || !numlimbs_out || !num_limbs_out || !denlen_out || !denlimbs_out || !den_limbs_out) return SLIP_HIP_INCORRECT_INPUT;
+    *numlen_out = *denlen_out = NULL; *numlimbs_out = *denlimbs_out = NULL; *num_limbs_out = *den_limbs_out = 0;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipScaledSol s;
+    TRY_(solve_scaled(f, transpose, nrhs, blen, blimbs, snlen, snlimbs, sdlen, sdlimbs, stream, &s));
+    const int32_t n = f->n;
+    const int64_t ne = (int64_t) n * nrhs;
+    /* the numerators' digit counts (4 bytes an entry) and q size the slots; no limb comes down before the result is packed */
+    int32_t *hx = (int32_t *) malloc((size_t) ne * 4), *hd = (int32_t *) malloc((size_t) nrhs * 4), *hoidx = (int32_t *) malloc((size_t) n * 4);
+    int rc = !hx || !hd || !hoidx ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    DOWN_(hx, s.nlen, (size_t) ne * 4); DOWN_(hoidx, s.doidx, (size_t) n * 4);
+    if (!rc) for (int32_t c = 0; c < nrhs; c++) hd[c] = s.ddig;
+    f->torational_ms = 0; memset(f->torational_paths, 0, sizeof f->torational_paths);
+    A_(reduce_core(n, nrhs, s.nlen, s.noff, s.nlimbs, hx, s.ddlen, s.ddoff, s.dden, hd, hoidx, s.doidx, s.flip,
+                   numlen_out, numlimbs_out, num_limbs_out, denlen_out, denlimbs_out, den_limbs_out, stream,
+                   &f->torational_ms, f->torational_paths));
+    free(hx); free(hd); free(hoidx);
+    scaled_free(&s);
+    return rc;
+}
+
+extern "C" double slip_hip_factor_to_rational_ms(const slip_hip_factor *f) { return f ? f->torational_ms : 0.0; }
+extern "C" int slip_hip_factor_to_rational_paths(const slip_hip_factor *f, int64_t out[4])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->torational_paths, sizeof f->torational_paths);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_solution_to_rational(int32_t n, int32_t nrhs, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                             const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                             int32_t **numlen_out, uint64_t **numlimbs_out, int64_t *num_limbs_out,
+                                             int32_t **denlen_out, uint64_t **denlimbs_out, int64_t *den_limbs_out, void *stream_v)
+{
+    if (n <= 0 || nrhs < 1 || !xlen || !xlimbs || !dlen || !dlimbs) return SLIP_HIP_INCORRECT_INPUT;
+    if (!numlen_out || !numlimbs_out || !num_limbs_out || !denlen_out || !denlimbs_out || !den_limbs_out) return SLIP_HIP_INCORRECT_INPUT;
+    *numlen_out = *denlen_out = NULL; *numlimbs_out = *denlimbs_out = NULL; *num_limbs_out = *den_limbs_out = 0;
+    TRY_(need_device());
+    const int64_t ne = (int64_t) n * nrhs;
+    SlipSlab xs, ds;
+    memset(&ds, 0, sizeof ds);
+    int rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
+    if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
+    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no number */
+    int32_t *dxl = NULL, *ddl = NULL; int64_t *dxo = NULL, *ddo = NULL; uint64_t *dxv = NULL, *ddv = NULL;
+    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total));
+    A_(dev_alloc(&ddl, nrhs)); A_(dev_alloc(&ddo, nrhs)); A_(dev_alloc(&ddv, ds.total));
+    UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
+    UP_(ddl, ds.dig, (size_t) nrhs * 4); UP_(ddo, ds.off, (size_t) nrhs * 8); UP_(ddv, dlimbs, (size_t) ds.total * 8);
+    memset(slip_rational_paths_last, 0, sizeof slip_rational_paths_last);
+    A_(reduce_core(n, nrhs, dxl, dxo, dxv, xs.dig, ddl, ddo, ddv, ds.dig, NULL, NULL, 0,
+                   numlen_out, numlimbs_out, num_limbs_out, denlen_out, denlimbs_out, den_limbs_out, (hipStream_t) stream_v,
+                   NULL, slip_rational_paths_last));
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
+    slab_free(&xs); slab_free(&ds);
+    return rc;
+}
+
+/* the path counts of this thread's last slip_hip_solution_to_rational, as slip_hip_factor_to_rational_paths lays them out */
+extern "C" int slip_hip_solution_to_rational_paths(int64_t out[4])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_rational_paths_last, sizeof slip_rational_paths_last);
+    return SLIP_HIP_OK;
 }
 
 /* ---- exact solution check (SLIP_check_solution.c:31-113 as one integer test; kernel: slip_check_kernel) ---- */

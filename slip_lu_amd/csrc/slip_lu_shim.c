@@ -280,6 +280,13 @@ done:
  * nothing else -- no L, U, rho or numerator is downloaded, no mpz_t is built.  x_doub[i][j] (allocated
  * by the caller, as for the reference) = entry i of the solution of right-hand side j.
  * ------------------------------------------------------------------------------------------------ */
+/* a status of the library as the reference's */
+static SLIP_info solve_status(int rc)
+{
+    return rc == SLIP_HIP_OK ? SLIP_OK : rc == SLIP_HIP_SINGULAR ? SLIP_SINGULAR
+         : rc == SLIP_HIP_INCORRECT_INPUT ? SLIP_INCORRECT_INPUT : SLIP_OUT_OF_MEMORY;
+}
+
 /* *len, *limbs (malloc'ed) = the limb slab of z */
 static int mpz_to_limbs(const mpz_t z, int32_t *len, uint64_t **limbs)
 {
@@ -292,46 +299,99 @@ static int mpz_to_limbs(const mpz_t z, int32_t *len, uint64_t **limbs)
     return 0;
 }
 
+/* what SLIP_hip_solve_double and SLIP_hip_solve_mpq share: A factorised on the device (handle *f), b as a limb slab and the
+ * scale A->scale / b->scale as two limb runs, a part that is 1 or 0 left out (SLIP_scale_x.c:29-31, :43-45).  The caller
+ * destroys *f and frees the four arrays whatever comes back. */
+static SLIP_info factor_for_solve(SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option, slip_hip_factor **f,
+                                  int32_t **blen, uint64_t **blimbs, int32_t *snlen, uint64_t **snl, int32_t *sdlen, uint64_t **sdl)
+{
+    const int32_t n = A->n, nrhs = b->n;
+    SLIP_info ret = SLIP_OUT_OF_MEMORY;
+    int64_t *Ap = NULL; int32_t *Alen = NULL;
+    uint64_t *Alimbs = NULL;
+    slip_hip_options opt;
+    mpz_t sn, sd;
+    int rc;
+    mpz_init_set_ui(sn, 1); mpz_init_set_ui(sd, 1);
+    if (mpq_sgn(A->scale) != 0 && mpq_cmp_ui(A->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_numref(A->scale)); mpz_mul(sd, sd, mpq_denref(A->scale)); }
+    if (mpq_sgn(b->scale) != 0 && mpq_cmp_ui(b->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_denref(b->scale)); mpz_mul(sd, sd, mpq_numref(b->scale)); }
+    if (mpz_to_limbs(sn, snlen, snl) || mpz_to_limbs(sd, sdlen, sdl)) goto done;
+    if (matrix_to_slab(A, n, &Ap, &Alen, &Alimbs) || dense_to_slab(b, n, nrhs, blen, blimbs)) goto done;
+    slip_hip_default_options(&opt);
+    opt.pivot = (int32_t) option->pivot;
+    opt.tol = option->tol;
+    opt.lnz_hint = S->lnz; opt.unz_hint = S->unz;
+    rc = slip_hip_factor_create(f, n, Ap, A->i, Alen, Alimbs, S->q, &opt);
+    if (rc == SLIP_HIP_OK) rc = slip_hip_factor_run(*f, 0, NULL);
+    ret = solve_status(rc);
+done:
+    mpz_clear(sn); mpz_clear(sd);
+    free(Ap); free(Alen); free(Alimbs);
+    return ret;
+}
+
 SLIP_info SLIP_hip_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
 {
     if (!x_doub || !A || !A->p || !A->i || !A->x || !S || !S->q || !b || !b->x || !option)
         return SLIP_INCORRECT_INPUT;                      /* SLIP_solve_double.c:53-57 */
     const int32_t n = A->n, nrhs = b->n;
     if (n <= 0 || nrhs <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
-    SLIP_info ret = SLIP_OUT_OF_MEMORY;
     slip_hip_factor *f = NULL;
-    int64_t *Ap = NULL; int32_t *Alen = NULL, *blen = NULL, snlen = 0, sdlen = 0;
-    uint64_t *Alimbs = NULL, *blimbs = NULL, *snl = NULL, *sdl = NULL;
+    int32_t *blen = NULL, snlen = 0, sdlen = 0;
+    uint64_t *blimbs = NULL, *snl = NULL, *sdl = NULL;
     double *xd = (double *) malloc((size_t) n * nrhs * sizeof(double));
-    slip_hip_options opt;
-    mpz_t sn, sd;
-    int rc;
-    /* scale = A->scale / b->scale, a part that is 1 or 0 left out (SLIP_scale_x.c:29-31, :43-45) */
-    mpz_init_set_ui(sn, 1); mpz_init_set_ui(sd, 1);
-    if (mpq_sgn(A->scale) != 0 && mpq_cmp_ui(A->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_numref(A->scale)); mpz_mul(sd, sd, mpq_denref(A->scale)); }
-    if (mpq_sgn(b->scale) != 0 && mpq_cmp_ui(b->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_denref(b->scale)); mpz_mul(sd, sd, mpq_numref(b->scale)); }
-    if (!xd || mpz_to_limbs(sn, &snlen, &snl) || mpz_to_limbs(sd, &sdlen, &sdl)) goto done;
-    if (matrix_to_slab(A, n, &Ap, &Alen, &Alimbs) || dense_to_slab(b, n, nrhs, &blen, &blimbs)) goto done;
-    slip_hip_default_options(&opt);
-    opt.pivot = (int32_t) option->pivot;
-    opt.tol = option->tol;
-    opt.lnz_hint = S->lnz; opt.unz_hint = S->unz;
-    rc = slip_hip_factor_create(&f, n, Ap, A->i, Alen, Alimbs, S->q, &opt);
-    if (rc == SLIP_HIP_OK) rc = slip_hip_factor_run(f, 0, NULL);
-    if (rc == SLIP_HIP_OK) rc = slip_hip_factor_solve_double(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl, xd, NULL);
-    if (rc != SLIP_HIP_OK) {
-        ret = rc == SLIP_HIP_SINGULAR ? SLIP_SINGULAR
-            : rc == SLIP_HIP_INCORRECT_INPUT ? SLIP_INCORRECT_INPUT : SLIP_OUT_OF_MEMORY;
-        goto done;
-    }
-    for (int32_t i = 0; i < n; i++)
-        for (int32_t j = 0; j < nrhs; j++) x_doub[i][j] = xd[(int64_t) j * n + i];
-    ret = SLIP_OK;
-done:
+    SLIP_info ret = xd ? factor_for_solve(A, S, b, option, &f, &blen, &blimbs, &snlen, &snl, &sdlen, &sdl) : SLIP_OUT_OF_MEMORY;
+    if (ret == SLIP_OK) ret = solve_status(slip_hip_factor_solve_double(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl, xd, NULL));
+    if (ret == SLIP_OK)
+        for (int32_t i = 0; i < n; i++)
+            for (int32_t j = 0; j < nrhs; j++) x_doub[i][j] = xd[(int64_t) j * n + i];
     if (f) slip_hip_factor_destroy(f);
-    mpz_clear(sn); mpz_clear(sd);
-    free(xd); free(Ap); free(Alen); free(Alimbs); free(blen); free(blimbs); free(snl); free(sdl);
+    free(xd); free(blen); free(blimbs); free(snl); free(sdl);
     return ret;
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * SLIP_solve_mpq (SLIP_LU/Include/SLIP_LU.h, SLIP_LU/Source/SLIP_solve_mpq.c:41-97) on the GPU: factorise,
+ * substitute, divide by det (slip_array_div.c:36-49), permute (SLIP_permute_x) and scale (SLIP_scale_x), every
+ * fraction in GMP's canonical form, without leaving the device: slip_hip_factor_solve_rational returns the
+ * reduced numerators and denominators as two limb slabs and nothing else -- no L, U, rho or unreduced numerator
+ * is downloaded.  The limbs are copied into mpq_numref / mpq_denref of x_mpq[i][j] (entry i of the solution of
+ * right-hand side j); no GMP arithmetic runs per entry.  x_mpq arrives from SLIP_create_mpq_mat (initialised),
+ * as for SLIP_hip_LU_solve.
+ * ------------------------------------------------------------------------------------------------ */
+SLIP_info SLIP_hip_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
+{
+    if (!x_mpq || !A || !A->p || !A->i || !A->x || !S || !S->q || !b || !b->x || !option)
+        return SLIP_INCORRECT_INPUT;                      /* SLIP_solve_mpq.c:51-55 */
+    const int32_t n = A->n, nrhs = b->n;
+    if (n <= 0 || nrhs <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
+    slip_hip_factor *f = NULL;
+    int32_t *blen = NULL, snlen = 0, sdlen = 0, *numlen = NULL, *denlen = NULL;
+    uint64_t *blimbs = NULL, *snl = NULL, *sdl = NULL, *numl = NULL, *denl = NULL;
+    int64_t nnl = 0, dnl = 0;
+    SLIP_info ret = factor_for_solve(A, S, b, option, &f, &blen, &blimbs, &snlen, &snl, &sdlen, &sdl);
+    if (ret == SLIP_OK)
+        ret = solve_status(slip_hip_factor_solve_rational(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl,
+                                                          &numlen, &numl, &nnl, &denlen, &denl, &dnl, NULL));
+    if (ret == SLIP_OK) {
+        int64_t on = 0, od = 0;
+        for (int32_t j = 0; j < nrhs; j++)
+            for (int32_t i = 0; i < n; i++) {
+                const int32_t ln = numlen[(int64_t) j * n + i], ld = denlen[(int64_t) j * n + i];
+                set_from_limbs(mpq_numref(x_mpq[i][j]), ln, numl + on);
+                set_from_limbs(mpq_denref(x_mpq[i][j]), ld, denl + od);
+                on += ln < 0 ? -ln : ln; od += ld;
+            }
+    }
+    if (f) slip_hip_factor_destroy(f);
+    slip_hip_free(numlen); slip_hip_free(numl); slip_hip_free(denlen); slip_hip_free(denl);
+    free(blen); free(blimbs); free(snl); free(sdl);
+    return ret;
+}
+
+SLIP_info SLIP_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
+{
+    return SLIP_hip_solve_mpq(x_mpq, A, S, b, option);
 }
 
 SLIP_info SLIP_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
