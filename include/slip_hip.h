@@ -81,6 +81,7 @@ typedef struct slip_hip_info {
     int32_t farm_jobs, farm_items, batch_commits;   /* update queues opened to helpers; items helpers ran (diagnostic); columns the committer committed side by side */
     int32_t engine_commits, engine_sources; /* columns committed by the committer's chain engine from FULL packages; late sources it applied */
     int32_t retractions, reexports;        /* packages a worker took back because a source arrived; packages exported again */
+    int64_t raw_fills;                     /* rows filled in as -a_j * L(i,j) from a source entry no earlier source had touched: no division (diagnostic; factorisation and the solves' forward sweeps) */
 } slip_hip_info;
 
 typedef struct slip_hip_factor slip_hip_factor;

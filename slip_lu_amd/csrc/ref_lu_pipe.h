@@ -90,6 +90,7 @@ typedef struct SlipState {
     unsigned long long c_upd, c_read, c_write, c_src, c_streamed, c_maxdig, c_macs, c_short, c_farm;   /* c_farm: queues opened to helpers (low word), items helpers ran (high word); c_short: columns committed by the short chain (high word: by the committer) */
     unsigned long long c_eng, c_retract;            /* c_eng: columns committed by the committer's chain engine (low word), late sources it applied (high word); c_retract: packages retracted (low), exported again (high) */
     unsigned long long c_batch;                     /* columns the committer committed side by side (its run of candidates-only columns) */
+    unsigned long long c_raw;                       /* rows filled in straight from an untouched source entry (slip_fill_raw; diagnostic) */
     unsigned long long prof[24];                    /* SLIP_PROFILE builds only */
 } SlipState;
 
@@ -226,6 +227,8 @@ enum { SV_ERR = 0, SV_CNT0 = 1 /* 3 rotating work counters */, SV_MAXDIG = 4, SV
        SV_LISTN = 6, SV_TMP = 7,
        SV_LNZ = 8 /* int64 slots from here */, SV_LNL = 10, SV_UNZ = 12, SV_UNL = 14,
        SV_LALLOC = 16 /* limbs of the L slab handed out to this column's direct rows */, SV_LEXACT = 18,
+       SV_RAWN = 20 /* rows of this column (this right-hand side) filled in from raw sources (slip_fill_raw; zeroed at its start) */,
+       SV_RAWA = 21 /* 2 words: the raw value of the source being applied, or whose queue is pending */, SV_RAWS = 23 /* its sign; 0: the source is not raw */,
        SV_NROWS = 24 /* rows discovered so far (length of rlist) */, SV_K = 25, SV_TAG = 26, SV_ABORT = 27,
        SV_TMP2 = 28, SV_F2 = 29 /* ready frontier as this worker knows it */, SV_TMP3 = 30, SV_ACNT = 31 /* class-A rows of the early commit (zeroed at column start) */,
        SV_EPR = 32, SV_EPP = 33, SV_EST = 34 /* early commit: pivot row, its position, status (written by wave 0) */,
@@ -871,6 +874,97 @@ SLIP_DEV int slip_history_wave(const SlipParams &P, int r, int pm, int pd, dig_t
     return slip_store_x(P, r, b2, W, sign * slip_sgn(d.len), xr.h, xr.tag);
 }
 
+/* Fill-in from an UNTOUCHED source entry.  The sweep finalises the source first (slip_REF_triangular_solve.c:139-149):
+ * x[j] <- x[j] * rho[jn-1] / rho[h[j]].  An entry no earlier source has updated (h[j] == -1, jn >= 1) is still a_j, the entry
+ * of A (or of the right-hand side) as scattered, so its final value is a_j * rho[jn-1]; and for a row that is still zero the
+ * update (:175-196) is x[i] <- -L_m * x[j] / rho[jn-1] = -a_j * L_m: one short-by-long product, no product with rho, no
+ * division, no inverse.  Every division of the algorithm is exact, so these are the digits the general path stores.
+ * Rule: the raw value travels when it fits ONE limb (|len| <= 2 digits); a wider untouched entry (multi-limb input) takes the
+ * general path.  jn == 0 has no division on the general path either and is not treated here. */
+struct SlipRaw { uint64_t a; int32_t s; };          /* |a_j| and its sign; s == 0: the source is not raw */
+SLIP_DEV SlipRaw slip_raw_none(void) { SlipRaw r; r.a = 0; r.s = 0; return r; }
+/* The sweep keeps the raw value of its current source in the workgroup's LDS words (SV_RAWA, SV_RAWS), not in registers:
+ * the worker's register allocation is at its limit.  Lane 0 of EVERY wave writes the same words when the source is taken up
+ * (every thread holds them; sixty-four lanes storing to one LDS address would be sixty-four passes) and the wave reads them
+ * after its own write; the next source is taken up behind a
+ * workgroup barrier and behind the drain of this one's queue. */
+SLIP_DEV void slip_raw_put(volatile int32_t *sv, uint64_t a, int s)
+{
+    if (slip_lane() == 0) { sv[SV_RAWA] = (int32_t)(uint32_t) a; sv[SV_RAWA + 1] = (int32_t)(uint32_t)(a >> 32); sv[SV_RAWS] = s; }
+    /* LDS only: a wave's LDS operations execute in order, and the full slip_wave_sync() would wait for the global loads in
+     * flight as well (the caller puts this behind the step's loads) */
+    slip_wave_sync_lds();
+}
+SLIP_DEV SlipRaw slip_raw_get(volatile int32_t *sv)
+{
+    SlipRaw r; r.s = slip_uniform_i32(sv[SV_RAWS]);
+    r.a = (uint64_t) slip_uniform((uint32_t) sv[SV_RAWA]) | ((uint64_t) slip_uniform((uint32_t) sv[SV_RAWA + 1]) << 32);
+    return r;
+}
+
+template <int D> SLIP_DEV int slip_fill_raw_reg(const SlipParams &P, int i, int jn, const SlipEnt &le, const SlipRaw &raw, int tag)
+{
+    const WR<D> Lm = wr_load_s<D>((const dig_t *)(P.Llimbs + le.off), slip_abs(le.len));
+    WR<D> Y;
+    if (!(raw.a >> 32)) Y = wr_mul_digit<D>((uint32_t) raw.a, Lm);
+    else {
+        WR<D> A = wr_zero<D>();
+        if (slip_lane() == 0) A.d[0] = (uint32_t) raw.a;
+        if (slip_lane() == 1) A.d[0] = (uint32_t)(raw.a >> 32);
+        Y = wr_mul<D>(A, 2, Lm);
+    }
+    return slip_store_x_reg<D>(P, i, Y, -raw.s * slip_sgn(le.len), jn, tag);
+}
+
+/* x[i] <- -a_j * L_m with history jn, one wavefront; the only width checked is the result's (<= xcap).
+ * The sweep finishes L entries of up to SLIP_FILL_LANE_LIMBS limbs (128 digits) in the lane (slip_fill_raw_lane), so what comes
+ * here is longer than that: register classes 3 and 4, then memory.  A shorter entry comes only when its lane product's
+ * 2 * (limbs + 1) digits might not fit the row (xcap within two digits of the value); it is rare and takes class 3 too. */
+SLIP_DEV int slip_fill_raw(const SlipParams &P, int i, int jn, const SlipEnt &le, const SlipRaw &raw, int tag, dig_t *b0, dig_t *b1)
+{
+    const int ll = slip_abs(le.len), la = (raw.a >> 32) ? 2 : 1, W = ll + la;
+    if (W <= 192) return slip_fill_raw_reg<3>(P, i, jn, le, raw, tag);          /* (the store checks the product's own width) */
+    if (W <= 256) return slip_fill_raw_reg<4>(P, i, jn, le, raw, tag);
+    /* wide L entries (see slip_ensure_inv): through scratch; the product has W or W - 1 digits and wcap >= xcap + 2.  The width
+     * is checked BEFORE the product, from the bound bits(L_m) + bits(a_j), which can be one bit more than the product has: a
+     * value that ends exactly at the row's last bit may ask for a regrow it did not need (same digits afterwards). */
+    if (((le.bits + 64 - slip_clz64(raw.a) + 31) >> 5) > P.xcap || W > P.wcap) return 1;
+    slip_agent_acquire();
+    if (slip_lane() < 2) b1[slip_lane()] = slip_lane() ? (uint32_t)(raw.a >> 32) : (uint32_t) raw.a;
+    slip_wave_sync();
+    wb_mul_lo(b0, (const dig_t *)(P.Llimbs + le.off), ll, b1, la, W);
+    return slip_store_x(P, i, b0, W, -raw.s * slip_sgn(le.len), jn, tag);
+}
+
+/* The same in ONE LANE, for L entries of at most SLIP_FILL_LANE_LIMBS limbs: the lane that streams the entry multiplies it limb
+ * by limb into the row (64 x 64 -> 128 bits and a carry).  As a wave item the product is two dependent round trips to memory
+ * and a store, about 2.7 us whatever its length, and a heavy column of the C4 window queues 550-700 of them behind one source
+ * (185 us on the worker's own eight waves); here every lane of the streaming pass has its row in flight at once, eight limbs
+ * per round of loads.  The caller has checked that 2 * (limbs + 1) digits fit the row. */
+#define SLIP_FILL_LANE_LIMBS 64
+SLIP_DEVN void slip_fill_raw_lane(const SlipParams *Pg, int i, int64_t off, int32_t llen, uint64_t a, int sign, int jn, int tag)
+{
+    const SlipParams &P = *Pg;
+    const uint64_t *src = P.Llimbs + off;
+    uint64_t *dst = (uint64_t *)(P.xd + (int64_t) i * P.xcap);
+    const int nl = slip_limbs(llen);
+    uint64_t carry = 0, top = 0;
+    int t = 0;
+    for (; t + 8 <= nl; t += 8) {
+        uint64_t v[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) v[q] = slip_ld_u64(src + t + q);
+#pragma unroll
+        for (int q = 0; q < 8; q++) { const slip_u128 p = (slip_u128) v[q] * a + carry; top = (uint64_t) p; dst[t + q] = top; carry = (uint64_t)(p >> 64); }
+    }
+    for (; t < nl; t++) { const slip_u128 p = (slip_u128) slip_ld_u64(src + t) * a + carry; top = (uint64_t) p; dst[t] = top; carry = (uint64_t)(p >> 64); }
+    int outl = nl;
+    if (carry) { dst[nl] = carry; top = carry; outl = nl + 1; }
+    SlipRow r; r.bits = 64 * outl - slip_clz64(top); r.len = (r.bits + 31) >> 5; r.h = jn; r.tag = tag;      /* (the top limb of a product of nonzero factors is not zero) */
+    if (sign < 0) r.len = -r.len;
+    P.xrow[i] = r;
+}
+
 /* One IPGE update (slip_REF_triangular_solve.c:156-241) of target row i by source row j
  * (pivot position jn) through the L entry m, one wavefront, everything modulo B^W:
  *     x[i] <- ( hist(x[i]) * rho[jn] - L_m * x[j] ) / rho[jn-1]                          */
@@ -958,11 +1052,13 @@ template <int D> SLIP_DEV int slip_ipge_wave_reg(const SlipParams &P, int i, int
     return slip_store_x_reg<D>(P, i, T, sT, jn, xi.tag);
 }
 
-SLIP_DEV int slip_ipge_wave(const SlipParams &P, int i, int j, int jn, int64_t m, dig_t *b0, dig_t *b1, dig_t *b2)
+SLIP_DEV int slip_ipge_wave(const SlipParams &P, int i, int j, int jn, int64_t m, const SlipRaw &raw, dig_t *b0, dig_t *b1, dig_t *b2)
 {
+    /* (every record is asked for before the first is looked at: one round trip to memory for all of them, on both paths) */
     const SlipRow xi = P.xrow[i], xj = P.xrow[j];
     const SlipEnt le = slip_ld_ent(&P.Le[m]);
     const SlipPiv R = slip_ld_piv(P.piv.at(jn));
+    if (raw.s && xi.len == 0) return slip_fill_raw(P, i, jn, le, raw, xi.tag, b0, b1);      /* a row with a value needs the finalised x[j]: below */
     const int lx = slip_abs(xi.len), sx = slip_sgn(xi.len);
     const dig_t *X = P.xd + (int64_t) i * P.xcap;
     const int lr = slip_abs(R.len), sr = slip_sgn(R.len);
@@ -1238,10 +1334,10 @@ SLIP_DEV int slip_submul_wave(const SlipParams &P, int i, int j, int64_t m, dig_
 
 /* kind 1: IPGE updates of source (j, jn), items = (m - m0, i) pairs; kind 2: history rows of column k (division by rho[h]);
  * kind 4: x * rho[k-1]; kind 5: back-substitution updates (m - m0, i) of source j */
-SLIP_DEV int slip_run_item(const SlipParams &P, int kind, int j, int jn, int k, int64_t m0, uint32_t ia, uint32_t ib,
+SLIP_DEV int slip_run_item(const SlipParams &P, int kind, int j, int jn, int k, int64_t m0, uint32_t ia, uint32_t ib, const SlipRaw &raw,
                            dig_t *b0, dig_t *b1, dig_t *b2)
 {
-    if (kind == 1) return slip_ipge_wave(P, (int) ib, j, jn, m0 + (int64_t) ia, b0, b1, b2);
+    if (kind == 1) return slip_ipge_wave(P, (int) ib, j, jn, m0 + (int64_t) ia, raw, b0, b1, b2);
     if (kind == 5) return slip_submul_wave(P, (int) ib, j, m0 + (int64_t) ia, b0, b1, b2);
     const int r = (int) ia;
     if (kind == 4) return slip_history_wave(P, r, k - 1, -1, b0, b1, b2, SLIP_KEEP_H);      /* x * rho[k-1] */
@@ -1250,10 +1346,11 @@ SLIP_DEV int slip_run_item(const SlipParams &P, int kind, int j, int jn, int k, 
 
 /* ---- out-of-line entry points (one copy each; the parameters are the workgroup's LDS copy; items travel by value:
  * (m - m0, i) for kinds 1 and 5, (row, -) otherwise) ---- */
-SLIP_DEVN int slip_run_item_out(const SlipParams *Pg, int kind, int j, int jn, int k, int64_t m0, uint32_t ia, uint32_t ib,
+SLIP_DEVN int slip_run_item_out(const SlipParams *Pg, int kind, int j, int jn, int k, int64_t m0, uint32_t ia, uint32_t ib, uint64_t raw_a, int raw_s,
                                 dig_t *b0, dig_t *b1, dig_t *b2)
 {
-    return slip_run_item(*Pg, kind, j, jn, k, m0, ia, ib, b0, b1, b2);
+    SlipRaw raw; raw.a = raw_a; raw.s = raw_s;
+    return slip_run_item(*Pg, kind, j, jn, k, m0, ia, ib, raw, b0, b1, b2);
 }
 SLIP_DEVN int slip_history_wave_out(const SlipParams *Pg, int r, int pm, int pd, dig_t *b0, dig_t *b1, dig_t *b2)
 {
@@ -1286,7 +1383,7 @@ SLIP_DEVN int slip_tol_compare_out(uint64_t tol_m, int te, const dig_t *num, int
  * factorisation while most workers wait for their turn.  The owner publishes such a queue as a JOB in its slot of P.jobs;
  * workers that are waiting take items from it with an atomic counter and run them on the OWNER's private x rows.
  * Slot (words): 0 gate = open bit + 256 * helpers inside (atomics only); 2 kind, 3 j, 4 jn, 5 k, 6-7 m0, 8 items, 11 error;
- * 16 next item; 32.. the items.  Visibility: the owner writes its dirty lines back (agent release) before it opens the
+ * 12-13 the source's raw value, 14 its sign (SlipRaw; 0: none); 16 next item; 32.. the items.  Visibility: the owner writes its dirty lines back (agent release) before it opens the
  * gate; a helper invalidates (agent acquire) when it enters and writes back before it leaves; the owner closes the gate,
  * waits for the helpers to leave, writes back and invalidates.  Rows share cache lines: the L2s write back the bytes
  * they own. */
@@ -1317,7 +1414,7 @@ SLIP_DEVN int slip_tol_compare_out(uint64_t tol_m, int te, const dig_t *num, int
 #endif
 
 /* take items until none is left (all waves of the calling workgroup); items: the owner's list in LDS, or null = the job's copy */
-SLIP_DEV int slip_farm_items(const SlipParams &P, uint32_t *jb, int kind, int j, int jn, int k, int64_t m0, int nq, const uint32_t *wl,
+SLIP_DEV int slip_farm_items(const SlipParams &P, uint32_t *jb, int kind, int j, int jn, int k, int64_t m0, int nq, const uint32_t *wl, const SlipRaw &raw,
                              dig_t *b0, dig_t *b1, dig_t *b2)
 {
     int err = 0, cnt = 0;
@@ -1331,7 +1428,7 @@ SLIP_DEV int slip_farm_items(const SlipParams &P, uint32_t *jb, int kind, int j,
             if (wl) { it0 = wl[2 * t]; it1 = wl[2 * t + 1]; }
             else { it0 = slip_ld_u32(jb + 32 + 2 * t); it1 = slip_ld_u32(jb + 32 + 2 * t + 1); }
         } else { it0 = wl ? wl[t] : slip_ld_u32(jb + 32 + t); it1 = 0u; }
-        const int e = slip_run_item_out(&P, kind, j, jn, k, m0, it0, it1, b0, b1, b2);
+        const int e = slip_run_item_out(&P, kind, j, jn, k, m0, it0, it1, raw.a, raw.s, b0, b1, b2);
         if (e) err = e;
         cnt++;
     }
@@ -1408,6 +1505,7 @@ SLIP_DEV void slip_farm_help(const SlipParams &P, SlipState *st, uint32_t *lds, 
     const int kind = (int) slip_ld_u32(jb + 2), j = (int) slip_ld_u32(jb + 3), jn = (int) slip_ld_u32(jb + 4), k = (int) slip_ld_u32(jb + 5);
     const int64_t m0 = (int64_t) slip_ld_u64((const uint64_t *)(jb + 6));
     const int nq = (int) slip_ld_u32(jb + 8);
+    SlipRaw raw; raw.a = slip_ld_u64((const uint64_t *)(jb + 12)); raw.s = (int32_t) slip_ld_u32(jb + 14);
     /* the items work on the owner's private rows: this worker's parameter block points there for the duration */
     SlipParams &Pm = const_cast<SlipParams &>(P);
     SlipRow *my_xrow = P.xrow; uint32_t *my_xd = P.xd;
@@ -1415,7 +1513,7 @@ SLIP_DEV void slip_farm_help(const SlipParams &P, SlipState *st, uint32_t *lds, 
     Pm.xrow = my_xrow + (int64_t)(slot - P.worker) * P.priv_rows;
     Pm.xd = my_xd + (int64_t)(slot - P.worker) * P.priv_rows * P.xcap;
     slip_block_sync();
-    const int e = slip_farm_items(P, jb, kind, j, jn, k, m0, nq, (const uint32_t *) 0, b0, b1, b2);
+    const int e = slip_farm_items(P, jb, kind, j, jn, k, m0, nq, (const uint32_t *) 0, raw, b0, b1, b2);
     if (e && slip_lane() == 0) slip_st_u32(jb + 11, (uint32_t) e);
     slip_vm_drain();
     slip_block_sync();
@@ -1427,12 +1525,14 @@ SLIP_DEV void slip_farm_help(const SlipParams &P, SlipState *st, uint32_t *lds, 
 }
 
 /* drain a queue of wave-level items with this workgroup's waves; errors land in sv[SV_ERR].
+ * nfill (kind 1): how many of the items are rows that the source's raw value (SV_RAWA, SV_RAWS) fills in (slip_fill_raw).
  * Called by all threads after a workgroup barrier; returns after a workgroup barrier with every item done. */
 SLIP_DEV void slip_drain(const SlipParams &P, uint32_t *lds, int kind, int j, int jn, int k, int64_t m0, int nq,
-                         const uint32_t *wl, dig_t *b0, dig_t *b1, dig_t *b2)
+                         const uint32_t *wl, dig_t *b0, dig_t *b1, dig_t *b2, int nfill = 0)
 {
     const int lane = slip_lane(), wave = slip_wave(), nw = slip_nwaves();
     volatile int32_t *sv = (volatile int32_t *)(lds + SLIP_LDS_VARS);
+    const SlipRaw raw = kind == 1 ? slip_raw_get(sv) : slip_raw_none();
     /* (only a column whose turn is near: further away the worker has the time, and every helper costs its XCD an L2 write-back
      * and invalidate) */
     /* (a handful of items is worth opening too when each of them is huge: model6's columns have fewer than 16 rows of 200-364
@@ -1445,7 +1545,8 @@ SLIP_DEV void slip_drain(const SlipParams &P, uint32_t *lds, int kind, int j, in
         /* (kind 5, back substitution: the multiplier is x[j]; the solves have no frontier, every long queue is opened) */
         const int lr = kind == 5 ? slip_limbs(P.xrow[j].len) : slip_limbs(slip_ld_piv(P.piv.at(kind == 1 ? jn : k - 1)).len);
         /* the queue alone takes about nq * 8 lr^2 / waves cycles; the frontier moves a column every few microseconds */
-        const int64_t cost = (int64_t) nq * lr * lr;
+        /* (a row filled in from a raw source is one short-by-long product: linear in the limbs) */
+        const int64_t cost = (int64_t)(nq - nfill) * lr * lr + (int64_t) nfill * lr;
         if ((nq >= SLIP_FARM_MIN_ITEMS || lr >= SLIP_FARM_FEW_LIMBS) && cost >= (kind == 2 ? (int64_t) SLIP_FARM_KIND2_COST : (int64_t) SLIP_FARM_MIN_COST) && (kind == 2 || kind == 5 || !P.in_factor || SLIP_FARM_NEAR_DIV == 0 || (int64_t)(sv[SV_K] - sv[SV_F]) <= cost / ((int64_t) nw * (SLIP_FARM_NEAR_DIV ? SLIP_FARM_NEAR_DIV : 1)) + 2)) {
             /* a long queue of long updates: open it to the workers that are waiting */
             const int tid = slip_tid(), T = slip_nthreads();
@@ -1454,11 +1555,12 @@ SLIP_DEV void slip_drain(const SlipParams &P, uint32_t *lds, int kind, int j, in
             if (tid == 0) {
                 slip_st_u32(jb + 2, (uint32_t) kind); slip_st_u32(jb + 3, (uint32_t) j); slip_st_u32(jb + 4, (uint32_t) jn); slip_st_u32(jb + 5, (uint32_t) k);
                 slip_st_u64((uint64_t *)(jb + 6), (uint64_t) m0); slip_st_u32(jb + 8, (uint32_t) nq); slip_st_u32(jb + 9, slip_xcc_id()); slip_st_u32(jb + 11, 0u); slip_st_u32(jb + 16, 0u);
+                slip_st_u64((uint64_t *)(jb + 12), raw.a); slip_st_u32(jb + 14, (uint32_t) raw.s);
             }
             slip_vm_drain();
             slip_block_sync();
             if (tid == 0) { slip_agent_release(); slip_agent_add_i32((int32_t *) jb, 1); slip_st_i32(&P.st->farm_hint[P.worker & (SLIP_FARM_HINTS - 1)], kind != 2 ? P.worker + 1 : -(P.worker + 1)); slip_agent_add_u64(&P.st->c_farm, 1ull); }
-            const int e = slip_farm_items(P, jb, kind, j, jn, k, m0, nq, wl, b0, b1, b2);
+            const int e = slip_farm_items(P, jb, kind, j, jn, k, m0, nq, wl, raw, b0, b1, b2);
             if (e && lane == 0) sv[SV_ERR] = e;
             slip_vm_drain();
             slip_block_sync();
@@ -1483,7 +1585,7 @@ SLIP_DEV void slip_drain(const SlipParams &P, uint32_t *lds, int kind, int j, in
                 if (wave == nw - 1 && lane == 0 && (slip_ld_i64(&P.st->stop) >> 8) < (int64_t) sv[SV_K]) sv[SV_ABORT] = 1;
                 if ((int) slip_bcast0_u32((uint32_t) sv[SV_ABORT])) break;      /* one lane's view for the whole wave */
             }
-            const int e = slip_run_item_out(&P, kind, j, jn, k, m0, (kind == 1 || kind == 5) ? wl[2 * t] : wl[t], (kind == 1 || kind == 5) ? wl[2 * t + 1] : 0u, b0, b1, b2);
+            const int e = slip_run_item_out(&P, kind, j, jn, k, m0, (kind == 1 || kind == 5) ? wl[2 * t] : wl[t], (kind == 1 || kind == 5) ? wl[2 * t + 1] : 0u, raw.a, raw.s, b0, b1, b2);
             if (e && lane == 0) sv[SV_ERR] = e;
         }
     slip_block_sync();

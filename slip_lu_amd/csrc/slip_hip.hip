@@ -3207,6 +3207,7 @@ extern "C" int slip_hip_factor_info(const slip_hip_factor *f, slip_hip_info *o)
     o->farm_jobs = (int32_t)(uint32_t) h->c_farm; o->farm_items = (int32_t)(h->c_farm >> 32);
     o->engine_commits = (int32_t)(uint32_t) h->c_eng; o->engine_sources = (int32_t)(h->c_eng >> 32);
     o->retractions = (int32_t)(uint32_t) h->c_retract; o->reexports = (int32_t)(h->c_retract >> 32); o->batch_commits = (int32_t) h->c_batch;
+    o->raw_fills = (int64_t) h->c_raw;
     return SLIP_HIP_OK;
 }
 
