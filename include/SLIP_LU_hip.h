@@ -18,7 +18,9 @@
  *
  * SLIP_LU_solve (SLIP_LU.h:941-949) is served the same way (SLIP_hip_LU_solve below), and so is SLIP_solve_double of the
  * simple interface (SLIP_hip_solve_double below), which never leaves the device between the factorisation and the doubles,
- * and SLIP_solve_mpq (SLIP_hip_solve_mpq below), which brings back nothing but the reduced fractions.
+ * and SLIP_solve_mpq (SLIP_hip_solve_mpq below), which brings back nothing but the reduced fractions, and SLIP_solve_mpfr
+ * (SLIP_hip_solve_mpfr below; declared once mpfr.h is in scope: define SLIP_HAVE_MPFR or include mpfr.h / SLIP_LU.h first),
+ * which brings back nothing but the rounded mantissas.
  *
  * When the reference's SLIP_LU.h has been included first, this header only adds
  * the aliases; otherwise it declares layout-compatible mirrors of the four types
@@ -30,6 +32,9 @@
 
 #include <stdint.h>
 #include <gmp.h>
+#if defined(SLIP_HAVE_MPFR) && !defined(MPFR_VERSION)
+#include <mpfr.h>                /* SLIP_hip_solve_mpfr below: only where mpfr.h is available (the reference's header includes it) */
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -77,6 +82,10 @@ SLIP_info SLIP_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, SLIP
 SLIP_info SLIP_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
 
 SLIP_info SLIP_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
+
+#ifdef MPFR_VERSION
+SLIP_info SLIP_solve_mpfr(mpfr_t **x_mpfr, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
+#endif
 #endif
 
 SLIP_info SLIP_hip_LU_factorize(SLIP_sparse *L, SLIP_sparse *U, SLIP_sparse *A, SLIP_LU_analysis *S,
@@ -105,6 +114,19 @@ SLIP_info SLIP_hip_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysi
  * denominators cross back and are copied into the mpq_t limb by limb; no GMP arithmetic runs per entry.  Also exported under
  * the reference's own name. */
 SLIP_info SLIP_hip_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
+
+#ifdef MPFR_VERSION
+/* SLIP_solve_mpfr (SLIP_LU/Source/SLIP_solve_mpfr.c:40-104) on the GPU, with its prototype, argument checks (:52-56) and error
+ * codes: factorisation, substitution, SLIP_permute_x, SLIP_scale_x (as above) and SLIP_get_mpfr_soln (mpfr_set_q per entry,
+ * under option->SLIP_MPFR_ROUND) all run on the device (slip_hip_factor_solve_mpfr).  x_mpfr[i][j] (n rows of b->n mpfr_t,
+ * initialised by the caller -- SLIP_create_mpfr_mat gives every entry option->prec bits) receives entry i of the solution of
+ * right-hand side j: the exact rational rounded ONCE to the precision the entries carry, mpfr_get_prec(x_mpfr[0][0]), from 2
+ * to 65536 bits.  A difference from the reference: entries of differing precisions are SLIP_INCORRECT_INPUT (the reference
+ * rounds each entry to its own).  Only sign, exponent and mantissa limbs cross back; every mpfr_t is filled through MPFR's
+ * public interface (mpz_roinit_n, mpfr_set_z_2exp -- exact -- and mpfr_set_zero).  Also exported under the reference's own
+ * name.  Present in libslip_lu_hip.so when it was built where mpfr.h is available. */
+SLIP_info SLIP_hip_solve_mpfr(mpfr_t **x_mpfr, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option);
+#endif
 
 #ifdef __cplusplus
 }

@@ -282,6 +282,46 @@ int    slip_hip_factor_to_rational_paths(const slip_hip_factor *f, int64_t out[4
 /* the same four counts for the calling thread's last slip_hip_solution_to_rational */
 int    slip_hip_solution_to_rational_paths(int64_t out[4]);
 
+/* Solve to multi-precision floats: the tail of SLIP_solve_mpfr (SLIP_LU/Source/SLIP_solve_mpfr.c:82-104: SLIP_permute_x,
+ * SLIP_scale_x, SLIP_get_mpfr_soln, i.e. mpfr_set_q per entry) on the device, after the substitution of slip_hip_factor_solve
+ * (transpose = 0) or slip_hip_factor_solve_transpose (transpose != 0).
+ *
+ * Every result is what mpfr_set_q(x, N / D, rnd) leaves in an mpfr_t of `prec` bits, 2 <= prec <= 65536, with rnd one of
+ * MPFR_RNDN = 0 (nearest, ties to the even mantissa), MPFR_RNDZ = 1, MPFR_RNDU = 2, MPFR_RNDD = 3, MPFR_RNDA = 4: the ONE
+ * correct rounding of the exact rational (no gcd is taken; the scale goes in before it).  Per entry:
+ *   sign     int8:  0 for a zero (always +0: the sign is dropped, also under a negative scale and under RNDD), else +1 / -1;
+ *   exp      int64: MPFR's exponent e, |x| = 0.1... * 2^e, i.e. |x| = m * 2^(e - prec) with 2^(prec-1) <= m < 2^prec; 0 for a zero;
+ *   mant     ceil(prec / 64) limbs, least significant first, the mantissa left-aligned as in MPFR's own limb array: the top
+ *            bit of the top limb set, the bits below the prec-th zero; all zero for a zero;
+ *   ternary  int8: the sign of (rounded - exact): 0 when the result is exact.
+ * There is no overflow or underflow: MPFR's default exponent range cannot be reached by operands that fit in memory.
+ *
+ * slip_hip_factor_solve_mpfr: b, transpose, the scale parts and the statuses exactly as slip_hip_factor_solve_double takes and
+ * returns them (also the refusal of a plain call on a handle from slip_hip_factor_from_factors); entry c*n + j in its order.
+ * The caller allocates sign_out[nrhs*n], exp_out[nrhs*n], mant_out[nrhs*n*ceil(prec/64)] and ternary_out[nrhs*n] (or NULL);
+ * nothing else crosses back.  SLIP_HIP_INCORRECT_INPUT also for prec outside 2..65536 and for any other rnd (MPFR_RNDF = 5
+ * and MPFR_RNDNA = -1 among them).  slip_hip_factor_solve / _solve_transpose / _solve_double / _solve_rational afterwards
+ * return what they always did.
+ *
+ * slip_hip_solution_to_mpfr: no handle; the (x, d) form of slip_hip_solution_to_double with its capacities and refusals, the
+ * result in the order of the input.  It is the slab form of SLIP_get_mpfr_soln.
+ *
+ * No CPU fallback: without a device the result is SLIP_HIP_DEVICE_ERROR. */
+int slip_hip_factor_solve_mpfr(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                               int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
+                               int32_t prec, int32_t rnd, int8_t *sign_out, int64_t *exp_out, uint64_t *mant_out,
+                               int8_t *ternary_out, void *stream);
+int slip_hip_solution_to_mpfr(int32_t n, int32_t nrhs, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                              const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs, int32_t prec, int32_t rnd,
+                              int8_t *sign_out, int64_t *exp_out, uint64_t *mant_out, int8_t *ternary_out, void *stream);
+/* device ms of the conversion kernel of the last slip_hip_factor_solve_mpfr; out[4]: the entries of that call settled by the
+ * kernel's lane pass with both parts within 64 bits (prec <= 64 only), by the wave pass (a long division) with a denominator
+ * of at most 256 digits of 32 bits, by the wave pass with a wider one, and -- out[3] -- as zero */
+double slip_hip_factor_to_mpfr_ms(const slip_hip_factor *f);
+int    slip_hip_factor_to_mpfr_paths(const slip_hip_factor *f, int64_t out[4]);
+/* the same four counts for the calling thread's last slip_hip_solution_to_mpfr */
+int    slip_hip_solution_to_mpfr_paths(int64_t out[4]);
+
 /* Subtree farm (no counterpart in the reference, which has no parallelism): multiply the K committed
  * columns by per-column scales on the device -- L(:,k) and rho[k] by scale[k], an entry of U in the row whose pivot sits
  * at position p by scale[p] -- where scale[k] is the product of the pivots the OTHER independent blocks had produced when

@@ -41,7 +41,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_solve_double", "slip_hip_solution_to_double", "slip_hip_factor_to_double_ms",
            "slip_hip_factor_to_double_slow",
            "slip_hip_factor_solve_rational", "slip_hip_solution_to_rational", "slip_hip_factor_to_rational_ms",
-           "slip_hip_factor_to_rational_paths", "slip_hip_solution_to_rational_paths")
+           "slip_hip_factor_to_rational_paths", "slip_hip_solution_to_rational_paths",
+           "slip_hip_factor_solve_mpfr", "slip_hip_solution_to_mpfr", "slip_hip_factor_to_mpfr_ms",
+           "slip_hip_factor_to_mpfr_paths", "slip_hip_solution_to_mpfr_paths")
 
 _libs = {}
 
@@ -122,5 +124,16 @@ def load(path=None):
     lib.slip_hip_factor_to_rational_paths.restype = C.c_int
     lib.slip_hip_solution_to_rational_paths.argtypes = [vp]
     lib.slip_hip_solution_to_rational_paths.restype = C.c_int
+    lib.slip_hip_factor_solve_mpfr.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp,
+                                               C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    lib.slip_hip_factor_solve_mpfr.restype = C.c_int
+    lib.slip_hip_solution_to_mpfr.argtypes = [C.c_int32, C.c_int32, vp, vp, i64, vp, vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    lib.slip_hip_solution_to_mpfr.restype = C.c_int
+    lib.slip_hip_factor_to_mpfr_ms.argtypes = [vp]
+    lib.slip_hip_factor_to_mpfr_ms.restype = C.c_double
+    lib.slip_hip_factor_to_mpfr_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_to_mpfr_paths.restype = C.c_int
+    lib.slip_hip_solution_to_mpfr_paths.argtypes = [vp]
+    lib.slip_hip_solution_to_mpfr_paths.restype = C.c_int
     _libs[path] = lib
     return lib

@@ -142,6 +142,41 @@ def solution_to_rational_paths(lib_path=None):
     return [int(v) for v in out]
 
 
+def _mpfr_outputs(count, prec):
+    """the four arrays a conversion to multi-precision floats fills: sign, exp, mant[count, ceil(prec / 64)], ternary"""
+    nl = (max(int(prec), 1) + 63) // 64 if int(prec) <= 65536 else 1      # a refused prec allocates nothing large
+    return (np.zeros(max(count, 1), np.int8), np.zeros(max(count, 1), np.int64), np.zeros((max(count, 1), nl), np.uint64),
+            np.zeros(max(count, 1), np.int8))
+
+
+def solution_to_mpfr(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, prec=128, rnd=0, lib_path=None):
+    """Numerators over one nonzero denominator per right-hand side -> correctly rounded floats of `prec` bits on the device
+    (slip_hip_solution_to_mpfr): (sign, exp, mant, ternary) of n * nrhs entries in the order of the input, every entry what
+    mpfr_set_q leaves under the rounding mode rnd (MPFR_RNDN 0, RNDZ 1, RNDU 2, RNDD 3, RNDA 4): sign 0 / +1 / -1, MPFR's
+    exponent, the mantissa left-aligned in ceil(prec / 64) limbs (mant[t, -1] is the top limb), the ternary value."""
+    lib = _lib.load(lib_path)
+    n, nrhs = int(n), int(nrhs)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
+    if nrhs >= 1 and (xlen.size != n * nrhs or dlen.size != nrhs):
+        raise ValueError("solution_to_mpfr: xlen needs n*nrhs entries, dlen nrhs")
+    count = max(n, 0) * max(nrhs, 0)
+    sign, exp, mant, tern = _mpfr_outputs(count, prec)
+    rc = lib.slip_hip_solution_to_mpfr(n, nrhs, xlen.ctypes.data, xlimbs.ctypes.data, xcap, dlen.ctypes.data, dlimbs.ctypes.data,
+                                       dcap, int(prec), int(rnd), sign.ctypes.data, exp.ctypes.data, mant.ctypes.data,
+                                       tern.ctypes.data, None)
+    if rc:
+        raise SlipError(rc, "slip_hip_solution_to_mpfr")
+    return sign[:count], exp[:count], mant[:count], tern[:count]
+
+
+def solution_to_mpfr_paths(lib_path=None):
+    """entries of this thread's last solution_to_mpfr by the path that settled them, as Factorization.to_mpfr_paths"""
+    out = np.zeros(4, np.int64)
+    _lib.load(lib_path).slip_hip_solution_to_mpfr_paths(out.ctypes.data)
+    return [int(v) for v in out]
+
+
 def matgen(n, density, bits, seed, lib_path=None):
     """The benchmark's synthetic CSC (slip_matgen.h) -> Ap, Ai, Ax (int64 values)."""
     lib = _lib.load(lib_path)
@@ -399,6 +434,46 @@ class Factorization:
         g > 1, the memory class]"""
         out = np.zeros(4, np.int64)
         self.lib.slip_hip_factor_to_rational_paths(self.h, out.ctypes.data)
+        return [int(v) for v in out]
+
+    def solve_mpfr(self, blen, blimbs, nrhs=1, transpose=False, scale=None, prec=128, rnd=0, stream=None):
+        """Solve and round on the device (slip_hip_factor_solve_mpfr): (sign, exp, mant, ternary), entry c*n + j the exact
+        rational scale * xnum / det rounded ONCE to `prec` bits under the rounding mode rnd (MPFR_RNDN 0, RNDZ 1, RNDU 2,
+        RNDD 3, RNDA 4), as mpfr_set_q leaves it (what SLIP_solve_mpfr returns): sign int8 (0 for +0), MPFR's exponent int64,
+        mant uint64[nrhs*n, ceil(prec / 64)] left-aligned (mant[t, -1] is the top limb), the ternary value int8.  Only these
+        come back.  b, transpose, scale and the order of the result as `solve_double`."""
+        blen = np.ascontiguousarray(blen, dtype=np.int32)
+        blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
+        nrhs = int(nrhs)
+        if nrhs >= 1 and blen.size != self.n * nrhs:
+            raise ValueError("blen must hold n*nrhs entries")
+        if blimbs.size == 0:
+            blimbs = np.zeros(1, dtype=np.uint64)
+        if scale is None:
+            sn = sd = (0, None)
+        else:
+            num, den = (scale.numerator, scale.denominator) if hasattr(scale, "numerator") else scale
+            sn, sd = _int_limbs(num), _int_limbs(den)
+        count = self.n * max(nrhs, 0)
+        sign, exp, mant, tern = _mpfr_outputs(count, prec)
+        rc = self.lib.slip_hip_factor_solve_mpfr(self.h, int(bool(transpose)), nrhs, blen.ctypes.data, blimbs.ctypes.data,
+                                                 sn[0], None if sn[1] is None else sn[1].ctypes.data,
+                                                 sd[0], None if sd[1] is None else sd[1].ctypes.data,
+                                                 int(prec), int(rnd), sign.ctypes.data, exp.ctypes.data, mant.ctypes.data,
+                                                 tern.ctypes.data, C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_solve_mpfr")
+        return sign[:count], exp[:count], mant[:count], tern[:count]
+
+    def to_mpfr_ms(self):
+        """device ms of the conversion kernel of the last solve_mpfr"""
+        return self.lib.slip_hip_factor_to_mpfr_ms(self.h)
+
+    def to_mpfr_paths(self):
+        """entries of the last solve_mpfr settled by [the lane pass within 64 bits, the wave pass with a denominator of at
+        most 256 digits, the wave pass with a wider one, as zero]"""
+        out = np.zeros(4, np.int64)
+        self.lib.slip_hip_factor_to_mpfr_paths(self.h, out.ctypes.data)
         return [int(v) for v in out]
 
     def check(self, blen, blimbs, xlen, xlimbs, nrhs=1, stream=None):

@@ -503,6 +503,236 @@ static void slip_todouble_body(SlipToDoubleArgs A)
     if (lane == 0 && slow_total) slip_atomic_add_u64(A.nslow, slow_total);
 }
 
+/* Solution to multi-precision floats (slip_hip_factor_solve_mpfr, slip_hip_solution_to_mpfr): per entry what mpfr_set_q leaves
+ * in an mpfr_t of `prec` bits under the rounding mode `rnd` (SLIP_get_mpfr_soln.c:53) -- the ONE correct rounding of the exact
+ * quotient v = N / D, with its ternary value.  Magnitudes below; the sign is that of N * D (times flip), and 0 is +0.
+ *
+ * With bn, bd the bit lengths of N and D:  2^(bn-bd-1) < v < 2^(bn-bd+1).  The quotient is formed with one bit to spare,
+ *     Q = floor(v * 2^s),  s = prec + 1 - (bn - bd),  2^prec <= Q < 2^(prec+2),
+ * and its leading bit says on which side of 2^(bn-bd) v lies: hi = bit prec+1 of Q, e0 = bn - bd + hi (2^(e0-1) <= v < 2^e0:
+ * MPFR's exponent before rounding; no separate comparison of N and D is made).  t = Q >> hi has prec + 1 bits,
+ *     m0 = t >> 1,   rb = t & 1,   st = (the bit of Q below t, when hi) | (v * 2^s is not an integer),
+ * and the mantissa is m0 + inc, inc = 0 toward zero, rb | st away from zero (RNDU / RNDD are one of the two by sign),
+ * rb & (st | (m0 & 1)) to nearest-even.  m0 + inc = 2^prec becomes 2^(prec-1) with exponent e0 + 1.  The ternary value is 0
+ * when rb | st = 0, else the sign of the value when inc = 1 and its opposite when inc = 0.
+ *
+ * Lane pass, one lane per entry: N = 0, and -- for prec <= 64, where the result is one limb -- every pair within 64 bits:
+ * both parts left-aligned, two 128-by-64 divisions (slip_div128by64) give 127 or 128 quotient bits, which hold t for every
+ * such prec, and their remainder gives st.  Beyond 64 bits of precision the lane would carry a multi-limb mantissa; those
+ * entries go to the wave.
+ *
+ * Wave pass, one wavefront per remaining entry, wave-uniform throughout: Knuth's algorithm D in base B = 2^32.  D' = D << zd
+ * has its top bit set (ld digits); U = floor(N * 2^(s + zd)) has exactly prec + 1 + 32*ld bits, so it fills at most
+ * nq + ld digits with nq = ceil((prec + 2) / 32) quotient digits, whatever the lengths of N and D: digits of N below that
+ * window never enter the division, they only make st (a trailing-zero count, wb_ctz: a ballot over "nonzero").  Per quotient
+ * digit, from the top: the estimate from the three leading digits of the running remainder and the two of D'
+ *     qh = floor((w[ld] * B + w[ld-1]) / v1), lowered while qh * v2 > (remainder of that) * B + w[ld-2]
+ * is the true digit or one above it (Knuth 4.3.1 Theorem B needs v1 >= B/2: the normalisation; the v2 test brings the
+ * error of at most 2 down to at most 1); the wave forms qh * D' (wb_mul_lo, 1 x ld), subtracts it from the ld + 1 digits
+ * of the window (wb_addsub, one digit wider so that the digit above the window shows a borrow as 0xFFFFFFFF) and adds D'
+ * back while that digit is nonzero (at most twice).  The running remainder lives in this wave's scratch, in place in U.
+ * st = remainder != 0 or dropped digits != 0.  The mantissa is written left-aligned into ceil(prec / 64) limbs -- Q shifted
+ * so that bit prec-1 of m0 is the top bit, the bits below the last place filled with ones when inc = 1 so that adding 1 at the
+ * bottom (wb_addsub) carries into the last place and leaves them zero; all limbs zero afterwards is the carry to 2^prec.
+ *
+ * Scratch per wave (stride, sized by the host from the widest D and prec): U nq + dcap + 2, the product dcap + 2, D' dcap,
+ * the quotient nq + 1 digits.  The kernel never aborts: a zero denominator (refused by the host) gives +0. */
+struct SlipMpfrArgs {
+    int32_t n, nrhs;
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* N: entry c*n + p, signed digit counts, limb offsets */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* D: one per right-hand side                         */
+    const int32_t *oidx;                                                           /* entry p goes to slot c*n + oidx[p]; null: to p     */
+    int32_t flip;                                                                  /* negate every result (the sign of a scale)          */
+    int32_t prec, rnd;                                                             /* 2..65536; MPFR_RNDN 0, Z 1, U 2, D 3, A 4          */
+    int32_t chunk;                                                                 /* entries a wave takes per round, 1..64              */
+    int8_t *sign; int64_t *exp; uint64_t *mant; int8_t *ternary;                   /* per slot; mant: ceil(prec / 64) limbs              */
+    dig_t *scratch; int32_t dcap; int64_t stride;                                  /* wave pass: stride digits per wave, D <= dcap digits */
+    unsigned long long *paths;                                                     /* entries settled by: lane (64 bits), wave with D <= 256 digits, wave wider, zero */
+};
+
+/* what is added to the truncated mantissa m0: rnd as mpfr_rnd_t, neg the sign of the value, odd = m0 & 1 */
+SLIP_DEV int slip_mpfr_inc(int rnd, int neg, int odd, int rb, int st)
+{
+    if (rnd == 0) return rb & (st | odd);
+    const int away = rnd == 4 || (rnd == 2 && !neg) || (rnd == 3 && neg);
+    return away ? (rb | st) : 0;
+}
+
+/* the ternary value: the sign of (rounded - exact) of the signed number */
+SLIP_DEV int slip_mpfr_ternary(int neg, int inexact, int inc)
+{
+    if (!inexact) return 0;
+    return (inc != 0) != (neg != 0) ? 1 : -1;
+}
+
+/* the lane pass for N, D < 2^64 (both nonzero) and prec <= 64: the one limb of the mantissa, the exponent, the ternary value */
+SLIP_DEV uint64_t slip_mpfr_lane64(uint64_t N, uint64_t D, int prec, int rnd, int neg, int64_t *e_out, int *tern_out)
+{
+    const int zn = slip_clz64(N), zd = slip_clz64(D);
+    const uint64_t nn = N << zn, dn = D << zd;
+    /* X = Q1 * 2^64 + Q2 = floor(nn * 2^127 / dn) in [2^126, 2^128), r2 its remainder */
+    const uint64_t Q1 = slip_div128by64(nn >> 1, nn << 63, dn), r1 = (nn << 63) - Q1 * dn;
+    const uint64_t Q2 = slip_div128by64(r1, 0, dn), r2 = 0 - Q2 * dn;
+    const int sig = (Q1 >> 63) ? 128 : 127, k = sig - (prec + 1), j = k + 1;      /* t = X >> k; 62 <= k <= 125 */
+    const uint64_t m0 = j < 64 ? (Q1 << 1) | (Q2 >> 63) : (j == 64 ? Q1 : Q1 >> (j - 64));
+    const int rb = (int)((k < 64 ? Q2 >> k : Q1 >> (k - 64)) & 1);
+    const uint64_t low = k < 64 ? Q2 & ((1ull << k) - 1) : Q2 | (Q1 & ((1ull << (k - 64)) - 1));
+    const int st = low != 0 || r2 != 0;
+    const int inc = slip_mpfr_inc(rnd, neg, (int)(m0 & 1), rb, st);
+    int64_t e = (int64_t) sig - 127 + zd - zn;                                     /* bn - bd = zd - zn */
+    uint64_t m = m0 + (uint64_t) inc;
+    if (prec == 64 ? (inc && m == 0) : (m >> prec) != 0) { m = 1ull << (prec - 1); e++; }
+    *e_out = e; *tern_out = slip_mpfr_ternary(neg, rb | st, inc);
+    return m << (64 - prec);
+}
+
+/* the wave pass for entry `it` (wave-uniform); returns the digits of its denominator (0: nothing to divide, +0 written) */
+SLIP_DEV int slip_mpfr_wave(const SlipMpfrArgs &A, int64_t it, dig_t *scr)
+{
+    const int lane = slip_lane();
+    const int c = (int)(it / A.n), p = (int)(it - (int64_t) c * A.n);
+    const int64_t slot = (int64_t) c * A.n + (A.oidx ? A.oidx[p] : p);
+    const int32_t sx = A.xlen[it], sd = A.dlen[c];
+    const dig_t *x = (const dig_t *)(A.xlimbs + A.xoff[it]), *d = (const dig_t *)(A.dlimbs + A.doff[c]);
+    const int la = slip_trim_digits(x, slip_abs(sx)), ld = slip_trim_digits(d, slip_abs(sd));
+    const int neg = ((sx < 0) != (sd < 0)) != (A.flip != 0);
+    const int prec = A.prec, nl = (prec + 63) >> 6, nq = (prec + 2 + 31) >> 5;
+    dig_t *out = (dig_t *)(A.mant + slot * nl);
+    if (la == 0 || ld == 0 || ld > A.dcap) {                                       /* ld <= dcap: the host sized it */
+        for (int cc = lane; cc < 2 * nl; cc += SLIP_WAVE) out[cc] = 0u;
+        if (lane == 0) { A.sign[slot] = 0; A.exp[slot] = 0; A.ternary[slot] = 0; }
+        slip_wave_sync();
+        return 0;
+    }
+    dig_t *u = scr, *P = u + nq + A.dcap + 2, *Dn = P + A.dcap + 2, *qd = Dn + A.dcap;
+    const int zd = slip_clz32(d[ld - 1]), nu = nq + ld;
+    const int64_t bn = 32 * (int64_t) la - slip_clz32(x[la - 1]), bd = 32 * (int64_t) ld - zd;
+    const int64_t S = (int64_t) prec + 1 - bn + bd + zd;                           /* U = floor(N * 2^S) */
+    const int sb = (int)(((S % 32) + 32) % 32);
+    const int64_t sw = (S - sb) / 32;
+    wb_copy_shl(Dn, d, ld, zd, ld);
+    for (int cc = lane; cc < nu + 2; cc += SLIP_WAVE) {
+        const int64_t idx = (int64_t) cc - sw;
+        const uint32_t lo = idx >= 0 && idx < la ? x[idx] : 0u, below = idx >= 1 && idx <= la ? x[idx - 1] : 0u;
+        u[cc] = cc < nu ? (sb ? (lo << sb) | (below >> (32 - sb)) : lo) : 0u;      /* the two digits above U: zero */
+    }
+    if (lane == 0) qd[nq] = 0u;
+    slip_wave_sync();
+    int st = S < 0 && (int64_t) wb_ctz(x, la) < -S;                                /* bits of N below the window */
+    const uint64_t B = 1ull << 32;
+    const uint32_t v1 = Dn[ld - 1], v2 = ld >= 2 ? Dn[ld - 2] : 0u;
+    for (int j = nq - 1; j >= 0; j--) {
+        dig_t *w = u + j;                                                          /* the window: ld + 1 digits, w[ld + 1] == 0 */
+        const uint64_t num = ((uint64_t) w[ld] << 32) | w[ld - 1];
+        const uint32_t w2 = ld >= 2 ? w[ld - 2] : 0u;
+        uint64_t qh = num / v1, rh = num - qh * v1;
+        while (qh >= B || qh * v2 > ((rh << 32) | w2)) { qh--; rh += v1; if (rh >= B) break; }
+        if (qh >= B) qh = B - 1;                                                   /* the true digit is below B */
+        if (lane == 0) qd[j] = (dig_t) qh;
+        slip_wave_sync();
+        if (qh) {
+            wb_mul_lo(P, qd + j, 1, Dn, ld, ld + 1);
+            wb_addsub(w, w, ld + 2, P, ld + 1, ld + 2, 1);
+            int back = 0;
+            while (w[ld + 1] != 0u && back < 2) { wb_addsub(w, w, ld + 2, Dn, ld, ld + 2, 0); back++; }
+            if (back) {
+                if (lane == 0) qd[j] = (dig_t)(qh - (uint64_t) back);
+                slip_wave_sync();
+            }
+        }
+    }
+    st |= wb_len(u, ld) != 0;
+    const int hi = (int)((qd[(prec + 1) >> 5] >> ((prec + 1) & 31)) & 1u);
+    const uint32_t q0 = qd[0];
+    const int rb = (int)((q0 >> hi) & 1u), odd = (int)((q0 >> (hi + 1)) & 1u);
+    st |= hi & (int)(q0 & 1u);
+    const int inc = slip_mpfr_inc(A.rnd, neg, odd, rb, st);
+    int64_t e = bn - bd + hi;
+    /* m0 = Q >> (1 + hi), left-aligned: shifted up by z = 64*nl - prec; the z bits below the last place are ones when inc */
+    const int z = 64 * nl - prec, sh = z - 1 - hi;
+    for (int cc = lane; cc < 2 * nl; cc += SLIP_WAVE) {
+        uint32_t v;
+        if (sh >= 0) {
+            const int idx = cc - (sh >> 5), b = sh & 31;
+            const uint32_t lo = idx >= 0 && idx <= nq ? qd[idx] : 0u, below = idx >= 1 && idx - 1 <= nq ? qd[idx - 1] : 0u;
+            v = b ? (lo << b) | (below >> (32 - b)) : lo;
+        } else {
+            const int r = -sh;                                                     /* 1 or 2 */
+            const uint32_t lo = cc <= nq ? qd[cc] : 0u, above = cc + 1 <= nq ? qd[cc + 1] : 0u;
+            v = (lo >> r) | (above << (32 - r));
+        }
+        const int nlow = z - 32 * cc;                                              /* bits of this digit below the last place */
+        const uint32_t mask = nlow >= 32 ? 0xFFFFFFFFu : (nlow > 0 ? (1u << nlow) - 1u : 0u);
+        out[cc] = inc ? v | mask : v & ~mask;
+    }
+    slip_wave_sync();
+    if (inc) {
+        wb_addsub(out, (const dig_t *) 0, 1, out, 2 * nl, 2 * nl, 0, 1u);
+        if (!(out[2 * nl - 1] >> 31)) {                                            /* 2^prec: every digit is zero now */
+            slip_wave_sync();
+            if (lane == 0) out[2 * nl - 1] = 0x80000000u;
+            e++;
+        }
+    }
+    if (lane == 0) { A.sign[slot] = neg ? -1 : 1; A.exp[slot] = e; A.ternary[slot] = (int8_t) slip_mpfr_ternary(neg, rb | st, inc); }
+    slip_wave_sync();
+    return ld;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_mpfr_kernel(SlipMpfrArgs A)
+#else
+static void slip_mpfr_body(SlipMpfrArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    dig_t *scr = A.scratch + wave0 * A.stride;
+    const int64_t items = (int64_t) A.n * A.nrhs;
+    const int nl = (A.prec + 63) >> 6;
+    unsigned long long cnt0 = 0, cnt1 = 0, cnt2 = 0, cnt3 = 0;
+    for (int64_t base = wave0 * A.chunk; base < items; base += nwaves * A.chunk) {
+        const int64_t it = base + lane;
+        const int mine = lane < A.chunk && it < items;
+        int wide = 0, zero = 0;
+        if (mine) {
+            const int c = (int)(it / A.n), p = (int)(it - (int64_t) c * A.n);
+            const int64_t slot = (int64_t) c * A.n + (A.oidx ? A.oidx[p] : p);
+            const int32_t sx = A.xlen[it], sd = A.dlen[c];
+            const dig_t *x = (const dig_t *)(A.xlimbs + A.xoff[it]), *d = (const dig_t *)(A.dlimbs + A.doff[c]);
+            const int la = slip_trim_digits(x, slip_abs(sx)), ld = slip_trim_digits(d, slip_abs(sd));
+            if (la == 0 || ld == 0) {
+                zero = 1;
+                for (int k = 0; k < nl; k++) A.mant[slot * nl + k] = 0ull;
+                A.sign[slot] = 0; A.exp[slot] = 0; A.ternary[slot] = 0;
+            } else if (la <= 2 && ld <= 2 && A.prec <= 64) {
+                const uint64_t N = x[0] | ((uint64_t)(la > 1 ? x[1] : 0u) << 32), D = d[0] | ((uint64_t)(ld > 1 ? d[1] : 0u) << 32);
+                const int neg = ((sx < 0) != (sd < 0)) != (A.flip != 0);
+                int64_t e; int tern;
+                A.mant[slot] = slip_mpfr_lane64(N, D, A.prec, A.rnd, neg, &e, &tern);
+                A.sign[slot] = neg ? -1 : 1; A.exp[slot] = e; A.ternary[slot] = (int8_t) tern;
+            } else wide = 1;
+        }
+        uint64_t pend = slip_ballot(wide);
+        const int nzero = slip_popc64(slip_ballot(zero));
+        cnt3 += (unsigned long long) nzero;
+        cnt0 += (unsigned long long)(slip_popc64(slip_ballot(mine)) - slip_popc64(pend) - nzero);
+        while (pend) {
+            const int src = slip_ctz64(pend);
+            pend &= pend - 1;
+            const int ld = slip_mpfr_wave(A, base + src, scr);
+            if (ld == 0) cnt3++; else if (ld <= 256) cnt1++; else cnt2++;
+        }
+    }
+    if (lane == 0) {
+        if (cnt0) slip_atomic_add_u64(A.paths + 0, cnt0);
+        if (cnt1) slip_atomic_add_u64(A.paths + 1, cnt1);
+        if (cnt2) slip_atomic_add_u64(A.paths + 2, cnt2);
+        if (cnt3) slip_atomic_add_u64(A.paths + 3, cnt3);
+    }
+}
+
 /* Solution as reduced fractions (slip_hip_factor_solve_rational, slip_hip_solution_to_rational): per entry the canonical form
  * of N / D that mpq_canonicalize leaves (SLIP_solve_mpq's output: SLIP_LU_solve's mpq_div, SLIP_permute_x, SLIP_scale_x):
  *     g = gcd(|N|, |D|),   num = sgn(N * D) * |N| / g,   den = |D| / g > 0,   0 = 0 / 1.
@@ -1147,6 +1377,8 @@ struct slip_hip_factor {
     double todouble_ms; int64_t todouble_slow;
     /* slip_hip_factor_solve_rational: device time of the last reduction kernel, entries of it by the path that settled them */
     double torational_ms; int64_t torational_paths[4];
+    /* slip_hip_factor_solve_mpfr: device time of the last conversion kernel, entries of it by the path that settled them */
+    double tompfr_ms; int64_t tompfr_paths[4];
 };
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -2605,6 +2837,140 @@ extern "C" int slip_hip_solution_to_double(int32_t n, int32_t nrhs, const int32_
     dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
     slab_free(&xs); slab_free(&ds);
     return rc;
+}
+
+/* ---- solutions as multi-precision floats (SLIP_solve_mpfr's tail: SLIP_permute_x, SLIP_scale_x, SLIP_get_mpfr_soln; kernels:
+ * slip_mpfr_kernel, slip_scale_kernel) ---- */
+
+/* the counts of the last slip_hip_solution_to_mpfr of this thread (the handle-less entry has nowhere else to keep them) */
+static thread_local int64_t slip_mpfr_paths_last[4];
+
+/* what both entry points refuse before anything runs: 2 <= prec <= 65536, the five rounding modes, the three arrays */
+static int mpfr_args_ok(int32_t prec, int32_t rnd, const int8_t *sign_out, const int64_t *exp_out, const uint64_t *mant_out)
+{
+    return prec >= 2 && prec <= 65536 && rnd >= 0 && rnd <= 4 && sign_out && exp_out && mant_out;
+}
+
+/* one conversion on the device: the operands as to_double_core takes them.  The host arrays receive n * nrhs signs, exponents
+ * and ternary values (ternary_out may be NULL) and n * nrhs * ceil(prec / 64) limbs; nothing else comes back. */
+static int mpfr_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int64_t *dxoff, const uint64_t *dxlimbs,
+                     const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
+                     const int32_t *doidx, int flip, int32_t prec, int32_t rnd,
+                     int8_t *sign_out, int64_t *exp_out, uint64_t *mant_out, int8_t *ternary_out,
+                     hipStream_t stream, double *ms_out, int64_t *paths_out)
+{
+    const int64_t ne = (int64_t) n * nrhs, nl = (prec + 63) >> 6, nq = (prec + 2 + 31) >> 5;
+    const int64_t dcap = dmaxdig > 1 ? dmaxdig : 1;
+    if (dcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
+    /* the running remainder with the quotient digits' room above it, one product, the normalised divisor, the quotient */
+    const int64_t stride = ((nq + dcap + 2) + (dcap + 2) + dcap + (nq + 1) + 1) & ~(int64_t) 1;
+#ifndef SLIP_EMULATE
+    /* a wave takes `chunk` entries per round: few entries are spread one to a wave, many fill the lanes of 4096 waves */
+    const int64_t waves_per_block = 4;
+    int64_t chunk = (ne + 4095) / 4096;
+    if (chunk > 64) chunk = 64;
+    int64_t blocks = (ne + chunk * waves_per_block - 1) / (chunk * waves_per_block);
+    if (blocks > 1024) blocks = 1024;
+    const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * stride * 4);      /* at most 256 MiB of scratch */
+    if (blocks > fit) blocks = fit;
+    if (blocks < 1) blocks = 1;
+#else
+    const int64_t blocks = 2, waves_per_block = 2, chunk = 5;
+#endif
+    int8_t *dsign = NULL, *dtern = NULL; int64_t *dexp = NULL; uint64_t *dmant = NULL;
+    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
+    hipEvent_t ev0 = NULL, ev1 = NULL;
+    int rc = 0;
+    A_(dev_alloc(&dsign, ne)); A_(dev_alloc(&dtern, ne)); A_(dev_alloc(&dexp, ne)); A_(dev_alloc(&dmant, ne * nl));
+    A_(dev_alloc(&dscr, blocks * waves_per_block * stride)); A_(dev_alloc(&dpaths, 4));
+    HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
+    HIP_(hipEventCreate(&ev0)); HIP_(hipEventCreate(&ev1));
+    if (!rc) {
+        SlipMpfrArgs A; memset(&A, 0, sizeof A);
+        A.n = n; A.nrhs = nrhs; A.xlen = dxlen; A.xoff = dxoff; A.xlimbs = dxlimbs; A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
+        A.oidx = doidx; A.flip = flip; A.prec = prec; A.rnd = rnd; A.chunk = (int32_t) chunk;
+        A.sign = dsign; A.exp = dexp; A.mant = dmant; A.ternary = dtern;
+        A.scratch = dscr; A.dcap = (int32_t) dcap; A.stride = stride; A.paths = dpaths;
+        HIP_(hipEventRecord(ev0, stream));
+#ifndef SLIP_EMULATE
+        if (!rc) {
+            hipLaunchKernelGGL(slip_mpfr_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
+            HIP_(hipGetLastError());
+        }
+#else
+        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_mpfr_body(A); }, 256 * 1024, 1);
+#endif
+        HIP_(hipEventRecord(ev1, stream)); HIP_(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIP_(hipEventElapsedTime(&ms, ev0, ev1));
+        if (ms_out) *ms_out = ms;
+    }
+    DOWN_(sign_out, dsign, (size_t) ne); DOWN_(exp_out, dexp, (size_t) ne * 8); DOWN_(mant_out, dmant, (size_t)(ne * nl) * 8);
+    if (ternary_out) DOWN_(ternary_out, dtern, (size_t) ne);
+    DOWN_(hpaths, dpaths, 32);
+    if (!rc && paths_out) for (int t = 0; t < 4; t++) paths_out[t] = (int64_t) hpaths[t];
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    dev_free(dsign); dev_free(dtern); dev_free(dexp); dev_free(dmant); dev_free(dscr); dev_free(dpaths);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_solve_mpfr(slip_hip_factor *f, int32_t transpose, int32_t nrhs, const int32_t *blen, const uint64_t *blimbs,
+                                          int32_t snlen, const uint64_t *snlimbs, int32_t sdlen, const uint64_t *sdlimbs,
+                                          int32_t prec, int32_t rnd, int8_t *sign_out, int64_t *exp_out, uint64_t *mant_out,
+                                          int8_t *ternary_out, void *stream_v)
+{
+    if (!mpfr_args_ok(prec, rnd, sign_out, exp_out, mant_out)) return SLIP_HIP_INCORRECT_INPUT;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipScaledSol s;
+    TRY_(solve_scaled(f, transpose, nrhs, blen, blimbs, snlen, snlimbs, sdlen, sdlimbs, stream, &s));
+    f->tompfr_ms = 0; memset(f->tompfr_paths, 0, sizeof f->tompfr_paths);
+    const int rc = mpfr_core(f->n, nrhs, s.nlen, s.noff, s.nlimbs, s.ddlen, s.ddoff, s.dden, s.ddig, s.doidx, s.flip, prec, rnd,
+                             sign_out, exp_out, mant_out, ternary_out, stream, &f->tompfr_ms, f->tompfr_paths);
+    scaled_free(&s);
+    return rc;
+}
+
+extern "C" double slip_hip_factor_to_mpfr_ms(const slip_hip_factor *f) { return f ? f->tompfr_ms : 0.0; }
+extern "C" int slip_hip_factor_to_mpfr_paths(const slip_hip_factor *f, int64_t out[4])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->tompfr_paths, sizeof f->tompfr_paths);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_solution_to_mpfr(int32_t n, int32_t nrhs, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                         const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs, int32_t prec, int32_t rnd,
+                                         int8_t *sign_out, int64_t *exp_out, uint64_t *mant_out, int8_t *ternary_out, void *stream_v)
+{
+    if (n <= 0 || nrhs < 1 || !xlen || !xlimbs || !dlen || !dlimbs) return SLIP_HIP_INCORRECT_INPUT;
+    if (!mpfr_args_ok(prec, rnd, sign_out, exp_out, mant_out)) return SLIP_HIP_INCORRECT_INPUT;
+    TRY_(need_device());
+    const int64_t ne = (int64_t) n * nrhs;
+    SlipSlab xs, ds;
+    memset(&ds, 0, sizeof ds);
+    int rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
+    if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
+    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no number */
+    int32_t *dxl = NULL, *ddl = NULL; int64_t *dxo = NULL, *ddo = NULL; uint64_t *dxv = NULL, *ddv = NULL;
+    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total));
+    A_(dev_alloc(&ddl, nrhs)); A_(dev_alloc(&ddo, nrhs)); A_(dev_alloc(&ddv, ds.total));
+    UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
+    UP_(ddl, ds.dig, (size_t) nrhs * 4); UP_(ddo, ds.off, (size_t) nrhs * 8); UP_(ddv, dlimbs, (size_t) ds.total * 8);
+    memset(slip_mpfr_paths_last, 0, sizeof slip_mpfr_paths_last);
+    A_(mpfr_core(n, nrhs, dxl, dxo, dxv, ddl, ddo, ddv, ds.maxdig, NULL, 0, prec, rnd, sign_out, exp_out, mant_out, ternary_out,
+                 (hipStream_t) stream_v, NULL, slip_mpfr_paths_last));
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
+    slab_free(&xs); slab_free(&ds);
+    return rc;
+}
+
+/* the path counts of this thread's last slip_hip_solution_to_mpfr, as slip_hip_factor_to_mpfr_paths lays them out */
+extern "C" int slip_hip_solution_to_mpfr_paths(int64_t out[4])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_mpfr_paths_last, sizeof slip_mpfr_paths_last);
+    return SLIP_HIP_OK;
 }
 
 /* ---- solutions as reduced fractions (SLIP_solve_mpq's tail: mpq_div, SLIP_permute_x, SLIP_scale_x, each canonicalising;

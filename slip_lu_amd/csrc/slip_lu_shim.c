@@ -389,6 +389,61 @@ SLIP_info SLIP_hip_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S,
     return ret;
 }
 
+#ifdef SLIP_HAVE_MPFR
+/* ------------------------------------------------------------------------------------------------
+ * SLIP_solve_mpfr (SLIP_LU/Include/SLIP_LU.h, SLIP_LU/Source/SLIP_solve_mpfr.c:40-104) on the GPU: factorise, substitute,
+ * permute (SLIP_permute_x), scale (SLIP_scale_x) and round (SLIP_get_mpfr_soln: mpfr_set_q per entry under
+ * option->SLIP_MPFR_ROUND) without leaving the device: slip_hip_factor_solve_mpfr returns per entry a sign, an exponent and
+ * the limbs of the mantissa, and nothing else -- no L, U, rho, numerator or fraction is downloaded.  x_mpfr[i][j] (n rows of
+ * b->n mpfr_t, initialised by the caller: SLIP_create_mpfr_mat gives every entry option->prec bits) receives entry i of the
+ * solution of right-hand side j.  The precision is the one the entries carry, mpfr_get_prec(x_mpfr[0][0]); entries of
+ * differing precisions are SLIP_INCORRECT_INPUT (the reference would round each to its own).  Every mpfr_t is filled through
+ * MPFR's public interface: the limbs as a read-only mpz_t (mpz_roinit_n) into mpfr_set_z_2exp, which is exact because the
+ * mantissa has at most that many significant bits; a zero through mpfr_set_zero(x, +1).
+ * ------------------------------------------------------------------------------------------------ */
+SLIP_info SLIP_hip_solve_mpfr(mpfr_t **x_mpfr, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
+{
+    if (!x_mpfr || !A || !A->p || !A->i || !A->x || !S || !S->q || !b || !b->x || !option)
+        return SLIP_INCORRECT_INPUT;                      /* SLIP_solve_mpfr.c:52-56 */
+    const int32_t n = A->n, nrhs = b->n;
+    if (n <= 0 || nrhs <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
+    for (int32_t i = 0; i < n; i++) if (!x_mpfr[i]) return SLIP_INCORRECT_INPUT;
+    const mpfr_prec_t prec = mpfr_get_prec(x_mpfr[0][0]);
+    for (int32_t i = 0; i < n; i++)
+        for (int32_t j = 0; j < nrhs; j++) if (mpfr_get_prec(x_mpfr[i][j]) != prec) return SLIP_INCORRECT_INPUT;
+    if (prec < 2 || prec > 65536) return SLIP_INCORRECT_INPUT;
+    if (option->SLIP_MPFR_ROUND < 0 || option->SLIP_MPFR_ROUND > 4) return SLIP_INCORRECT_INPUT;      /* RNDN, Z, U, D, A: before any device work */
+    const int64_t ne = (int64_t) n * nrhs, nl = ((int64_t) prec + 63) / 64;
+    slip_hip_factor *f = NULL;
+    int32_t *blen = NULL, snlen = 0, sdlen = 0;
+    uint64_t *blimbs = NULL, *snl = NULL, *sdl = NULL;
+    int8_t *sign = (int8_t *) malloc((size_t) ne);
+    int64_t *ex = (int64_t *) malloc((size_t) ne * 8);
+    uint64_t *mant = (uint64_t *) malloc((size_t)(ne * nl) * 8);
+    SLIP_info ret = sign && ex && mant ? factor_for_solve(A, S, b, option, &f, &blen, &blimbs, &snlen, &snl, &sdlen, &sdl) : SLIP_OUT_OF_MEMORY;
+    if (ret == SLIP_OK)
+        ret = solve_status(slip_hip_factor_solve_mpfr(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl, (int32_t) prec,
+                                                      (int32_t) option->SLIP_MPFR_ROUND, sign, ex, mant, NULL, NULL));
+    if (ret == SLIP_OK)
+        for (int32_t j = 0; j < nrhs; j++)
+            for (int32_t i = 0; i < n; i++) {
+                const int64_t t = (int64_t) j * n + i;
+                if (sign[t] == 0) { mpfr_set_zero(x_mpfr[i][j], +1); continue; }
+                mpz_t z;
+                mpz_roinit_n(z, (const mp_limb_t *)(mant + t * nl), sign[t] < 0 ? -(mp_size_t) nl : (mp_size_t) nl);
+                mpfr_set_z_2exp(x_mpfr[i][j], z, (mpfr_exp_t)(ex[t] - 64 * nl), MPFR_RNDN);      /* exact: prec bits at most */
+            }
+    if (f) slip_hip_factor_destroy(f);
+    free(sign); free(ex); free(mant); free(blen); free(blimbs); free(snl); free(sdl);
+    return ret;
+}
+
+SLIP_info SLIP_solve_mpfr(mpfr_t **x_mpfr, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
+{
+    return SLIP_hip_solve_mpfr(x_mpfr, A, S, b, option);
+}
+#endif
+
 SLIP_info SLIP_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
 {
     return SLIP_hip_solve_mpq(x_mpq, A, S, b, option);
