@@ -23,6 +23,8 @@
  *   slip_hip_solution_to_rational             SLIP_LU/Source/SLIP_solve_mpq.c:74-93, slip_array_div.c:36-49 (mpq_canonicalize per entry)
  *   slip_hip_factor_solve_transpose,     <->  no counterpart: the reference solves A x = b only (KLU's klu_tsolve,
  *   slip_hip_factor_check_transpose           UMFPACK's A' system are the transposed solves of other sparse LUs)
+ *   slip_hip_factor_rewind,              <->  no counterpart: the reference factorises from column 0 (KLU's klu_refactor,
+ *   slip_hip_factor_replace_column            a simplex code's basis change are what other codes offer between two solves)
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
  *
  * The GMP-typed drop-in  SLIP_LU_factorize(L,U,A,S,rhos,pinv,option)  built on
@@ -342,6 +344,44 @@ int slip_hip_factor_set_prefix(slip_hip_factor *f, int32_t K,
                                const int64_t *Lp, const int32_t *Li, const int32_t *Llen, const uint64_t *Llimbs,
                                const int64_t *Up, const int32_t *Ui, const int32_t *Ulen, const uint64_t *Ulimbs,
                                const int32_t *piv_row);
+
+/* Back to column K, and a column of A replaced in place: what a code that solves a sequence of nearly equal systems does
+ * between two solves (an exact simplex code's basis change; cf. klu_refactor).  No counterpart in the reference, which offers
+ * SLIP_LU_factorize from column 0 only.  REF LU is left-looking: columns 0..p-1 of L and U, their pivots and their row swaps
+ * depend on A(:, q[0..p-1]) alone, so after a change to the column at position p they still are the exact factorisation.
+ * All of it is device work on the resident data; only a new column crosses to the device.
+ *
+ * slip_hip_factor_rewind: a handle made by slip_hip_factor_create is put back into the state slip_hip_factor_run(f, K) from a
+ * reset would have left: columns K.. forgotten, their row swaps undone from the swap log, slip_hip_factor_run continues with
+ * column K.  0 <= K <= info.K.  K == info.K with q_tail == NULL changes nothing; K == 0 is slip_hip_factor_reset.  What
+ * _info / _download then serve (K, lnz, unz, l_limbs, u_limbs, the columns, the pivots, pinv) is that of a run to K.  The
+ * algorithmic counters (n_upd .. limb_macs, raw_fills and the commit diagnostics) restart at zero and then count the work
+ * SINCE the rewind; max_limbs keeps its value, an upper bound from then on.  The transposed view and a rescaled copy are
+ * dropped, as by reset.  q_tail: NULL, or n - K original column ids, the new order of positions K..n-1 (the columns there
+ * are factorised again anyway) -- this is how a replaced column moves to the last position, Forrest-Tomlin style.  It must
+ * be a permutation of the ids that stand there now.
+ *
+ * slip_hip_factor_replace_column: column j of A (ORIGINAL column id) gets new content, nz >= 1 entries in the per-column form
+ * of slip_hip_factor_create: row ids, signed limb counts, limbs back to back, limbs_cap = the limbs the array holds.  The
+ * rules of slip_hip_factor_create hold: unsorted rows are allowed, a repeated row keeps its LAST value, high zero limbs are
+ * trimmed.  The handle is rewound to min(info.K, p) with q[p] = j (not at all when column j has not been reached yet), and
+ * slip_hip_factor_run continues from there.  Everything the handle serves afterwards -- factors, pivots, pinv, the solves,
+ * the checks -- is bit for bit what a fresh handle on the new matrix (same q, same options) serves.  The resident CSC is
+ * edited on the device: the new limbs are appended to the limb slab, the entry arrays are spliced; limbs of replaced columns
+ * are compacted away once they outnumber the live ones, so the storage of A stays within twice its live content plus the
+ * initial allocation (slip_hip_factor_a_storage).
+ *
+ * Statuses: SLIP_HIP_INCORRECT_INPUT, with the handle untouched, for a handle from slip_hip_factor_from_factors, K outside
+ * [0, info.K], a q_tail that is no permutation of the tail, j outside [0, n), nz < 1, a row id outside [0, n), sum |len| >
+ * limbs_cap.  A device step that fails after the resident arrays began to change leaves a handle that refuses every further
+ * call but slip_hip_factor_destroy with SLIP_HIP_DEVICE_ERROR: it never serves a mixed matrix. */
+int slip_hip_factor_rewind(slip_hip_factor *f, int32_t K, const int32_t *q_tail, void *stream);
+int slip_hip_factor_replace_column(slip_hip_factor *f, int32_t j, int32_t nz, const int32_t *rows, const int32_t *len,
+                                   const uint64_t *limbs, int64_t limbs_cap, void *stream);
+/* the storage of the resident A: out[0] live entries, out[1] entries the entry arrays can hold, out[2] live limbs, out[3]
+ * limbs the slab can hold.  After any sequence of replacements out[1] <= 2 * out[0] + (entries at creation) and
+ * out[3] <= 2 * out[2] + (limbs at creation). */
+int slip_hip_factor_a_storage(const slip_hip_factor *f, int64_t out[4]);
 
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize

@@ -43,7 +43,8 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_solve_rational", "slip_hip_solution_to_rational", "slip_hip_factor_to_rational_ms",
            "slip_hip_factor_to_rational_paths", "slip_hip_solution_to_rational_paths",
            "slip_hip_factor_solve_mpfr", "slip_hip_solution_to_mpfr", "slip_hip_factor_to_mpfr_ms",
-           "slip_hip_factor_to_mpfr_paths", "slip_hip_solution_to_mpfr_paths")
+           "slip_hip_factor_to_mpfr_paths", "slip_hip_solution_to_mpfr_paths",
+           "slip_hip_factor_rewind", "slip_hip_factor_replace_column", "slip_hip_factor_a_storage")
 
 _libs = {}
 
@@ -135,5 +136,11 @@ def load(path=None):
     lib.slip_hip_factor_to_mpfr_paths.restype = C.c_int
     lib.slip_hip_solution_to_mpfr_paths.argtypes = [vp]
     lib.slip_hip_solution_to_mpfr_paths.restype = C.c_int
+    lib.slip_hip_factor_rewind.argtypes = [vp, C.c_int32, vp, vp]
+    lib.slip_hip_factor_rewind.restype = C.c_int
+    lib.slip_hip_factor_replace_column.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, i64, vp]
+    lib.slip_hip_factor_replace_column.restype = C.c_int
+    lib.slip_hip_factor_a_storage.argtypes = [vp, vp]
+    lib.slip_hip_factor_a_storage.restype = C.c_int
     _libs[path] = lib
     return lib

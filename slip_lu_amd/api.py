@@ -288,6 +288,57 @@ class Factorization:
         if rc:
             raise SlipError(rc, "slip_hip_factor_reset")
 
+    def rewind(self, K, q_tail=None, stream=None):
+        """Back to column K (slip_hip_factor_rewind): the state run(K) from a reset would have left, 0 <= K <= info()["K"];
+        run() continues with column K.  q_tail: None, or the new order of positions K..n-1 (original column ids, a
+        permutation of the ids that stand there now)."""
+        qt = None
+        if q_tail is not None:
+            qt = np.ascontiguousarray(q_tail, dtype=np.int32)
+            if qt.size != self.n - int(K):
+                raise SlipError(-3, "rewind: q_tail must hold n - K column ids")
+            if qt.size == 0:
+                qt = np.zeros(1, np.int32)
+        rc = self.lib.slip_hip_factor_rewind(self.h, int(K), None if qt is None else qt.ctypes.data, C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_rewind")
+
+    def replace_column(self, j, rows, values=None, slab=None, stream=None):
+        """Column j of A (original column id) gets new content on the device (slip_hip_factor_replace_column): `rows` row
+        ids and `values` Python ints of any size (through ints_to_slab while they fit 63 bits), or slab=(signed limb counts,
+        limbs) as Factorization() takes a column.  A repeated row keeps its LAST value.  The handle is rewound to the
+        column's position if it was factorised already; run() continues from there."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if slab is not None:
+            lens, limbs = slab
+        elif all(abs(int(v)) < 2 ** 63 for v in values):
+            lens, limbs = ints_to_slab([int(v) for v in values])
+        else:
+            parts = [_int_limbs(v) for v in values]
+            lens = [l for l, _ in parts]
+            limbs = np.concatenate([x[:abs(l)] for l, x in parts]) if parts else np.zeros(0, np.uint64)
+        lens, limbs, cap = _limb_arrays(lens, limbs)
+        if lens.size != rows.size:
+            raise SlipError(-3, "replace_column: one value per row id")
+        if rows.size == 0:
+            rows, lens = np.zeros(1, np.int32), np.zeros(1, np.int32)
+            nz = 0
+        else:
+            nz = int(rows.size)
+        rc = self.lib.slip_hip_factor_replace_column(self.h, int(j), nz, rows.ctypes.data, lens.ctypes.data, limbs.ctypes.data,
+                                                     cap, C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_replace_column")
+
+    def a_storage(self):
+        """the storage of the resident A: dict(nnz, nnz_cap, limbs, limbs_cap) -- live entries, entries the arrays can hold,
+        live limbs, limbs the slab can hold (slip_hip_factor_a_storage)"""
+        out = np.zeros(4, np.int64)
+        rc = self.lib.slip_hip_factor_a_storage(self.h, out.ctypes.data)
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_a_storage")
+        return dict(nnz=int(out[0]), nnz_cap=int(out[1]), limbs=int(out[2]), limbs_cap=int(out[3]))
+
     def run(self, kmax=0, stream=None, check=True):
         rc = self.lib.slip_hip_factor_run(self.h, int(kmax), C.c_void_p(stream or 0))
         if rc and check:

@@ -1224,8 +1224,141 @@ slip_tview_scan_kernel(SlipTViewArgs A)
 }
 #endif
 
+/* Back to column K (slip_hip_factor_rewind): the swaps of columns Kold-1 ... K undone from the log, in parallel.  The serial
+ * undo of column c, with r = row_perm[c], d = sw_row[c], p = sw_pos[c] (p >= c: the pivot row stood at or behind c), writes
+ * row_perm[c] = d and row_perm[p] = r (the same value when p == c: then d == r), walking c downwards.  Two facts make it a
+ * parallel pass: (1) the undo of a later column c' > c writes positions c' and p' >= c' only, so row_perm[c] is still what
+ * the factorisation left when column c's turn comes -- every r_c can be read up front; (2) the walk goes downwards, so the
+ * LAST write to a position x >= K, the one that stays, is that of the SMALLEST c >= K with c == x or sw_pos[c] == x: d_c in
+ * the first case, r_c in the second.  Positions < K are never written.  pinv then follows from row_perm on [K, n): the rows
+ * at those positions are the same set before and after.
+ *   phase 0: rsave[c - K] = row_perm[c], win[x - K] = min over the columns c that write x (win starts at SLIP_REWIND_NONE)
+ *   phase 1: row_perm[x] from the winner         phase 2: pinv[row_perm[x]] = x, Lready[x] = 0, for x in [K, n)
+ *   phase 3: the limbs of the entries below Lp[K] / Up[K] summed (out[0], out[1]: SlipState.Lnl_exact / Unl_exact of the
+ *            frontier K) and out[2..6] = Lp[K], Up[K], Lo[K], Uo[K], row_perm[K - 1] */
+#define SLIP_REWIND_NONE 0x7f7f7f7f
+struct SlipRewindArgs {
+    int32_t n, K, Kold, phase;
+    int32_t *row_perm, *pinv, *Lready; const int32_t *sw_row, *sw_pos;
+    int32_t *win, *rsave;                                              /* n - K and Kold - K words */
+    const int64_t *Lp, *Up, *Lo, *Uo; const SlipEnt *Le, *Ue;
+    int64_t lnz_max, unz_max;                                          /* the entries there are: no read beyond them */
+    unsigned long long *out;                                           /* 8 words, zeroed */
+};
+
+SLIP_DEV uint64_t slip_wave_sum_u64(uint64_t v)
+{
+    const int lane = slip_lane();
+    for (int d = 32; d >= 1; d >>= 1) v += slip_shfl_u64(v, lane ^ d);
+    return v;
+}
+
 #ifndef SLIP_EMULATE
-#define SLIP_MAX_WAVES 8                   /* at most 512 threads per worker: 256 VGPRs per lane, two waves per SIMD */
+__global__ void __launch_bounds__(256)
+slip_rewind_kernel(SlipRewindArgs A)
+#else
+static void slip_rewind_body(SlipRewindArgs A)
+#endif
+{
+    const int64_t t0 = (int64_t) slip_block() * slip_nthreads() + slip_tid(), nt = (int64_t) slip_nblocks() * slip_nthreads();
+    const int K = A.K, n = A.n;
+    if (A.phase == 0) {
+        for (int64_t c = K + t0; c < A.Kold; c += nt) {
+            const int p = A.sw_pos[c];
+            A.rsave[c - K] = A.row_perm[c];
+            slip_atomic_min_i32(&A.win[c - K], (int32_t) c);
+            if (p >= K && p < n) slip_atomic_min_i32(&A.win[p - K], (int32_t) c);
+        }
+    } else if (A.phase == 1) {
+        for (int64_t x = K + t0; x < n; x += nt) {
+            const int w = A.win[x - K];
+            if (w != SLIP_REWIND_NONE) A.row_perm[x] = x == w ? A.sw_row[w] : A.rsave[w - K];
+        }
+    } else if (A.phase == 2) {
+        for (int64_t x = K + t0; x < n; x += nt) {
+            const int r = A.row_perm[x];
+            if (r >= 0 && r < n) A.pinv[r] = (int32_t) x;
+            A.Lready[x] = 0;
+        }
+    } else {
+        const int64_t lnz = A.Lp[K], unz = A.Up[K];
+        uint64_t sl = 0, su = 0;
+        for (int64_t t = t0; t < lnz && t < A.lnz_max; t += nt) sl += (uint64_t) slip_limbs(A.Le[t].len);
+        for (int64_t t = t0; t < unz && t < A.unz_max; t += nt) su += (uint64_t) slip_limbs(A.Ue[t].len);
+        sl = slip_wave_sum_u64(sl); su = slip_wave_sum_u64(su);
+        if (slip_lane() == 0) {
+            if (sl) slip_atomic_add_u64(&A.out[0], sl);
+            if (su) slip_atomic_add_u64(&A.out[1], su);
+        }
+        if (t0 == 0) {
+            A.out[2] = (unsigned long long) lnz; A.out[3] = (unsigned long long) unz;
+            A.out[4] = (unsigned long long) A.Lo[K]; A.out[5] = (unsigned long long) A.Uo[K];
+            A.out[6] = (unsigned long long)(K > 0 ? A.row_perm[K - 1] : 0);
+        }
+    }
+}
+
+/* A column of the resident A replaced (slip_hip_factor_replace_column): the entries keep their own limb offsets, so only the
+ * entry arrays move.  Out of place: entry t of the old arrays goes to t (before the column, t < a0) or to t + diff (behind
+ * it, t >= a1), diff = nz_new - (a1 - a0); the slots [a0, a0 + nz_new) of the new arrays are filled by the host's upload of
+ * the new column.  The column pointers behind the column move by diff in place (nobody reads them here: a0, a1 are
+ * arguments). */
+struct SlipSpliceArgs {
+    int32_t n, j; int64_t a0, a1, nz_new, nnz_old;
+    const int32_t *Ai, *Alen; const int64_t *Aoff;
+    int32_t *nAi, *nAlen; int64_t *nAoff; int64_t *Ap;
+};
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_splice_kernel(SlipSpliceArgs A)
+#else
+static void slip_splice_body(SlipSpliceArgs A)
+#endif
+{
+    const int64_t t0 = (int64_t) slip_block() * slip_nthreads() + slip_tid(), nt = (int64_t) slip_nblocks() * slip_nthreads();
+    const int64_t diff = A.nz_new - (A.a1 - A.a0);
+    for (int64_t t = t0; t < A.nnz_old; t += nt) {
+        if (t >= A.a0 && t < A.a1) continue;
+        const int64_t d = t < A.a0 ? t : t + diff;
+        A.nAi[d] = A.Ai[t]; A.nAlen[d] = A.Alen[t]; A.nAoff[d] = A.Aoff[t];
+    }
+    if (diff) for (int64_t c = (int64_t) A.j + 1 + t0; c <= A.n; c += nt) A.Ap[c] += diff;
+}
+
+/* The limb offsets of a compacted slab (the dead limbs of replaced columns squeezed out; slip_pack_kernel then moves the
+ * limbs): off[t] = the limbs of the entries before t, len in signed digits.  Every workgroup owns a contiguous chunk of the
+ * entries and every thread a contiguous share of the chunk.  phase 0: bsum[b] = the limbs of chunk b; phase 1: the offsets,
+ * each workgroup starting at the sum of the chunks before its own.  tmp: 40 words per workgroup. */
+struct SlipOffScanArgs { int64_t count; const int32_t *len; int64_t *off; unsigned long long *bsum; int32_t phase; };
+
+SLIP_DEV void slip_offscan_body(const SlipOffScanArgs &A, uint64_t *tmp)
+{
+    const int tid = slip_tid(), T = slip_nthreads(), b = slip_block(), B = slip_nblocks();
+    const int64_t chunk = (A.count + B - 1) / B, c0 = (int64_t) b * chunk < A.count ? (int64_t) b * chunk : A.count,
+                  c1 = c0 + chunk < A.count ? c0 + chunk : A.count;
+    const int64_t per = (c1 - c0 + T - 1) / T, i0 = c0 + (int64_t) tid * per < c1 ? c0 + (int64_t) tid * per : c1,
+                  i1 = i0 + per < c1 ? i0 + per : c1;
+    uint64_t s = 0;
+    for (int64_t i = i0; i < i1; i++) s += (uint64_t) slip_limbs(A.len[i]);
+    if (A.phase == 1 && tid == 0) { uint64_t base = 0; for (int k = 0; k < b; k++) base += A.bsum[k]; tmp[36] = base; }
+    uint64_t e, e2, t, t2;
+    slip_block_scan2(s, 0, tmp, &e, &e2, &t, &t2);
+    if (A.phase == 0) { if (tid == 0) A.bsum[b] = t; return; }
+    e += tmp[36];
+    for (int64_t i = i0; i < i1; i++) { A.off[i] = (int64_t) e; e += (uint64_t) slip_limbs(A.len[i]); }
+}
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_offscan_kernel(SlipOffScanArgs A)
+{
+    __shared__ uint64_t tmp[40];
+    slip_offscan_body(A, tmp);
+}
+#endif
+
+#ifndef SLIP_EMULATE
+#define SLIP_MAX_WAVES 8                  /* at most 512 threads per worker: 256 VGPRs per lane, two waves per SIMD */
 template <bool FAST>
 __global__ void __launch_bounds__(64 * SLIP_MAX_WAVES)
 slip_factor_kernel(SlipParams P, SlipState *st)
@@ -1379,6 +1512,13 @@ struct slip_hip_factor {
     double torational_ms; int64_t torational_paths[4];
     /* slip_hip_factor_solve_mpfr: device time of the last conversion kernel, entries of it by the path that settled them */
     double tompfr_ms; int64_t tompfr_paths[4];
+    /* slip_hip_factor_rewind / _replace_column: the host copy of q; the storage of the resident A -- annz / alimbs are its
+     * LIVE entries and limbs, Acap_nz / Acap_nl what dAi, dAlen, dAoff / dAlimbs can hold, Anl_used the limbs of the slab
+     * handed out (live ones and the dead ones of replaced columns: new limbs are appended there), A0_nz / A0_nl the initial
+     * allocation; broken: a device step of a replacement or rewind failed half way, every further use is refused */
+    int32_t *hq;
+    int64_t Acap_nz, Acap_nl, Anl_used, A0_nz, A0_nl;
+    int32_t broken;
 };
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -1799,6 +1939,7 @@ static int upload_state(slip_hip_factor *f, hipStream_t stream)
 extern "C" int slip_hip_factor_reset(slip_hip_factor *f)
 {
     if (!f || f->factors_only) return SLIP_HIP_INCORRECT_INPUT;
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
     SlipParams *P = &f->P;
     const int32_t n = f->n;
     if (!P->xd || !P->xrow) return SLIP_HIP_OUT_OF_MEMORY;
@@ -1842,6 +1983,7 @@ extern "C" void slip_hip_factor_destroy(slip_hip_factor *f)
     dev_free(f->chkt_rp); dev_free(f->chkt_re); dev_free(f->chkt_rx);
     rescale_drop(f);
     tview_drop(f);
+    free(f->hq);
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     free(f);
@@ -1962,6 +2104,7 @@ extern "C" int slip_hip_factor_create(slip_hip_factor **out, int32_t n,
     if (!f) { host_a_free(&ha); return SLIP_HIP_OUT_OF_MEMORY; }
     SlipParams *P = &f->P;
     f->n = n; f->annz = onz; f->alimbs = ol; f->amaxdig = maxdig;
+    f->Acap_nz = f->A0_nz = onz > 0 ? onz : 1; f->Acap_nl = f->A0_nl = ol > 0 ? ol : 1; f->Anl_used = ol;
     apply_options(f, opt);
     P->n = n; P->pivot_scheme = opt.pivot; P->limb_cap = opt.limb_cap;
     if (!(opt.tol > 0)) { P->tol_mode = 0; P->tol_m = 0; P->tol_e = 0; }
@@ -1995,6 +2138,8 @@ extern "C" int slip_hip_factor_create(slip_hip_factor **out, int32_t n,
     UP_(f->dAp, ha.Ap, ((size_t) n + 1) * 8); UP_(f->dAi, ha.Ai, (size_t) onz * 4); UP_(f->dAlen, ha.Alen, (size_t) onz * 4);
     UP_(f->dAoff, ha.Aoff, (size_t) onz * 8); UP_(f->dAlimbs, ha.Alimbs, (size_t) ol * 8); UP_(f->dq, q, (size_t) n * 4);
     host_a_free(&ha);
+    if (!rc && !(f->hq = (int32_t *) malloc((size_t) n * 4))) rc = SLIP_HIP_OUT_OF_MEMORY;
+    if (!rc) memcpy(f->hq, q, (size_t) n * 4);
     P->Ap = f->dAp; P->Ai = f->dAi; P->Alen = f->dAlen; P->Aoff = f->dAoff; P->Alimbs = f->dAlimbs; P->q = f->dq;
     HIP_(hipEventCreate(&f->ev0)); HIP_(hipEventCreate(&f->ev1));
     if (!rc) { f->hs.ticket = 0; rc = slip_hip_factor_reset(f); }
@@ -2131,6 +2276,7 @@ static int launch_columns(slip_hip_factor *f, hipStream_t stream)
 extern "C" int slip_hip_factor_run(slip_hip_factor *f, int32_t kmax, void *stream_v)
 {
     if (!f || f->factors_only) return SLIP_HIP_INCORRECT_INPUT;
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
     hipStream_t stream = (hipStream_t) stream_v;
     SlipParams *P = &f->P;
     SlipState *h = &f->hs;
@@ -2357,6 +2503,311 @@ extern "C" int slip_hip_factor_set_prefix(slip_hip_factor *f, int32_t K,
     return rc;
 }
 
+/* ---- back to column K, and a column of the resident A replaced (no counterpart in the reference; cf. klu_refactor and the
+ * basis change of a simplex code).  REF LU is left-looking: columns 0..p-1 of L and U, their pivots and their row swaps
+ * depend on A(:, q[0..p-1]) alone, so after a change to the column at position p the first p columns still are the exact
+ * factorisation and slip_hip_factor_run goes on from there.  Everything happens on data already in HBM (slip_rewind_kernel,
+ * slip_splice_kernel, slip_offscan_kernel + slip_pack_kernel); only the new column crosses to the device. ---- */
+static void check_views_drop(slip_hip_factor *f)
+{
+    dev_free(f->chk_rp); dev_free(f->chk_re); dev_free(f->chk_rx); f->chk_rp = NULL; f->chk_re = NULL; f->chk_rx = NULL;
+    dev_free(f->chkt_rp); dev_free(f->chkt_re); dev_free(f->chkt_rx); f->chkt_rp = NULL; f->chkt_re = NULL; f->chkt_rx = NULL;
+}
+
+/* a device step failed after the handle's arrays had begun to change: it must not serve a mixed state */
+static int handle_broken(slip_hip_factor *f)
+{
+    f->broken = 1; f->last_status = SLIP_HIP_DEVICE_ERROR;
+    return SLIP_HIP_DEVICE_ERROR;
+}
+
+/* one thread per item of a service kernel's loop */
+static unsigned service_blocks(int64_t items)
+{
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+static int rewind_launch(SlipRewindArgs A, int phase, int64_t items, hipStream_t stream)
+{
+    A.phase = phase;
+#ifndef SLIP_EMULATE
+    hipLaunchKernelGGL(slip_rewind_kernel, dim3(service_blocks(items)), dim3(256), 0, stream, A);
+    CK(hipGetLastError());
+#else
+    (void) items;
+    emu::launch(2, 128, [A]() { slip_rewind_body(A); }, 256 * 1024, 1);
+#endif
+    return 0;
+}
+
+/* the handle as slip_hip_factor_run(f, K) from a reset would have left it, 0 < K < the committed columns.  *changed: the
+ * device arrays have been written (an error from then on breaks the handle). */
+static int rewind_device(slip_hip_factor *f, int32_t K, hipStream_t stream, int *changed)
+{
+    SlipParams *P = &f->P;
+    const int32_t n = f->n, Kold = f->hs.F;
+    int32_t *win = NULL, *rsave = NULL; unsigned long long *dout = NULL, hout[8];
+    int rc = 0;
+    A_(dev_alloc(&win, (int64_t) n - K)); A_(dev_alloc(&rsave, (int64_t) Kold - K)); A_(dev_alloc(&dout, 8));
+    if (!rc) {
+        if (f->rescaled) rescale_drop(f);
+        tview_drop(f);
+        *changed = 1;
+        /* tickets never go back; should they be about to wrap, every private row is untagged (as slip_hip_factor_reset) */
+        if (f->hs.ticket > (1 << 30)) {
+            HIP_(hipMemsetAsync(P->xrow, 0, (size_t)((int64_t) f->nworkers * n) * sizeof(SlipRow), stream));
+            f->hs.ticket = 0;
+        }
+        HIP_(hipMemsetAsync(win, 0x7f, (size_t)(n - K) * 4, stream));
+        HIP_(hipMemsetAsync(dout, 0, sizeof hout, stream));
+        SlipRewindArgs A; memset(&A, 0, sizeof A);
+        A.n = n; A.K = K; A.Kold = Kold;
+        A.row_perm = P->row_perm.p_; A.pinv = P->pinv.p_; A.Lready = P->Lready.p_; A.sw_row = P->sw_row.p_; A.sw_pos = P->sw_pos.p_;
+        A.win = win; A.rsave = rsave; A.Lp = P->Lp; A.Up = P->Up; A.Lo = P->Lo; A.Uo = P->Uo; A.Le = P->Le; A.Ue = P->Ue; A.out = dout;
+        A.lnz_max = f->hs.Lnz; A.unz_max = f->hs.Unz;
+        A_(rewind_launch(A, 0, Kold - K, stream));
+        A_(rewind_launch(A, 1, n - K, stream));
+        A_(rewind_launch(A, 2, n - K, stream));
+        A_(rewind_launch(A, 3, f->hs.Lnz > f->hs.Unz ? f->hs.Lnz : f->hs.Unz, stream));
+        HIP_(hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, stream));
+        HIP_(hipStreamSynchronize(stream));
+    }
+    dev_free(win); dev_free(rsave); dev_free(dout);
+    if (rc) return rc;
+    SlipState *h = &f->hs;
+    if ((int64_t) hout[2] > h->Lnz || (int64_t) hout[3] > h->Unz || (int64_t) hout[4] > h->Lnl || (int64_t) hout[5] > h->Unl) return SLIP_HIP_DEVICE_ERROR;
+    {
+        const int32_t ticket = h->ticket; const unsigned long long maxdig = h->c_maxdig;
+        memset(h, 0, sizeof *h);
+        h->ticket = ticket; h->c_maxdig = maxdig;         /* (an upper bound now) */
+        h->stop = INT64_MAX;
+    }
+    h->F = K; h->F2 = K; h->k_next = K; h->status_k = K; h->Fpiv = (int32_t) hout[6];
+    h->Lnl_exact = (int64_t) hout[0]; h->Unl_exact = (int64_t) hout[1];
+    h->Lnz = (int64_t) hout[2]; h->Unz = (int64_t) hout[3]; h->Lnl = (int64_t) hout[4]; h->Unl = (int64_t) hout[5];
+    TRY_(upload_state(f, stream));
+    CK(hipStreamSynchronize(stream));
+    f->last_status = 0; f->window_end = 0; f->kernel_ms = 0; f->launches = 0;
+    return SLIP_HIP_OK;
+}
+
+/* rewind to K <= the committed columns (checked by the callers); K equal to them: nothing to do */
+static int rewind_to(slip_hip_factor *f, int32_t K, hipStream_t stream)
+{
+    if (K == f->hs.F) return SLIP_HIP_OK;
+    if (K == 0) return slip_hip_factor_reset(f);
+    int changed = 0;
+    const int rc = rewind_device(f, K, stream, &changed);
+    if (rc && changed) return handle_broken(f);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_rewind(slip_hip_factor *f, int32_t K, const int32_t *q_tail, void *stream_v)
+{
+    if (!f || f->factors_only) return SLIP_HIP_INCORRECT_INPUT;
+    if (f->broken || f->last_status == SLIP_HIP_DEVICE_ERROR) return SLIP_HIP_DEVICE_ERROR;
+    const int32_t n = f->n;
+    if (K < 0 || K > f->hs.F) return SLIP_HIP_INCORRECT_INPUT;
+    if (!f->P.xd || !f->P.xrow) return SLIP_HIP_OUT_OF_MEMORY;
+    if (q_tail) {
+        /* a permutation of the ids at positions K..n-1 */
+        char *there = (char *) calloc((size_t) n, 1);
+        if (!there) return SLIP_HIP_OUT_OF_MEMORY;
+        int bad = 0;
+        for (int32_t p = K; p < n; p++) there[f->hq[p]] = 1;
+        for (int32_t p = K; p < n && !bad; p++) { const int32_t j = q_tail[p - K]; if (j < 0 || j >= n || there[j] != 1) bad = 1; else there[j] = 2; }
+        free(there);
+        if (bad) return SLIP_HIP_INCORRECT_INPUT;
+    }
+    TRY_(rewind_to(f, K, (hipStream_t) stream_v));
+    if (q_tail && K < n) {
+        if (hipMemcpy(f->dq + K, q_tail, (size_t)(n - K) * 4, hipMemcpyHostToDevice) != hipSuccess) return handle_broken(f);
+        memcpy(f->hq + K, q_tail, (size_t)(n - K) * 4);
+        check_views_drop(f);                              /* both are laid out by position */
+    }
+    return SLIP_HIP_OK;
+}
+
+/* the limbs the device counted for the live entries must be the host's figure: it sized the new slab */
+static int a_compact_total(const unsigned long long *bsum, int64_t blocks, int64_t live, hipStream_t stream)
+{
+    unsigned long long h[1024], total = 0;
+    CK(hipMemcpyAsync(h, bsum, (size_t) blocks * 8, hipMemcpyDeviceToHost, stream));
+    CK(hipStreamSynchronize(stream));
+    for (int64_t b = 0; b < blocks; b++) total += h[b];
+    return total == (unsigned long long) live ? 0 : SLIP_HIP_DEVICE_ERROR;
+}
+
+/* the dead limbs squeezed out of the slab of A: new offsets by a scan over the entries, the limbs moved entry by entry */
+static int a_compact(slip_hip_factor *f, hipStream_t stream)
+{
+    const int64_t nnz = f->annz, live = f->alimbs, newcap = live + live / 2 + 1;
+#ifndef SLIP_EMULATE
+    int64_t blocks = (nnz + 2047) / 2048; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
+#else
+    const int64_t blocks = 2;
+#endif
+    uint64_t *nl = NULL; int64_t *noff = NULL; unsigned long long *bsum = NULL;
+    int rc = 0;
+    A_(dev_alloc(&nl, newcap)); A_(dev_alloc(&noff, f->Acap_nz)); A_(dev_alloc(&bsum, blocks));
+    if (!rc) {
+        SlipOffScanArgs S; memset(&S, 0, sizeof S);
+        S.count = nnz; S.len = f->dAlen; S.off = noff; S.bsum = bsum;
+        SlipPackArgs A; memset(&A, 0, sizeof A);
+        A.count = nnz; A.len = f->dAlen; A.soff = f->dAoff; A.doff = noff; A.src = f->dAlimbs; A.dst = nl;
+#ifndef SLIP_EMULATE
+        for (int phase = 0; phase < 2 && !rc; phase++) {
+            S.phase = phase;
+            hipLaunchKernelGGL(slip_offscan_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, S);
+            HIP_(hipGetLastError());
+        }
+        A_(a_compact_total(bsum, blocks, live, stream));
+        if (!rc) {
+            int64_t pb = (nnz + 3) / 4; if (pb > 4096) pb = 4096; if (pb < 1) pb = 1;
+            hipLaunchKernelGGL(slip_pack_kernel, dim3((unsigned) pb), dim3(256), 0, stream, A);
+            HIP_(hipGetLastError());
+        }
+#else
+        uint64_t *tmp = (uint64_t *) calloc((size_t) blocks * 40, 8);
+        if (!tmp) rc = SLIP_HIP_OUT_OF_MEMORY;
+        for (int phase = 0; phase < 2 && !rc; phase++) {
+            S.phase = phase;
+            emu::launch((int) blocks, 128, [S, tmp]() { slip_offscan_body(S, tmp + 40 * slip_block()); }, 256 * 1024, 1);
+        }
+        free(tmp);
+        A_(a_compact_total(bsum, blocks, live, stream));
+        if (!rc) emu::launch(2, 128, [A]() { slip_pack_body(A); }, 256 * 1024, 1);
+#endif
+        HIP_(hipStreamSynchronize(stream));
+    }
+    if (rc) { dev_free(nl); dev_free(noff); dev_free(bsum); return rc; }
+    dev_free(f->dAlimbs); dev_free(f->dAoff); dev_free(bsum);
+    f->dAlimbs = nl; f->dAoff = noff; f->P.Alimbs = nl; f->P.Aoff = noff;
+    f->Acap_nl = newcap; f->Anl_used = live;
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_replace_column(slip_hip_factor *f, int32_t j, int32_t nz, const int32_t *rows, const int32_t *len,
+                                              const uint64_t *limbs, int64_t limbs_cap, void *stream_v)
+{
+    if (!f || f->factors_only) return SLIP_HIP_INCORRECT_INPUT;
+    if (f->broken || f->last_status == SLIP_HIP_DEVICE_ERROR) return SLIP_HIP_DEVICE_ERROR;
+    const int32_t n = f->n;
+    if (j < 0 || j >= n || nz < 1 || !rows || !len || !limbs || limbs_cap < 0) return SLIP_HIP_INCORRECT_INPUT;
+    if (!f->P.xd || !f->P.xrow) return SLIP_HIP_OUT_OF_MEMORY;
+    hipStream_t stream = (hipStream_t) stream_v;
+    {
+        int64_t total = 0;
+        for (int32_t t = 0; t < nz; t++) {
+            if (rows[t] < 0 || rows[t] >= n) return SLIP_HIP_INCORRECT_INPUT;
+            total += len[t] < 0 ? -(int64_t) len[t] : len[t];
+            if (total > limbs_cap) return SLIP_HIP_INCORRECT_INPUT;
+        }
+    }
+    /* the column as prepare_A would have laid it out: a repeated row once, with its LAST value; signed digit counts, high
+     * zero limbs trimmed; offsets from the start of the column's limbs */
+    int32_t *last = (int32_t *) malloc((size_t) n * 4), *cAi = (int32_t *) malloc((size_t) nz * 4), *cAlen = (int32_t *) malloc((size_t) nz * 4);
+    int64_t *cAoff = (int64_t *) malloc((size_t) nz * 8);
+    uint64_t *cl = (uint64_t *) malloc((size_t)(limbs_cap > 0 ? limbs_cap : 1) * 8);
+    int32_t *oldlen = NULL;
+    int64_t cnz = 0, cnl = 0; int32_t cmaxdig = 1;
+    int rc = !last || !cAi || !cAlen || !cAoff || !cl ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    if (!rc) {
+        for (int32_t t = 0; t < nz; t++) last[rows[t]] = t;
+        int64_t in = 0;
+        for (int32_t t = 0; t < nz; t++) {
+            const int64_t l0 = len[t] < 0 ? -(int64_t) len[t] : len[t];
+            if (last[rows[t]] == t) {
+                const int32_t dig = limb_digits(limbs + in, l0);
+                const int64_t l = (dig + 1) >> 1;
+                cAi[cnz] = rows[t]; cAlen[cnz] = len[t] < 0 ? -dig : dig; cAoff[cnz] = cnl;
+                memcpy(cl + cnl, limbs + in, (size_t) l * 8);
+                if (dig > cmaxdig) cmaxdig = dig;
+                cnl += l; cnz++;
+            }
+            in += l0;
+        }
+    }
+    /* where the column stands: its position in q, its extent in the resident arrays and the limbs it holds there */
+    int32_t p = 0;
+    int64_t ap[2] = {0, 0}, old_l = 0;
+    if (!rc) {
+        while (p < n && f->hq[p] != j) p++;
+        DOWN_(ap, f->dAp + j, 16);
+        if (!rc && (ap[0] < 0 || ap[1] < ap[0] || ap[1] > f->annz)) rc = SLIP_HIP_DEVICE_ERROR;
+    }
+    const int64_t nz_old = ap[1] - ap[0], nnz_new = f->annz - nz_old + cnz;
+    if (!rc && nz_old > 0) {
+        if (!(oldlen = (int32_t *) malloc((size_t) nz_old * 4))) rc = SLIP_HIP_OUT_OF_MEMORY;
+        DOWN_(oldlen, f->dAlen + ap[0], (size_t) nz_old * 4);
+        if (!rc) for (int64_t t = 0; t < nz_old; t++) old_l += ((oldlen[t] < 0 ? -(int64_t) oldlen[t] : oldlen[t]) + 1) >> 1;
+    }
+    /* the new entry arrays: the old capacity, doubled when it is short, never beyond twice the live entries plus the
+     * initial allocation */
+    int64_t ncap = f->Acap_nz;
+    if (nnz_new > ncap) ncap = 2 * ncap > nnz_new ? 2 * ncap : nnz_new;
+    if (ncap > 2 * nnz_new + f->A0_nz) ncap = 2 * nnz_new + f->A0_nz;
+    int32_t *nAi = NULL, *nAlen = NULL; int64_t *nAoff = NULL;
+    A_(dev_alloc(&nAi, ncap)); A_(dev_alloc(&nAlen, ncap)); A_(dev_alloc(&nAoff, ncap));
+    if (rc) {
+        /* nothing of the handle has changed */
+        dev_free(nAi); dev_free(nAlen); dev_free(nAoff);
+        free(last); free(cAi); free(cAlen); free(cAoff); free(cl); free(oldlen);
+        return rc;
+    }
+    /* from here on a failure leaves a mixed state behind: the handle then refuses further use */
+    if (p < f->hs.F) rc = rewind_to(f, p, stream);
+    /* the limbs: appended to the slab, which doubles when it is full */
+    if (!rc && f->Anl_used + cnl > f->Acap_nl) {
+        const int64_t need = f->Anl_used + cnl, cap = 2 * f->Acap_nl > need ? 2 * f->Acap_nl : need;
+        rc = dev_grow(&f->dAlimbs, f->Anl_used, cap);
+        if (!rc) { f->Acap_nl = cap; f->P.Alimbs = f->dAlimbs; }
+    }
+    if (!rc) for (int64_t t = 0; t < cnz; t++) cAoff[t] += f->Anl_used;
+    UP_(f->dAlimbs + f->Anl_used, cl, (size_t) cnl * 8);
+    UP_(nAi + ap[0], cAi, (size_t) cnz * 4); UP_(nAlen + ap[0], cAlen, (size_t) cnz * 4); UP_(nAoff + ap[0], cAoff, (size_t) cnz * 8);
+    if (!rc) {
+        SlipSpliceArgs A; memset(&A, 0, sizeof A);
+        A.n = n; A.j = j; A.a0 = ap[0]; A.a1 = ap[1]; A.nz_new = cnz; A.nnz_old = f->annz;
+        A.Ai = f->dAi; A.Alen = f->dAlen; A.Aoff = f->dAoff; A.nAi = nAi; A.nAlen = nAlen; A.nAoff = nAoff; A.Ap = f->dAp;
+#ifndef SLIP_EMULATE
+        hipLaunchKernelGGL(slip_splice_kernel, dim3(service_blocks(f->annz > n ? f->annz : n)), dim3(256), 0, stream, A);
+        HIP_(hipGetLastError());
+#else
+        emu::launch(2, 128, [A]() { slip_splice_body(A); }, 256 * 1024, 1);
+#endif
+        HIP_(hipStreamSynchronize(stream));
+    }
+    free(last); free(cAi); free(cAlen); free(cAoff); free(cl); free(oldlen);
+    if (rc) { dev_free(nAi); dev_free(nAlen); dev_free(nAoff); handle_broken(f); return rc == SLIP_HIP_OUT_OF_MEMORY ? rc : SLIP_HIP_DEVICE_ERROR; }
+    dev_free(f->dAi); dev_free(f->dAlen); dev_free(f->dAoff);
+    f->dAi = nAi; f->dAlen = nAlen; f->dAoff = nAoff; f->P.Ai = nAi; f->P.Alen = nAlen; f->P.Aoff = nAoff;
+    f->Acap_nz = ncap; f->annz = nnz_new; f->Anl_used += cnl; f->alimbs += cnl - old_l;
+    if (cmaxdig > f->amaxdig) f->amaxdig = cmaxdig;       /* (an upper bound: a narrower column does not lower it) */
+    check_views_drop(f);
+    /* more dead limbs than live ones, or a slab larger than twice its live content plus the initial allocation: compact */
+    if (f->Anl_used - f->alimbs > f->alimbs || f->Acap_nl > 2 * f->alimbs + f->A0_nl) {
+        const int e = a_compact(f, stream);
+        if (e) { handle_broken(f); return e; }
+    }
+    /* values wider than the private x rows were sized for: the stride grows now rather than in the first launch */
+    if (2 * (int64_t) cmaxdig + 8 > f->P.xcap) {
+        const int e = grow_x_keep(f, 2 * (int64_t) cmaxdig + 8, f->hs.F);
+        if (e == SLIP_HIP_DEVICE_ERROR) return handle_broken(f);
+        if (e) return e;                                  /* the handle keeps its old stride; the run would grow it */
+    }
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_a_storage(const slip_hip_factor *f, int64_t out[4])
+{
+    if (!f || !out || f->factors_only) return SLIP_HIP_INCORRECT_INPUT;
+    out[0] = f->annz; out[1] = f->Acap_nz; out[2] = f->alimbs; out[3] = f->Acap_nl;
+    return SLIP_HIP_OK;
+}
+
 /* ---- REF triangular solves on the resident factors (SLIP_LU_solve.c:41-86) ---- */
 #ifndef SLIP_SOLVE_HELPERS
 #define SLIP_SOLVE_HELPERS 16
@@ -2501,6 +2952,7 @@ static int solve_device(slip_hip_factor *f, int transpose, int32_t nrhs, const i
     memset(out, 0, sizeof *out);
     if (!f || nrhs <= 0 || !blen || !blimbs) return SLIP_HIP_INCORRECT_INPUT;
     const int32_t n = f->n;
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
     if (f->hs.F != n) return SLIP_HIP_INCORRECT_INPUT;          /* needs the complete factorisation */
     if (!f->P.xd || !f->P.xrow) return SLIP_HIP_OUT_OF_MEMORY;
     SlipParams *P = &f->P;
@@ -3310,6 +3762,7 @@ static int check_on_handle(slip_hip_factor *f, int transpose, int32_t nrhs,
 {
     if (!f || f->factors_only || nrhs < 1 || !blen || !blimbs || !xlen || !xlimbs) return SLIP_HIP_INCORRECT_INPUT;
     const int32_t n = f->n;
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
     if (f->hs.F != n || f->last_status == SLIP_HIP_DEVICE_ERROR) return SLIP_HIP_INCORRECT_INPUT;   /* needs the complete factorisation */
     const int64_t ne = (int64_t) n * nrhs;
     SlipSlab bs, xs;
