@@ -89,19 +89,53 @@ def _int_limbs(v):
     return (-len(limbs) if v < 0 else len(limbs)), np.array(limbs if limbs else [0], np.uint64)
 
 
+def _rhs(n, blen, blimbs, nrhs):
+    """the right-hand sides of a solve-and-convert as contiguous arrays (the limbs never empty) and nrhs as an int"""
+    blen = np.ascontiguousarray(blen, dtype=np.int32)
+    blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
+    nrhs = int(nrhs)
+    if nrhs >= 1 and blen.size != n * nrhs:
+        raise ValueError("blen must hold n*nrhs entries")
+    return blen, (blimbs if blimbs.size else np.zeros(1, dtype=np.uint64)), nrhs
+
+
+def _scale_args(scale):
+    """a scale -- None, a pair (num, den) of Python ints or a Fraction -- as the four arguments of the C ABI: each part's
+    signed limb count and a pointer to its limbs (None: the part is 1; the pointer keeps its array alive)"""
+    if scale is None:
+        return 0, None, 0, None
+    num, den = (scale.numerator, scale.denominator) if hasattr(scale, "numerator") else scale
+    (snlen, sn), (sdlen, sd) = _int_limbs(num), _int_limbs(den)
+    return snlen, sn.ctypes.data_as(C.c_void_p), sdlen, sd.ctypes.data_as(C.c_void_p)
+
+
+def _quot_args(n, nrhs, xlen, xlimbs, dlen, dlimbs, where):
+    """n, nrhs and the leading arguments of slip_hip_solution_to_*: n, nrhs and the two slabs with the capacities they really
+    have (the pointers keep their arrays alive)"""
+    n, nrhs = int(n), int(nrhs)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
+    if nrhs >= 1 and (xlen.size != n * nrhs or dlen.size != nrhs):
+        raise ValueError(f"{where}: xlen needs n*nrhs entries, dlen nrhs")
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    return n, nrhs, (n, nrhs, ptr(xlen), ptr(xlimbs), xcap, ptr(dlen), ptr(dlimbs), dcap)
+
+
+def _paths(fn, *args):
+    """the four path counters a *_paths entry point fills"""
+    out = np.zeros(4, np.int64)
+    fn(*args, out.ctypes.data)
+    return [int(v) for v in out]
+
+
 def solution_to_double(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, lib_path=None):
     """Numerators over one nonzero denominator per right-hand side -> float64[nrhs, n] on the device
     (slip_hip_solution_to_double): every entry is the exact rational truncated toward zero onto the double grid, bit for bit
     what mpq_get_d returns.  x as limb slabs (n entries per right-hand side), output in the order of the input."""
     lib = _lib.load(lib_path)
-    n, nrhs = int(n), int(nrhs)
-    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
-    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
-    if nrhs >= 1 and (xlen.size != n * nrhs or dlen.size != nrhs):
-        raise ValueError("solution_to_double: xlen needs n*nrhs entries, dlen nrhs")
+    n, nrhs, args = _quot_args(n, nrhs, xlen, xlimbs, dlen, dlimbs, "solution_to_double")
     out = np.zeros((max(nrhs, 1), max(n, 1)), np.float64)
-    rc = lib.slip_hip_solution_to_double(n, nrhs, xlen.ctypes.data, xlimbs.ctypes.data, xcap, dlen.ctypes.data, dlimbs.ctypes.data,
-                                         dcap, out.ctypes.data, None)
+    rc = lib.slip_hip_solution_to_double(*args, out.ctypes.data, None)
     if rc:
         raise SlipError(rc, "slip_hip_solution_to_double")
     return out[:nrhs, :n]
@@ -122,14 +156,10 @@ def solution_to_rational(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, lib_path=None):
     (slip_hip_solution_to_rational): (numlen, numlimbs, denlen, denlimbs), two compact limb slabs of n * nrhs entries in the
     order of the input, GMP's canonical form -- den > 0, the sign on num, 0 as 0 / 1."""
     lib = _lib.load(lib_path)
-    n, nrhs = int(n), int(nrhs)
-    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
-    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
-    if nrhs >= 1 and (xlen.size != n * nrhs or dlen.size != nrhs):
-        raise ValueError("solution_to_rational: xlen needs n*nrhs entries, dlen nrhs")
+    n, nrhs, args = _quot_args(n, nrhs, xlen, xlimbs, dlen, dlimbs, "solution_to_rational")
     pnl, pnx, nnl, pdl, pdx, dnl = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
-    rc = lib.slip_hip_solution_to_rational(n, nrhs, xlen.ctypes.data, xlimbs.ctypes.data, xcap, dlen.ctypes.data, dlimbs.ctypes.data,
-                                           dcap, C.byref(pnl), C.byref(pnx), C.byref(nnl), C.byref(pdl), C.byref(pdx), C.byref(dnl), None)
+    rc = lib.slip_hip_solution_to_rational(*args, C.byref(pnl), C.byref(pnx), C.byref(nnl), C.byref(pdl), C.byref(pdx), C.byref(dnl),
+                                           None)
     if rc:
         raise SlipError(rc, "slip_hip_solution_to_rational")
     return _take_slab(lib, pnl, pnx, nnl, n * nrhs) + _take_slab(lib, pdl, pdx, dnl, n * nrhs)
@@ -137,9 +167,7 @@ def solution_to_rational(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, lib_path=None):
 
 def solution_to_rational_paths(lib_path=None):
     """entries of this thread's last solution_to_rational by the path that settled them, as Factorization.to_rational_paths"""
-    out = np.zeros(4, np.int64)
-    _lib.load(lib_path).slip_hip_solution_to_rational_paths(out.ctypes.data)
-    return [int(v) for v in out]
+    return _paths(_lib.load(lib_path).slip_hip_solution_to_rational_paths)
 
 
 def _mpfr_outputs(count, prec):
@@ -155,15 +183,10 @@ def solution_to_mpfr(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, prec=128, rnd=0, lib
     mpfr_set_q leaves under the rounding mode rnd (MPFR_RNDN 0, RNDZ 1, RNDU 2, RNDD 3, RNDA 4): sign 0 / +1 / -1, MPFR's
     exponent, the mantissa left-aligned in ceil(prec / 64) limbs (mant[t, -1] is the top limb), the ternary value."""
     lib = _lib.load(lib_path)
-    n, nrhs = int(n), int(nrhs)
-    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
-    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
-    if nrhs >= 1 and (xlen.size != n * nrhs or dlen.size != nrhs):
-        raise ValueError("solution_to_mpfr: xlen needs n*nrhs entries, dlen nrhs")
+    n, nrhs, args = _quot_args(n, nrhs, xlen, xlimbs, dlen, dlimbs, "solution_to_mpfr")
     count = max(n, 0) * max(nrhs, 0)
     sign, exp, mant, tern = _mpfr_outputs(count, prec)
-    rc = lib.slip_hip_solution_to_mpfr(n, nrhs, xlen.ctypes.data, xlimbs.ctypes.data, xcap, dlen.ctypes.data, dlimbs.ctypes.data,
-                                       dcap, int(prec), int(rnd), sign.ctypes.data, exp.ctypes.data, mant.ctypes.data,
+    rc = lib.slip_hip_solution_to_mpfr(*args, int(prec), int(rnd), sign.ctypes.data, exp.ctypes.data, mant.ctypes.data,
                                        tern.ctypes.data, None)
     if rc:
         raise SlipError(rc, "slip_hip_solution_to_mpfr")
@@ -172,9 +195,7 @@ def solution_to_mpfr(n, xlen, xlimbs, dlen, dlimbs, nrhs=1, prec=128, rnd=0, lib
 
 def solution_to_mpfr_paths(lib_path=None):
     """entries of this thread's last solution_to_mpfr by the path that settled them, as Factorization.to_mpfr_paths"""
-    out = np.zeros(4, np.int64)
-    _lib.load(lib_path).slip_hip_solution_to_mpfr_paths(out.ctypes.data)
-    return [int(v) for v in out]
+    return _paths(_lib.load(lib_path).slip_hip_solution_to_mpfr_paths)
 
 
 def matgen(n, density, bits, seed, lib_path=None):
@@ -407,12 +428,7 @@ class Factorization:
                                    C.byref(pl), C.byref(px), C.byref(nl), C.c_void_p(stream or 0))
         if rc:
             raise SlipError(rc, fn)
-        xlen = np.ctypeslib.as_array(C.cast(pl, C.POINTER(C.c_int32)), shape=(self.n * nrhs,)).copy()
-        xlimbs = (np.ctypeslib.as_array(C.cast(px, C.POINTER(C.c_uint64)), shape=(nl.value,)).copy()
-                  if nl.value else np.zeros(0, np.uint64))
-        self.lib.slip_hip_free(pl)
-        self.lib.slip_hip_free(px)
-        return xlen, xlimbs
+        return _take_slab(self.lib, pl, px, nl, self.n * nrhs)
 
     def solve_double(self, blen, blimbs, nrhs=1, transpose=False, scale=None, stream=None):
         """Solve and convert on the device (slip_hip_factor_solve_double): float64[nrhs, n], every entry the exact rational
@@ -420,23 +436,10 @@ class Factorization:
         Only the doubles come back.  b as `solve` takes it, the result in ORIGINAL column order (x[c, q[p]]); with
         transpose=True b as `solve_transpose` takes it, the result by original row id.  scale: a pair (num, den) of Python
         ints or a Fraction, both parts nonzero."""
-        blen = np.ascontiguousarray(blen, dtype=np.int32)
-        blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
-        nrhs = int(nrhs)
-        if nrhs >= 1 and blen.size != self.n * nrhs:
-            raise ValueError("blen must hold n*nrhs entries")
-        if blimbs.size == 0:
-            blimbs = np.zeros(1, dtype=np.uint64)
-        if scale is None:
-            sn = sd = (0, None)
-        else:
-            num, den = (scale.numerator, scale.denominator) if hasattr(scale, "numerator") else scale
-            sn, sd = _int_limbs(num), _int_limbs(den)
+        blen, blimbs, nrhs = _rhs(self.n, blen, blimbs, nrhs)
         out = np.zeros((max(nrhs, 1), self.n), np.float64)
         rc = self.lib.slip_hip_factor_solve_double(self.h, int(bool(transpose)), nrhs, blen.ctypes.data, blimbs.ctypes.data,
-                                                   sn[0], None if sn[1] is None else sn[1].ctypes.data,
-                                                   sd[0], None if sd[1] is None else sd[1].ctypes.data,
-                                                   out.ctypes.data, C.c_void_p(stream or 0))
+                                                   *_scale_args(scale), out.ctypes.data, C.c_void_p(stream or 0))
         if rc:
             raise SlipError(rc, "slip_hip_factor_solve_double")
         return out[:nrhs]
@@ -454,23 +457,10 @@ class Factorization:
         c*n + j the exact rational scale * xnum / det in lowest terms, GMP's canonical form (den > 0, the sign on num, 0 as
         0 / 1: what SLIP_solve_mpq returns).  Only these two compact slabs come back.  b, transpose, scale and the order of
         the result as `solve_double`: ORIGINAL column order for the plain solve, original row id for the transposed one."""
-        blen = np.ascontiguousarray(blen, dtype=np.int32)
-        blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
-        nrhs = int(nrhs)
-        if nrhs >= 1 and blen.size != self.n * nrhs:
-            raise ValueError("blen must hold n*nrhs entries")
-        if blimbs.size == 0:
-            blimbs = np.zeros(1, dtype=np.uint64)
-        if scale is None:
-            sn = sd = (0, None)
-        else:
-            num, den = (scale.numerator, scale.denominator) if hasattr(scale, "numerator") else scale
-            sn, sd = _int_limbs(num), _int_limbs(den)
+        blen, blimbs, nrhs = _rhs(self.n, blen, blimbs, nrhs)
         pnl, pnx, nnl, pdl, pdx, dnl = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
         rc = self.lib.slip_hip_factor_solve_rational(self.h, int(bool(transpose)), nrhs, blen.ctypes.data, blimbs.ctypes.data,
-                                                     sn[0], None if sn[1] is None else sn[1].ctypes.data,
-                                                     sd[0], None if sd[1] is None else sd[1].ctypes.data,
-                                                     C.byref(pnl), C.byref(pnx), C.byref(nnl), C.byref(pdl), C.byref(pdx), C.byref(dnl),
+                                                     *_scale_args(scale), C.byref(pnl), C.byref(pnx), C.byref(nnl), C.byref(pdl), C.byref(pdx), C.byref(dnl),
                                                      C.c_void_p(stream or 0))
         if rc:
             raise SlipError(rc, "slip_hip_factor_solve_rational")
@@ -483,9 +473,7 @@ class Factorization:
     def to_rational_paths(self):
         """entries of the last solve_rational settled by [the lane pass, the register wave pass with g = 1, the same with
         g > 1, the memory class]"""
-        out = np.zeros(4, np.int64)
-        self.lib.slip_hip_factor_to_rational_paths(self.h, out.ctypes.data)
-        return [int(v) for v in out]
+        return _paths(self.lib.slip_hip_factor_to_rational_paths, self.h)
 
     def solve_mpfr(self, blen, blimbs, nrhs=1, transpose=False, scale=None, prec=128, rnd=0, stream=None):
         """Solve and round on the device (slip_hip_factor_solve_mpfr): (sign, exp, mant, ternary), entry c*n + j the exact
@@ -493,24 +481,11 @@ class Factorization:
         RNDD 3, RNDA 4), as mpfr_set_q leaves it (what SLIP_solve_mpfr returns): sign int8 (0 for +0), MPFR's exponent int64,
         mant uint64[nrhs*n, ceil(prec / 64)] left-aligned (mant[t, -1] is the top limb), the ternary value int8.  Only these
         come back.  b, transpose, scale and the order of the result as `solve_double`."""
-        blen = np.ascontiguousarray(blen, dtype=np.int32)
-        blimbs = np.ascontiguousarray(blimbs, dtype=np.uint64)
-        nrhs = int(nrhs)
-        if nrhs >= 1 and blen.size != self.n * nrhs:
-            raise ValueError("blen must hold n*nrhs entries")
-        if blimbs.size == 0:
-            blimbs = np.zeros(1, dtype=np.uint64)
-        if scale is None:
-            sn = sd = (0, None)
-        else:
-            num, den = (scale.numerator, scale.denominator) if hasattr(scale, "numerator") else scale
-            sn, sd = _int_limbs(num), _int_limbs(den)
+        blen, blimbs, nrhs = _rhs(self.n, blen, blimbs, nrhs)
         count = self.n * max(nrhs, 0)
         sign, exp, mant, tern = _mpfr_outputs(count, prec)
         rc = self.lib.slip_hip_factor_solve_mpfr(self.h, int(bool(transpose)), nrhs, blen.ctypes.data, blimbs.ctypes.data,
-                                                 sn[0], None if sn[1] is None else sn[1].ctypes.data,
-                                                 sd[0], None if sd[1] is None else sd[1].ctypes.data,
-                                                 int(prec), int(rnd), sign.ctypes.data, exp.ctypes.data, mant.ctypes.data,
+                                                 *_scale_args(scale), int(prec), int(rnd), sign.ctypes.data, exp.ctypes.data, mant.ctypes.data,
                                                  tern.ctypes.data, C.c_void_p(stream or 0))
         if rc:
             raise SlipError(rc, "slip_hip_factor_solve_mpfr")
@@ -523,9 +498,7 @@ class Factorization:
     def to_mpfr_paths(self):
         """entries of the last solve_mpfr settled by [the lane pass within 64 bits, the wave pass with a denominator of at
         most 256 digits, the wave pass with a wider one, as zero]"""
-        out = np.zeros(4, np.int64)
-        self.lib.slip_hip_factor_to_mpfr_paths(self.h, out.ctypes.data)
-        return [int(v) for v in out]
+        return _paths(self.lib.slip_hip_factor_to_mpfr_paths, self.h)
 
     def check(self, blen, blimbs, xlen, xlimbs, nrhs=1, stream=None):
         """Exact check of a solve on the device (slip_hip_factor_check): A(:,q) xnum_c == det b_c, with b as `solve` takes

@@ -2521,25 +2521,107 @@ static int handle_broken(slip_hip_factor *f)
     return SLIP_HIP_DEVICE_ERROR;
 }
 
-/* one thread per item of a service kernel's loop */
-static unsigned service_blocks(int64_t items)
+/* ---- the host side every service kernel shares (one kernel argument record, four waves a workgroup; the emulator runs
+ * the same body as two workgroups of two waves, whatever the item count): the grids, the launch, the timed section ---- */
+#ifndef SLIP_EMULATE
+#define SERVICE_WAVES 4
+#else
+#define SERVICE_WAVES 2
+#endif
+
+static int64_t service_grid(int64_t items, int64_t per_block)
 {
-    int64_t blocks = (items + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
+#ifndef SLIP_EMULATE
+    const int64_t blocks = (items + per_block - 1) / per_block;
+    return blocks > 4096 ? 4096 : blocks < 1 ? 1 : blocks;
+#else
+    (void) items; (void) per_block;
+    return 2;
+#endif
+}
+/* one thread per item of a service kernel's loop */
+static int64_t service_blocks(int64_t items) { return service_grid(items, 64 * SERVICE_WAVES); }
+/* one wave per item */
+static int64_t wave_blocks(int64_t items) { return service_grid(items, SERVICE_WAVES); }
+
+/* no more workgroups than keep the waves' scratch, per_wave digits each, within 256 MiB */
+static int64_t fit_scratch(int64_t blocks, int64_t per_wave)
+{
+#ifndef SLIP_EMULATE
+    const int64_t fit = ((int64_t) 256 << 20) / (SERVICE_WAVES * per_wave * 4);
+    if (blocks > fit) blocks = fit;
+    return blocks < 1 ? 1 : blocks;
+#else
+    (void) per_wave;
+    return blocks;
+#endif
+}
+
+/* the grid of a kernel whose waves take `chunk` entries per round: few entries are spread one to a wave, many fill the lanes of
+ * 4096 waves; at most block_cap workgroups, and no more than fit_scratch allows */
+struct SlipWaveGrid { int64_t blocks, chunk; };
+static SlipWaveGrid wave_grid(int64_t ne, int64_t per_wave, int64_t block_cap)
+{
+    SlipWaveGrid g;
+#ifndef SLIP_EMULATE
+    g.chunk = (ne + 4095) / 4096;
+    if (g.chunk > 64) g.chunk = 64;
+    g.blocks = (ne + g.chunk * SERVICE_WAVES - 1) / (g.chunk * SERVICE_WAVES);
+    if (g.blocks > block_cap) g.blocks = block_cap;
+#else
+    (void) ne; (void) block_cap;
+    g.chunk = 5; g.blocks = 2;
+#endif
+    g.blocks = fit_scratch(g.blocks, per_wave);
+    return g;
+}
+
+/* SERVICE_LAUNCH(X, blocks, stream, A): slip_X_kernel(A) on the stream (the emulator: slip_X_body(A), at once); the launch's
+ * error is the result; nothing is synchronised.  Not for slip_offscan and slip_tview_scan, whose emulated bodies take the
+ * array that is __shared__ on the device: those two sites launch by hand. */
+template <class Args> static int service_launch(void (*entry)(Args), int64_t blocks, hipStream_t stream, const Args &A)
+{
+#ifndef SLIP_EMULATE
+    hipLaunchKernelGGL(entry, dim3((unsigned) blocks), dim3(64 * SERVICE_WAVES), 0, stream, A);
+    CK(hipGetLastError());
+#else
+    (void) stream;
+    emu::launch((int) blocks, 64 * SERVICE_WAVES, [entry, A]() { entry(A); }, 256 * 1024, 1);
+#endif
+    return 0;
+}
+#ifndef SLIP_EMULATE
+#define SERVICE_LAUNCH(X, blocks, stream, A) service_launch(slip_##X##_kernel, blocks, stream, A)
+#else
+#define SERVICE_LAUNCH(X, blocks, stream, A) service_launch(slip_##X##_body, blocks, stream, A)
+#endif
+
+/* a timed section of a stream: begin, the launches, end (which waits for them); the events go with the record */
+namespace {                                               /* (its member functions are no symbols of the library) */
+struct SlipTimed {
+    hipEvent_t ev0 = NULL, ev1 = NULL;
+    int begin(hipStream_t stream)
+    {
+        CK(hipEventCreate(&ev0)); CK(hipEventCreate(&ev1));
+        CK(hipEventRecord(ev0, stream));
+        return 0;
+    }
+    int end(hipStream_t stream, double *ms_out)
+    {
+        float ms = 0;
+        CK(hipEventRecord(ev1, stream)); CK(hipStreamSynchronize(stream));
+        CK(hipEventElapsedTime(&ms, ev0, ev1));
+        if (ms_out) *ms_out = ms;
+        return 0;
+    }
+    ~SlipTimed() { if (ev0) hipEventDestroy(ev0); if (ev1) hipEventDestroy(ev1); }
+};
 }
 
 static int rewind_launch(SlipRewindArgs A, int phase, int64_t items, hipStream_t stream)
 {
     A.phase = phase;
-#ifndef SLIP_EMULATE
-    hipLaunchKernelGGL(slip_rewind_kernel, dim3(service_blocks(items)), dim3(256), 0, stream, A);
-    CK(hipGetLastError());
-#else
-    (void) items;
-    emu::launch(2, 128, [A]() { slip_rewind_body(A); }, 256 * 1024, 1);
-#endif
-    return 0;
+    return SERVICE_LAUNCH(rewind, service_blocks(items), stream, A);
 }
 
 /* the handle as slip_hip_factor_run(f, K) from a reset would have left it, 0 < K < the committed columns.  *changed: the
@@ -2657,16 +2739,11 @@ static int a_compact(slip_hip_factor *f, hipStream_t stream)
         S.count = nnz; S.len = f->dAlen; S.off = noff; S.bsum = bsum;
         SlipPackArgs A; memset(&A, 0, sizeof A);
         A.count = nnz; A.len = f->dAlen; A.soff = f->dAoff; A.doff = noff; A.src = f->dAlimbs; A.dst = nl;
+        /* (by hand: the emulated scan takes a block's share of tmp, which is __shared__ on the device) */
 #ifndef SLIP_EMULATE
         for (int phase = 0; phase < 2 && !rc; phase++) {
             S.phase = phase;
             hipLaunchKernelGGL(slip_offscan_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, S);
-            HIP_(hipGetLastError());
-        }
-        A_(a_compact_total(bsum, blocks, live, stream));
-        if (!rc) {
-            int64_t pb = (nnz + 3) / 4; if (pb > 4096) pb = 4096; if (pb < 1) pb = 1;
-            hipLaunchKernelGGL(slip_pack_kernel, dim3((unsigned) pb), dim3(256), 0, stream, A);
             HIP_(hipGetLastError());
         }
 #else
@@ -2677,9 +2754,9 @@ static int a_compact(slip_hip_factor *f, hipStream_t stream)
             emu::launch((int) blocks, 128, [S, tmp]() { slip_offscan_body(S, tmp + 40 * slip_block()); }, 256 * 1024, 1);
         }
         free(tmp);
-        A_(a_compact_total(bsum, blocks, live, stream));
-        if (!rc) emu::launch(2, 128, [A]() { slip_pack_body(A); }, 256 * 1024, 1);
 #endif
+        A_(a_compact_total(bsum, blocks, live, stream));
+        A_(SERVICE_LAUNCH(pack, wave_blocks(nnz), stream, A));
         HIP_(hipStreamSynchronize(stream));
     }
     if (rc) { dev_free(nl); dev_free(noff); dev_free(bsum); return rc; }
@@ -2772,12 +2849,7 @@ extern "C" int slip_hip_factor_replace_column(slip_hip_factor *f, int32_t j, int
         SlipSpliceArgs A; memset(&A, 0, sizeof A);
         A.n = n; A.j = j; A.a0 = ap[0]; A.a1 = ap[1]; A.nz_new = cnz; A.nnz_old = f->annz;
         A.Ai = f->dAi; A.Alen = f->dAlen; A.Aoff = f->dAoff; A.nAi = nAi; A.nAlen = nAlen; A.nAoff = nAoff; A.Ap = f->dAp;
-#ifndef SLIP_EMULATE
-        hipLaunchKernelGGL(slip_splice_kernel, dim3(service_blocks(f->annz > n ? f->annz : n)), dim3(256), 0, stream, A);
-        HIP_(hipGetLastError());
-#else
-        emu::launch(2, 128, [A]() { slip_splice_body(A); }, 256 * 1024, 1);
-#endif
+        A_(SERVICE_LAUNCH(splice, service_blocks(f->annz > n ? f->annz : n), stream, A));
         HIP_(hipStreamSynchronize(stream));
     }
     free(last); free(cAi); free(cAlen); free(cAoff); free(cl); free(oldlen);
@@ -2865,15 +2937,7 @@ static SlipTViewArgs tview_args(const slip_hip_factor *f)
 static int tview_launch(SlipTViewArgs A, int phase, hipStream_t stream)
 {
     A.phase = phase;
-#ifndef SLIP_EMULATE
-    int64_t blocks = phase == 2 ? ((int64_t) A.n + 255) / 256 : (2 * (int64_t) A.n + 3) / 4;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(slip_tview_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, A);
-    CK(hipGetLastError());
-#else
-    emu::launch(2, 128, [A]() { slip_tview_body(A); }, 256 * 1024, 1);
-#endif
-    return 0;
+    return SERVICE_LAUNCH(tview, phase == 2 ? service_blocks(A.n) : wave_blocks(2 * (int64_t) A.n), stream, A);
 }
 
 /* the view's inverse cache follows the handle's stride (a GROW_X reallocates both): a new one starts empty, so the pivot
@@ -2907,6 +2971,7 @@ static int tview_build(slip_hip_factor *f, hipStream_t stream)
         HIP_(hipEventRecord(f->ev0, stream));
         HIP_(hipMemsetAsync(cnt, 0, (size_t) n * 8, stream));
         A_(tview_launch(A, 0, stream));
+        /* (by hand: one workgroup of 1024 threads, and the emulated scan takes the tmp that is __shared__ on the device) */
 #ifndef SLIP_EMULATE
         if (!rc) { hipLaunchKernelGGL(slip_tview_scan_kernel, dim3(1), dim3(1024), 0, stream, A); HIP_(hipGetLastError()); }
 #else
@@ -3091,53 +3156,71 @@ extern "C" double slip_hip_factor_solve_transpose_ms(const slip_hip_factor *f, d
 /* ---- solutions as doubles (SLIP_solve_double's tail: SLIP_permute_x, SLIP_scale_x, SLIP_get_double_soln; kernels:
  * slip_todouble_kernel, slip_scale_kernel) ---- */
 
-/* one conversion on the device: numerators (entry c*n + p) and one denominator per right-hand side, all device arrays of signed
- * digit counts, limb offsets and limbs; dmaxdig: digits of the widest denominator; doidx: where entry p of a right-hand side
- * goes (device, n entries; NULL: to p).  out (host) receives n * nrhs doubles and nothing else comes back. */
-static int to_double_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int64_t *dxoff, const uint64_t *dxlimbs,
-                          const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
-                          const int32_t *doidx, int flip, double *out, hipStream_t stream, double *ms_out, int64_t *slow_out)
+/* the operands of the three conversions (to_double_core, mpfr_core, reduce_core), all device arrays of signed digit counts, limb
+ * offsets and limbs: numerators (entry c*n + p) and one denominator per right-hand side; dmaxdig: digits of the widest
+ * denominator; oidx: where entry p of a right-hand side goes (n entries; NULL: to p); flip: the quotients' sign changes */
+struct SlipQuot {
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs; int32_t dmaxdig;
+    const int32_t *oidx; int flip;
+};
+/* a kernel's argument record (SlipToDoubleArgs, SlipMpfrArgs, SlipReduceArgs), zeroed but for the operands they all begin with */
+template <class Args> static Args quot_args(int32_t n, int32_t nrhs, const SlipQuot &q)
 {
-    const int64_t ne = (int64_t) n * nrhs, wcap = (int64_t) dmaxdig + 4;      /* the wave pass forms a product of dmaxdig + 3 digits */
+    Args A; memset(&A, 0, sizeof A);
+    A.n = n; A.nrhs = nrhs; A.xlen = q.xlen; A.xoff = q.xoff; A.xlimbs = q.xlimbs; A.dlen = q.dlen; A.doff = q.doff; A.dlimbs = q.dlimbs;
+    A.oidx = q.oidx; A.flip = q.flip;
+    return A;
+}
+
+/* the operands of a handle-less conversion: the caller's two slabs on the device, with the host's digit counts and offsets */
+struct SlipQuotUpload { SlipQuot q; SlipSlab xs, ds; };
+static void quot_upload_free(SlipQuotUpload *u)
+{
+    dev_free((void *) u->q.xlen); dev_free((void *) u->q.xoff); dev_free((void *) u->q.xlimbs);
+    dev_free((void *) u->q.dlen); dev_free((void *) u->q.doff); dev_free((void *) u->q.dlimbs);
+    slab_free(&u->xs); slab_free(&u->ds);
+    memset(u, 0, sizeof *u);
+}
+static int quot_upload(int32_t n, int32_t nrhs, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                       const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs, SlipQuotUpload *u)
+{
+    memset(u, 0, sizeof *u);
+    const int64_t ne = (int64_t) n * nrhs;
+    SlipSlab &xs = u->xs, &ds = u->ds;
+    int rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
+    A_(slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds));
+    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no number */
+    int32_t *dxl = NULL, *ddl = NULL; int64_t *dxo = NULL, *ddo = NULL; uint64_t *dxv = NULL, *ddv = NULL;
+    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total));
+    A_(dev_alloc(&ddl, nrhs)); A_(dev_alloc(&ddo, nrhs)); A_(dev_alloc(&ddv, ds.total));
+    UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
+    UP_(ddl, ds.dig, (size_t) nrhs * 4); UP_(ddo, ds.off, (size_t) nrhs * 8); UP_(ddv, dlimbs, (size_t) ds.total * 8);
+    u->q.xlen = dxl; u->q.xoff = dxo; u->q.xlimbs = dxv; u->q.dlen = ddl; u->q.doff = ddo; u->q.dlimbs = ddv; u->q.dmaxdig = ds.maxdig;
+    if (rc) quot_upload_free(u);
+    return rc;
+}
+
+/* one conversion on the device.  out (host) receives n * nrhs doubles and nothing else comes back. */
+static int to_double_core(int32_t n, int32_t nrhs, const SlipQuot &q, double *out, hipStream_t stream, double *ms_out, int64_t *slow_out)
+{
+    const int64_t ne = (int64_t) n * nrhs, wcap = (int64_t) q.dmaxdig + 4;      /* the wave pass forms a product of dmaxdig + 3 digits */
     if (wcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
-#ifndef SLIP_EMULATE
-    const int64_t waves_per_block = 4;
-    int64_t blocks = (ne + 64 * waves_per_block - 1) / (64 * waves_per_block);
-    if (blocks > 4096) blocks = 4096;
-    const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * (4 + wcap) * 4);      /* at most 256 MiB of scratch */
-    if (blocks > fit) blocks = fit;
-    if (blocks < 1) blocks = 1;
-#else
-    const int64_t blocks = 2, waves_per_block = 2;
-#endif
+    const int64_t blocks = fit_scratch(service_blocks(ne), 4 + wcap);         /* a wave takes 64 entries per round */
     double *dout = NULL; dig_t *dscr = NULL; unsigned long long *dslow = NULL, hslow = 0;
-    hipEvent_t ev0 = NULL, ev1 = NULL;
+    SlipTimed timed;
     int rc = 0;
-    A_(dev_alloc(&dout, ne)); A_(dev_alloc(&dscr, blocks * waves_per_block * (4 + wcap))); A_(dev_alloc(&dslow, 1));
+    A_(dev_alloc(&dout, ne)); A_(dev_alloc(&dscr, blocks * SERVICE_WAVES * (4 + wcap))); A_(dev_alloc(&dslow, 1));
     HIP_(hipMemsetAsync(dslow, 0, 8, stream));
-    HIP_(hipEventCreate(&ev0)); HIP_(hipEventCreate(&ev1));
     if (!rc) {
-        SlipToDoubleArgs A; memset(&A, 0, sizeof A);
-        A.n = n; A.nrhs = nrhs; A.xlen = dxlen; A.xoff = dxoff; A.xlimbs = dxlimbs; A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
-        A.oidx = doidx; A.flip = flip; A.out = dout; A.scratch = dscr; A.wcap = (int32_t) wcap; A.nslow = dslow;
-        HIP_(hipEventRecord(ev0, stream));
-#ifndef SLIP_EMULATE
-        if (!rc) {
-            hipLaunchKernelGGL(slip_todouble_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
-            HIP_(hipGetLastError());
-        }
-#else
-        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_todouble_body(A); }, 256 * 1024, 1);
-#endif
-        HIP_(hipEventRecord(ev1, stream)); HIP_(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIP_(hipEventElapsedTime(&ms, ev0, ev1));
-        if (ms_out) *ms_out = ms;
+        SlipToDoubleArgs A = quot_args<SlipToDoubleArgs>(n, nrhs, q);
+        A.out = dout; A.scratch = dscr; A.wcap = (int32_t) wcap; A.nslow = dslow;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(todouble, blocks, stream, A));
+        A_(timed.end(stream, ms_out));
     }
     DOWN_(out, dout, (size_t) ne * 8); DOWN_(&hslow, dslow, 8);
     if (!rc && slow_out) *slow_out = (int64_t) hslow;
-    if (ev0) hipEventDestroy(ev0);
-    if (ev1) hipEventDestroy(ev1);
     dev_free(dout); dev_free(dscr); dev_free(dslow);
     return rc;
 }
@@ -3148,13 +3231,7 @@ static int scale_launch(int64_t count, const int32_t *dlen, const int64_t *doff,
 {
     SlipScaleArgs A; memset(&A, 0, sizeof A);
     A.count = count; A.len = dlen; A.off = doff; A.limbs = dlimbs; A.slen = slen; A.slimbs = dsl; A.olen = dolen; A.ooff = dooff; A.olimbs = dolimbs;
-#ifndef SLIP_EMULATE
-    int64_t blocks = (count + 3) / 4; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(slip_scale_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, A);
-    CK(hipGetLastError());
-#else
-    emu::launch(2, 128, [A]() { slip_scale_body(A); }, 256 * 1024, 1);
-#endif
+    TRY_(SERVICE_LAUNCH(scale, wave_blocks(count), stream, A));
     CK(hipStreamSynchronize(stream));
     return 0;
 }
@@ -3173,15 +3250,13 @@ static int scale_is_unit(int32_t dig, const uint64_t *limbs) { return !limbs || 
  * apart (flip), and where position p goes: column q[p] (SLIP_permute_x); the transposed solve's position p is row i with
  * pinv[i] = p */
 struct SlipScaledSol {
-    const int32_t *nlen; const int64_t *noff; const uint64_t *nlimbs;              /* numerators: entry c*n + p                  */
-    int32_t *ddlen; int64_t *ddoff; const uint64_t *dden; int32_t ddig;            /* denominators: entry c; digits of the one   */
-    const int32_t *doidx; int flip;
+    SlipQuot q;
     SlipSolveOut o;                                                                /* owned: the substitution's output ...        */
-    int32_t *own_oidx, *dxlen2; int64_t *dxoff2; uint64_t *dprod, *dxl2;           /* ... and what the scale made                 */
+    int32_t *own_dlen, *own_oidx, *dxlen2; int64_t *own_doff, *dxoff2; uint64_t *dprod, *dxl2;      /* ... and what the scale made */
 };
 static void scaled_free(SlipScaledSol *s)
 {
-    dev_free(s->ddlen); dev_free(s->ddoff); dev_free(s->own_oidx); dev_free(s->dxlen2); dev_free(s->dxoff2); dev_free(s->dprod); dev_free(s->dxl2);
+    dev_free(s->own_dlen); dev_free(s->own_doff); dev_free(s->own_oidx); dev_free(s->dxlen2); dev_free(s->dxoff2); dev_free(s->dprod); dev_free(s->dxl2);
     solve_out_free(&s->o);
     memset(s, 0, sizeof *s);
 }
@@ -3200,7 +3275,7 @@ static int solve_scaled(slip_hip_factor *f, int32_t transpose, int32_t nrhs, con
     const int32_t n = f->n;
     const int64_t ne = (int64_t) n * nrhs;
     SlipParams *P = &f->P;
-    s->flip = (sndig < 0) != (sddig < 0);
+    s->q.flip = (sndig < 0) != (sddig < 0);
     const int32_t snabs = sndig < 0 ? -sndig : sndig, sdabs = sddig < 0 ? -sddig : sddig;
     int32_t *dplen = NULL; uint64_t *dsl = NULL;
     int32_t *hl = (int32_t *) malloc((size_t)(ne > nrhs ? ne : nrhs) * 4); int64_t *ho = (int64_t *) malloc((size_t)(ne > nrhs ? ne : nrhs) * 8);
@@ -3210,26 +3285,26 @@ static int solve_scaled(slip_hip_factor *f, int32_t transpose, int32_t nrhs, con
     DOWN_(&pr, P->piv.p_ + (n - 1), sizeof pr);
     int32_t ddig = pr.len < 0 ? -pr.len : pr.len;
     if (!rc && (pr.len == 0 || pr.off < 0 || pr.off + ((ddig + 1) >> 1) > P->Lcap_nl)) rc = SLIP_HIP_DEVICE_ERROR;
-    s->dden = P->Llimbs; int64_t denoff = pr.off; int32_t denlen = pr.len;
-    A_(dev_alloc(&s->ddlen, nrhs)); A_(dev_alloc(&s->ddoff, nrhs));
+    s->q.dlimbs = P->Llimbs; int64_t denoff = pr.off; int32_t denlen = pr.len;
+    A_(dev_alloc(&s->own_dlen, nrhs)); A_(dev_alloc(&s->own_doff, nrhs));
     /* det * |sden|, once per call, on one wave */
     if (!rc && !scale_is_unit(sddig, sdlimbs)) {
         const int64_t zero = 0;
         A_(dev_alloc(&dsl, (sdabs + 1) >> 1)); A_(dev_alloc(&s->dprod, (ddig + sdabs + 1) / 2 + 1)); A_(dev_alloc(&dplen, 1));
         UP_(dsl, sdlimbs, (size_t)((sdabs + 1) >> 1) * 8);
-        UP_(s->ddlen, &pr.len, 4); UP_(s->ddoff, &pr.off, 8);                       /* the source record; rewritten below */
+        UP_(s->own_dlen, &pr.len, 4); UP_(s->own_doff, &pr.off, 8);                 /* the source record; rewritten below */
         int64_t *dzero = NULL;
         A_(dev_alloc(&dzero, 1)); UP_(dzero, &zero, 8);
-        A_(scale_launch(1, s->ddlen, s->ddoff, P->Llimbs, sdabs, dsl, dplen, dzero, s->dprod, stream));
+        A_(scale_launch(1, s->own_dlen, s->own_doff, P->Llimbs, sdabs, dsl, dplen, dzero, s->dprod, stream));
         DOWN_(&denlen, dplen, 4);
         dev_free(dzero); dev_free(dsl); dsl = NULL;
-        s->dden = s->dprod; denoff = 0; ddig = denlen < 0 ? -denlen : denlen;
+        s->q.dlimbs = s->dprod; denoff = 0; ddig = denlen < 0 ? -denlen : denlen;
     }
-    s->ddig = ddig;
+    s->q.dmaxdig = ddig; s->q.dlen = s->own_dlen; s->q.doff = s->own_doff;
     if (!rc) for (int32_t c = 0; c < nrhs; c++) { hl[c] = denlen; ho[c] = denoff; }
-    UP_(s->ddlen, hl, (size_t) nrhs * 4); UP_(s->ddoff, ho, (size_t) nrhs * 8);
+    UP_(s->own_dlen, hl, (size_t) nrhs * 4); UP_(s->own_doff, ho, (size_t) nrhs * 8);
     /* xnum * |snum| per entry, only when |snum| != 1: the counts come down (4 bytes an entry) to lay the products out */
-    s->nlen = o.olen; s->noff = o.ooff; s->nlimbs = o.olimbs;
+    s->q.xlen = o.olen; s->q.xoff = o.ooff; s->q.xlimbs = o.olimbs;
     if (!rc && !scale_is_unit(sndig, snlimbs)) {
         DOWN_(hl, o.olen, (size_t) ne * 4);
         int64_t total = 0;
@@ -3237,13 +3312,13 @@ static int solve_scaled(slip_hip_factor *f, int32_t transpose, int32_t nrhs, con
         A_(dev_alloc(&dsl, (snabs + 1) >> 1)); A_(dev_alloc(&s->dxlen2, ne)); A_(dev_alloc(&s->dxoff2, ne)); A_(dev_alloc(&s->dxl2, total));
         UP_(dsl, snlimbs, (size_t)((snabs + 1) >> 1) * 8); UP_(s->dxoff2, ho, (size_t) ne * 8);
         A_(scale_launch(ne, o.olen, o.ooff, o.olimbs, snabs, dsl, s->dxlen2, s->dxoff2, s->dxl2, stream));
-        s->nlen = s->dxlen2; s->noff = s->dxoff2; s->nlimbs = s->dxl2;
+        s->q.xlen = s->dxlen2; s->q.xoff = s->dxoff2; s->q.xlimbs = s->dxl2;
     }
-    s->doidx = f->dq;
+    s->q.oidx = f->dq;
     if (!rc && transpose) {
         for (int32_t i = 0; i < n; i++) hl[f->tpinv[i]] = i;
         A_(dev_alloc(&s->own_oidx, n)); UP_(s->own_oidx, hl, (size_t) n * 4);
-        s->doidx = s->own_oidx;
+        s->q.oidx = s->own_oidx;
     }
     free(hl); free(ho);
     dev_free(dplen); dev_free(dsl);
@@ -3260,8 +3335,7 @@ extern "C" int slip_hip_factor_solve_double(slip_hip_factor *f, int32_t transpos
     SlipScaledSol s;
     TRY_(solve_scaled(f, transpose, nrhs, blen, blimbs, snlen, snlimbs, sdlen, sdlimbs, stream, &s));
     f->todouble_ms = 0; f->todouble_slow = 0;
-    const int rc = to_double_core(f->n, nrhs, s.nlen, s.noff, s.nlimbs, s.ddlen, s.ddoff, s.dden, s.ddig, s.doidx, s.flip, x_out, stream,
-                                  &f->todouble_ms, &f->todouble_slow);
+    const int rc = to_double_core(f->n, nrhs, s.q, x_out, stream, &f->todouble_ms, &f->todouble_slow);
     scaled_free(&s);
     return rc;
 }
@@ -3274,20 +3348,10 @@ extern "C" int slip_hip_solution_to_double(int32_t n, int32_t nrhs, const int32_
 {
     if (n <= 0 || nrhs < 1 || !xlen || !xlimbs || !dlen || !dlimbs || !out) return SLIP_HIP_INCORRECT_INPUT;
     TRY_(need_device());
-    const int64_t ne = (int64_t) n * nrhs;
-    SlipSlab xs, ds;
-    memset(&ds, 0, sizeof ds);
-    int rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
-    if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
-    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no number */
-    int32_t *dxl = NULL, *ddl = NULL; int64_t *dxo = NULL, *ddo = NULL; uint64_t *dxv = NULL, *ddv = NULL;
-    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total));
-    A_(dev_alloc(&ddl, nrhs)); A_(dev_alloc(&ddo, nrhs)); A_(dev_alloc(&ddv, ds.total));
-    UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
-    UP_(ddl, ds.dig, (size_t) nrhs * 4); UP_(ddo, ds.off, (size_t) nrhs * 8); UP_(ddv, dlimbs, (size_t) ds.total * 8);
-    A_(to_double_core(n, nrhs, dxl, dxo, dxv, ddl, ddo, ddv, ds.maxdig, NULL, 0, out, (hipStream_t) stream_v, NULL, NULL));
-    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
-    slab_free(&xs); slab_free(&ds);
+    SlipQuotUpload u;
+    int rc = quot_upload(n, nrhs, xlen, xlimbs, x_limbs, dlen, dlimbs, d_limbs, &u);
+    A_(to_double_core(n, nrhs, u.q, out, (hipStream_t) stream_v, NULL, NULL));
+    quot_upload_free(&u);
     return rc;
 }
 
@@ -3305,64 +3369,36 @@ static int mpfr_args_ok(int32_t prec, int32_t rnd, const int8_t *sign_out, const
 
 /* one conversion on the device: the operands as to_double_core takes them.  The host arrays receive n * nrhs signs, exponents
  * and ternary values (ternary_out may be NULL) and n * nrhs * ceil(prec / 64) limbs; nothing else comes back. */
-static int mpfr_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int64_t *dxoff, const uint64_t *dxlimbs,
-                     const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
-                     const int32_t *doidx, int flip, int32_t prec, int32_t rnd,
+static int mpfr_core(int32_t n, int32_t nrhs, const SlipQuot &q, int32_t prec, int32_t rnd,
                      int8_t *sign_out, int64_t *exp_out, uint64_t *mant_out, int8_t *ternary_out,
                      hipStream_t stream, double *ms_out, int64_t *paths_out)
 {
     const int64_t ne = (int64_t) n * nrhs, nl = (prec + 63) >> 6, nq = (prec + 2 + 31) >> 5;
-    const int64_t dcap = dmaxdig > 1 ? dmaxdig : 1;
+    const int64_t dcap = q.dmaxdig > 1 ? q.dmaxdig : 1;
     if (dcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
     /* the running remainder with the quotient digits' room above it, one product, the normalised divisor, the quotient */
     const int64_t stride = ((nq + dcap + 2) + (dcap + 2) + dcap + (nq + 1) + 1) & ~(int64_t) 1;
-#ifndef SLIP_EMULATE
-    /* a wave takes `chunk` entries per round: few entries are spread one to a wave, many fill the lanes of 4096 waves */
-    const int64_t waves_per_block = 4;
-    int64_t chunk = (ne + 4095) / 4096;
-    if (chunk > 64) chunk = 64;
-    int64_t blocks = (ne + chunk * waves_per_block - 1) / (chunk * waves_per_block);
-    if (blocks > 1024) blocks = 1024;
-    const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * stride * 4);      /* at most 256 MiB of scratch */
-    if (blocks > fit) blocks = fit;
-    if (blocks < 1) blocks = 1;
-#else
-    const int64_t blocks = 2, waves_per_block = 2, chunk = 5;
-#endif
+    const SlipWaveGrid g = wave_grid(ne, stride, 1024);
     int8_t *dsign = NULL, *dtern = NULL; int64_t *dexp = NULL; uint64_t *dmant = NULL;
     dig_t *dscr = NULL; unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
-    hipEvent_t ev0 = NULL, ev1 = NULL;
+    SlipTimed timed;
     int rc = 0;
     A_(dev_alloc(&dsign, ne)); A_(dev_alloc(&dtern, ne)); A_(dev_alloc(&dexp, ne)); A_(dev_alloc(&dmant, ne * nl));
-    A_(dev_alloc(&dscr, blocks * waves_per_block * stride)); A_(dev_alloc(&dpaths, 4));
+    A_(dev_alloc(&dscr, g.blocks * SERVICE_WAVES * stride)); A_(dev_alloc(&dpaths, 4));
     HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
-    HIP_(hipEventCreate(&ev0)); HIP_(hipEventCreate(&ev1));
     if (!rc) {
-        SlipMpfrArgs A; memset(&A, 0, sizeof A);
-        A.n = n; A.nrhs = nrhs; A.xlen = dxlen; A.xoff = dxoff; A.xlimbs = dxlimbs; A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
-        A.oidx = doidx; A.flip = flip; A.prec = prec; A.rnd = rnd; A.chunk = (int32_t) chunk;
+        SlipMpfrArgs A = quot_args<SlipMpfrArgs>(n, nrhs, q);
+        A.prec = prec; A.rnd = rnd; A.chunk = (int32_t) g.chunk;
         A.sign = dsign; A.exp = dexp; A.mant = dmant; A.ternary = dtern;
         A.scratch = dscr; A.dcap = (int32_t) dcap; A.stride = stride; A.paths = dpaths;
-        HIP_(hipEventRecord(ev0, stream));
-#ifndef SLIP_EMULATE
-        if (!rc) {
-            hipLaunchKernelGGL(slip_mpfr_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
-            HIP_(hipGetLastError());
-        }
-#else
-        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_mpfr_body(A); }, 256 * 1024, 1);
-#endif
-        HIP_(hipEventRecord(ev1, stream)); HIP_(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIP_(hipEventElapsedTime(&ms, ev0, ev1));
-        if (ms_out) *ms_out = ms;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(mpfr, g.blocks, stream, A));
+        A_(timed.end(stream, ms_out));
     }
     DOWN_(sign_out, dsign, (size_t) ne); DOWN_(exp_out, dexp, (size_t) ne * 8); DOWN_(mant_out, dmant, (size_t)(ne * nl) * 8);
     if (ternary_out) DOWN_(ternary_out, dtern, (size_t) ne);
     DOWN_(hpaths, dpaths, 32);
     if (!rc && paths_out) for (int t = 0; t < 4; t++) paths_out[t] = (int64_t) hpaths[t];
-    if (ev0) hipEventDestroy(ev0);
-    if (ev1) hipEventDestroy(ev1);
     dev_free(dsign); dev_free(dtern); dev_free(dexp); dev_free(dmant); dev_free(dscr); dev_free(dpaths);
     return rc;
 }
@@ -3377,8 +3413,7 @@ extern "C" int slip_hip_factor_solve_mpfr(slip_hip_factor *f, int32_t transpose,
     SlipScaledSol s;
     TRY_(solve_scaled(f, transpose, nrhs, blen, blimbs, snlen, snlimbs, sdlen, sdlimbs, stream, &s));
     f->tompfr_ms = 0; memset(f->tompfr_paths, 0, sizeof f->tompfr_paths);
-    const int rc = mpfr_core(f->n, nrhs, s.nlen, s.noff, s.nlimbs, s.ddlen, s.ddoff, s.dden, s.ddig, s.doidx, s.flip, prec, rnd,
-                             sign_out, exp_out, mant_out, ternary_out, stream, &f->tompfr_ms, f->tompfr_paths);
+    const int rc = mpfr_core(f->n, nrhs, s.q, prec, rnd, sign_out, exp_out, mant_out, ternary_out, stream, &f->tompfr_ms, f->tompfr_paths);
     scaled_free(&s);
     return rc;
 }
@@ -3398,22 +3433,11 @@ extern "C" int slip_hip_solution_to_mpfr(int32_t n, int32_t nrhs, const int32_t 
     if (n <= 0 || nrhs < 1 || !xlen || !xlimbs || !dlen || !dlimbs) return SLIP_HIP_INCORRECT_INPUT;
     if (!mpfr_args_ok(prec, rnd, sign_out, exp_out, mant_out)) return SLIP_HIP_INCORRECT_INPUT;
     TRY_(need_device());
-    const int64_t ne = (int64_t) n * nrhs;
-    SlipSlab xs, ds;
-    memset(&ds, 0, sizeof ds);
-    int rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
-    if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
-    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no number */
-    int32_t *dxl = NULL, *ddl = NULL; int64_t *dxo = NULL, *ddo = NULL; uint64_t *dxv = NULL, *ddv = NULL;
-    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total));
-    A_(dev_alloc(&ddl, nrhs)); A_(dev_alloc(&ddo, nrhs)); A_(dev_alloc(&ddv, ds.total));
-    UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
-    UP_(ddl, ds.dig, (size_t) nrhs * 4); UP_(ddo, ds.off, (size_t) nrhs * 8); UP_(ddv, dlimbs, (size_t) ds.total * 8);
+    SlipQuotUpload u;
+    int rc = quot_upload(n, nrhs, xlen, xlimbs, x_limbs, dlen, dlimbs, d_limbs, &u);
     memset(slip_mpfr_paths_last, 0, sizeof slip_mpfr_paths_last);
-    A_(mpfr_core(n, nrhs, dxl, dxo, dxv, ddl, ddo, ddv, ds.maxdig, NULL, 0, prec, rnd, sign_out, exp_out, mant_out, ternary_out,
-                 (hipStream_t) stream_v, NULL, slip_mpfr_paths_last));
-    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
-    slab_free(&xs); slab_free(&ds);
+    A_(mpfr_core(n, nrhs, u.q, prec, rnd, sign_out, exp_out, mant_out, ternary_out, (hipStream_t) stream_v, NULL, slip_mpfr_paths_last));
+    quot_upload_free(&u);
     return rc;
 }
 
@@ -3451,13 +3475,7 @@ static int pack_download(int64_t ne, const int32_t *dlen, const int64_t *dsoff, 
     if (!rc) {
         SlipPackArgs A; memset(&A, 0, sizeof A);
         A.count = ne; A.len = dlen; A.soff = dsoff; A.doff = dcoff; A.src = dsrc; A.dst = dpacked;
-#ifndef SLIP_EMULATE
-        int64_t blocks = (ne + 3) / 4; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(slip_pack_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, A);
-        HIP_(hipGetLastError());
-#else
-        emu::launch(2, 128, [A]() { slip_pack_body(A); }, 256 * 1024, 1);
-#endif
+        A_(SERVICE_LAUNCH(pack, wave_blocks(ne), stream, A));
         HIP_(hipStreamSynchronize(stream));
     }
     out = (uint64_t *) malloc((size_t)(total > 0 ? total : 1) * 8);
@@ -3473,13 +3491,10 @@ static int pack_download(int64_t ne, const int32_t *dlen, const int64_t *dsoff, 
     return rc;
 }
 
-/* one reduction on the device: numerators (entry c*n + p) and one denominator per right-hand side as to_double_core takes them;
- * hxdig, hddig: the same digit counts on the host (they size every slot: a fraction in lowest terms is no longer than what it
- * came from); hoidx / doidx: where entry p goes, host and device copies (both NULL: to p).  The six outputs are compact
- * malloc'ed slabs in slot order. */
-static int reduce_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int64_t *dxoff, const uint64_t *dxlimbs, const int32_t *hxdig,
-                       const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, const int32_t *hddig,
-                       const int32_t *hoidx, const int32_t *doidx, int flip,
+/* one reduction on the device: the operands as to_double_core takes them; hxdig, hddig: their digit counts on the host (they size
+ * every slot: a fraction in lowest terms is no longer than what it came from); hoidx: the host's copy of q.oidx (both NULL: to p).
+ * The six outputs are compact malloc'ed slabs in slot order. */
+static int reduce_core(int32_t n, int32_t nrhs, const SlipQuot &q, const int32_t *hxdig, const int32_t *hddig, const int32_t *hoidx,
                        int32_t **numlen_out, uint64_t **numlimbs_out, int64_t *num_limbs_out,
                        int32_t **denlen_out, uint64_t **denlimbs_out, int64_t *den_limbs_out,
                        hipStream_t stream, double *ms_out, int64_t *paths_out)
@@ -3503,47 +3518,23 @@ static int reduce_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int6
     /* the memory class works on five buffers of the widest operand plus two digits; the register class shifts through 258 */
     const int64_t wcap = (((int64_t) maxdig + 2 > 264 ? (int64_t) maxdig + 2 : 264) + 1) & ~(int64_t) 1, per_wave = 8 + 5 * wcap;
     if (wcap > (1 << 28)) { free(hno); free(hdo); return SLIP_HIP_OUT_OF_MEMORY; }
-#ifndef SLIP_EMULATE
-    /* a wave takes `chunk` entries per round: few entries are spread one to a wave, many fill the lanes of 4096 waves */
-    const int64_t waves_per_block = 4;
-    int64_t chunk = (ne + 4095) / 4096;
-    if (chunk > 64) chunk = 64;
-    int64_t blocks = (ne + chunk * waves_per_block - 1) / (chunk * waves_per_block);
-    if (blocks > 1024) blocks = 1024;
-    const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * per_wave * 4);      /* at most 256 MiB of scratch */
-    if (blocks > fit) blocks = fit;
-    if (blocks < 1) blocks = 1;
-#else
-    const int64_t blocks = 2, waves_per_block = 2, chunk = 5;
-#endif
+    const SlipWaveGrid g = wave_grid(ne, per_wave, 1024);
     int32_t *dnl = NULL, *ddl = NULL; int64_t *dno = NULL, *ddo = NULL; uint64_t *dnv = NULL, *ddv = NULL;
     dig_t *dscr = NULL; unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
-    hipEvent_t ev0 = NULL, ev1 = NULL;
+    SlipTimed timed;
     int rc = 0;
     A_(dev_alloc(&dnl, ne)); A_(dev_alloc(&ddl, ne)); A_(dev_alloc(&dno, ne)); A_(dev_alloc(&ddo, ne));
     A_(dev_alloc(&dnv, ntotal)); A_(dev_alloc(&ddv, dtotal));
-    A_(dev_alloc(&dscr, blocks * waves_per_block * per_wave)); A_(dev_alloc(&dpaths, 4));
+    A_(dev_alloc(&dscr, g.blocks * SERVICE_WAVES * per_wave)); A_(dev_alloc(&dpaths, 4));
     UP_(dno, hno, (size_t) ne * 8); UP_(ddo, hdo, (size_t) ne * 8);
     HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
-    HIP_(hipEventCreate(&ev0)); HIP_(hipEventCreate(&ev1));
     if (!rc) {
-        SlipReduceArgs A; memset(&A, 0, sizeof A);
-        A.n = n; A.nrhs = nrhs; A.xlen = dxlen; A.xoff = dxoff; A.xlimbs = dxlimbs; A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
-        A.oidx = doidx; A.flip = flip; A.chunk = (int32_t) chunk; A.numlen = dnl; A.denlen = ddl; A.numoff = dno; A.denoff = ddo;
+        SlipReduceArgs A = quot_args<SlipReduceArgs>(n, nrhs, q);
+        A.chunk = (int32_t) g.chunk; A.numlen = dnl; A.denlen = ddl; A.numoff = dno; A.denoff = ddo;
         A.numlimbs = dnv; A.denlimbs = ddv; A.scratch = dscr; A.wcap = (int32_t) wcap; A.paths = dpaths;
-        HIP_(hipEventRecord(ev0, stream));
-#ifndef SLIP_EMULATE
-        if (!rc) {
-            hipLaunchKernelGGL(slip_reduce_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
-            HIP_(hipGetLastError());
-        }
-#else
-        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_reduce_body(A); }, 256 * 1024, 1);
-#endif
-        HIP_(hipEventRecord(ev1, stream)); HIP_(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIP_(hipEventElapsedTime(&ms, ev0, ev1));
-        if (ms_out) *ms_out = ms;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(reduce, g.blocks, stream, A));
+        A_(timed.end(stream, ms_out));
     }
     DOWN_(hpaths, dpaths, 32);
     if (!rc && paths_out) for (int t = 0; t < 4; t++) paths_out[t] = (int64_t) hpaths[t];
@@ -3555,8 +3546,6 @@ static int reduce_core(int32_t n, int32_t nrhs, const int32_t *dxlen, const int6
         nl = dl = NULL; nv = dv = NULL;
     }
     free(nl); free(dl); free(nv); free(dv); free(hno); free(hdo);
-    if (ev0) hipEventDestroy(ev0);
-    if (ev1) hipEventDestroy(ev1);
     dev_free(dnl); dev_free(ddl); dev_free(dno); dev_free(ddo); dev_free(dnv); dev_free(ddv); dev_free(dscr); dev_free(dpaths);
     return rc;
 }
@@ -3576,11 +3565,10 @@ extern "C" int slip_hip_factor_solve_rational(slip_hip_factor *f, int32_t transp
     /* the numerators' digit counts (4 bytes an entry) and q size the slots; no limb comes down before the result is packed */
     int32_t *hx = (int32_t *) malloc((size_t) ne * 4), *hd = (int32_t *) malloc((size_t) nrhs * 4), *hoidx = (int32_t *) malloc((size_t) n * 4);
     int rc = !hx || !hd || !hoidx ? SLIP_HIP_OUT_OF_MEMORY : 0;
-    DOWN_(hx, s.nlen, (size_t) ne * 4); DOWN_(hoidx, s.doidx, (size_t) n * 4);
-    if (!rc) for (int32_t c = 0; c < nrhs; c++) hd[c] = s.ddig;
+    DOWN_(hx, s.q.xlen, (size_t) ne * 4); DOWN_(hoidx, s.q.oidx, (size_t) n * 4);
+    if (!rc) for (int32_t c = 0; c < nrhs; c++) hd[c] = s.q.dmaxdig;
     f->torational_ms = 0; memset(f->torational_paths, 0, sizeof f->torational_paths);
-    A_(reduce_core(n, nrhs, s.nlen, s.noff, s.nlimbs, hx, s.ddlen, s.ddoff, s.dden, hd, hoidx, s.doidx, s.flip,
-                   numlen_out, numlimbs_out, num_limbs_out, denlen_out, denlimbs_out, den_limbs_out, stream,
+    A_(reduce_core(n, nrhs, s.q, hx, hd, hoidx, numlen_out, numlimbs_out, num_limbs_out, denlen_out, denlimbs_out, den_limbs_out, stream,
                    &f->torational_ms, f->torational_paths));
     free(hx); free(hd); free(hoidx);
     scaled_free(&s);
@@ -3604,23 +3592,12 @@ extern "C" int slip_hip_solution_to_rational(int32_t n, int32_t nrhs, const int3
     if (!numlen_out || !numlimbs_out || !num_limbs_out || !denlen_out || !denlimbs_out || !den_limbs_out) return SLIP_HIP_INCORRECT_INPUT;
     *numlen_out = *denlen_out = NULL; *numlimbs_out = *denlimbs_out = NULL; *num_limbs_out = *den_limbs_out = 0;
     TRY_(need_device());
-    const int64_t ne = (int64_t) n * nrhs;
-    SlipSlab xs, ds;
-    memset(&ds, 0, sizeof ds);
-    int rc = slab_prepare(ne, xlen, xlimbs, x_limbs, &xs);
-    if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
-    for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no number */
-    int32_t *dxl = NULL, *ddl = NULL; int64_t *dxo = NULL, *ddo = NULL; uint64_t *dxv = NULL, *ddv = NULL;
-    A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total));
-    A_(dev_alloc(&ddl, nrhs)); A_(dev_alloc(&ddo, nrhs)); A_(dev_alloc(&ddv, ds.total));
-    UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
-    UP_(ddl, ds.dig, (size_t) nrhs * 4); UP_(ddo, ds.off, (size_t) nrhs * 8); UP_(ddv, dlimbs, (size_t) ds.total * 8);
+    SlipQuotUpload u;
+    int rc = quot_upload(n, nrhs, xlen, xlimbs, x_limbs, dlen, dlimbs, d_limbs, &u);
     memset(slip_rational_paths_last, 0, sizeof slip_rational_paths_last);
-    A_(reduce_core(n, nrhs, dxl, dxo, dxv, xs.dig, ddl, ddo, ddv, ds.dig, NULL, NULL, 0,
-                   numlen_out, numlimbs_out, num_limbs_out, denlen_out, denlimbs_out, den_limbs_out, (hipStream_t) stream_v,
-                   NULL, slip_rational_paths_last));
-    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(ddl); dev_free(ddo); dev_free(ddv);
-    slab_free(&xs); slab_free(&ds);
+    A_(reduce_core(n, nrhs, u.q, u.xs.dig, u.ds.dig, NULL, numlen_out, numlimbs_out, num_limbs_out, denlen_out, denlimbs_out, den_limbs_out,
+                   (hipStream_t) stream_v, NULL, slip_rational_paths_last));
+    quot_upload_free(&u);
     return rc;
 }
 
@@ -3664,28 +3641,18 @@ static int check_core(int32_t n, int32_t nrhs, const int64_t *drp, const int64_t
     /* every (row, rhs) width is at most this (slip_check_kernel): the memory path's scratch is sized from it */
     const int64_t wcap = (amaxdig + xs.maxdig > dmaxdig + bs.maxdig ? amaxdig + xs.maxdig : dmaxdig + bs.maxdig) + 1;
     if (wcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
-#ifndef SLIP_EMULATE
-    int64_t blocks = (ne + 3) / 4; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    const int64_t waves_per_block = 4;
-    if (wcap > 256) {                                          /* memory path: at most 256 MiB of scratch */
-        const int64_t fit = ((int64_t) 256 << 20) / (waves_per_block * 2 * wcap * 4);
-        if (blocks > fit) blocks = fit > 0 ? fit : 1;
-    }
-#else
-    const int64_t blocks = 2, waves_per_block = 2;
-#endif
+    const int64_t blocks = wcap > 256 ? fit_scratch(wave_blocks(ne), 2 * wcap) : wave_blocks(ne);      /* (only the memory path has scratch) */
     int32_t *dxl = NULL, *dbl = NULL, *dfirst = NULL, *dbad = NULL; int64_t *dxo = NULL, *dbo = NULL; uint64_t *dxv = NULL, *dbv = NULL; dig_t *dscr = NULL;
     int32_t *hfirst = (int32_t *) malloc((size_t) nrhs * 4), *hbad = (int32_t *) malloc((size_t) nrhs * 4);
-    hipEvent_t ev0 = NULL, ev1 = NULL;
+    SlipTimed timed;
     int rc = (!hfirst || !hbad) ? SLIP_HIP_OUT_OF_MEMORY : 0;
     A_(dev_alloc(&dxl, ne)); A_(dev_alloc(&dxo, ne)); A_(dev_alloc(&dxv, xs.total)); A_(dev_alloc(&dbl, ne)); A_(dev_alloc(&dbo, ne)); A_(dev_alloc(&dbv, bs.total));
     A_(dev_alloc(&dfirst, nrhs)); A_(dev_alloc(&dbad, nrhs));
-    if (wcap > 256) A_(dev_alloc(&dscr, blocks * waves_per_block * 2 * wcap));
+    if (wcap > 256) A_(dev_alloc(&dscr, blocks * SERVICE_WAVES * 2 * wcap));
     if (!rc) for (int32_t c = 0; c < nrhs; c++) { hfirst[c] = n; hbad[c] = 0; }
     UP_(dxl, xs.dig, (size_t) ne * 4); UP_(dxo, xs.off, (size_t) ne * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
     UP_(dbl, bs.dig, (size_t) ne * 4); UP_(dbo, bs.off, (size_t) ne * 8); UP_(dbv, blimbs, (size_t) bs.total * 8);
     UP_(dfirst, hfirst, (size_t) nrhs * 4); UP_(dbad, hbad, (size_t) nrhs * 4);
-    HIP_(hipEventCreate(&ev0)); HIP_(hipEventCreate(&ev1));
     if (!rc) {
         SlipCheckArgs A; memset(&A, 0, sizeof A);
         A.n = n; A.nrhs = nrhs; A.rp = drp; A.re = dre; A.rx = drx;
@@ -3693,19 +3660,9 @@ static int check_core(int32_t n, int32_t nrhs, const int64_t *drp, const int64_t
         A.xlen = dxl; A.xoff = dxo; A.xlimbs = dxv; A.blen = dbl; A.boff = dbo; A.blimbs = dbv;
         A.dlen = ddlen; A.doff = ddoff; A.dlimbs = ddlimbs;
         A.first_bad = dfirst; A.nbad = dbad; A.scratch = dscr; A.wcap = (int32_t) wcap;
-        HIP_(hipEventRecord(ev0, stream));
-#ifndef SLIP_EMULATE
-        if (!rc) {
-            hipLaunchKernelGGL(slip_check_kernel, dim3((unsigned) blocks), dim3(64 * waves_per_block), 0, stream, A);
-            HIP_(hipGetLastError());
-        }
-#else
-        if (!rc) emu::launch((int) blocks, (int)(64 * waves_per_block), [A]() { slip_check_body(A); }, 256 * 1024, 1);
-#endif
-        HIP_(hipEventRecord(ev1, stream)); HIP_(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIP_(hipEventElapsedTime(&ms, ev0, ev1));
-        if (ms_out) *ms_out = ms;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(check, blocks, stream, A));
+        A_(timed.end(stream, ms_out));
     }
     DOWN_(hfirst, dfirst, (size_t) nrhs * 4); DOWN_(hbad, dbad, (size_t) nrhs * 4);
     if (!rc) {
@@ -3717,8 +3674,6 @@ static int check_core(int32_t n, int32_t nrhs, const int64_t *drp, const int64_t
         }
         rc = exact ? SLIP_HIP_OK : SLIP_HIP_INCORRECT;
     }
-    if (ev0) hipEventDestroy(ev0);
-    if (ev1) hipEventDestroy(ev1);
     dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dbl); dev_free(dbo); dev_free(dbv); dev_free(dfirst); dev_free(dbad); dev_free(dscr);
     free(hfirst); free(hbad);
     return rc;
@@ -3909,13 +3864,8 @@ static int rescale_one(slip_hip_factor *f, int isL, int64_t nz, const int32_t *s
         A.ent = isL ? P->Le : P->Ue; A.limbs = isL ? P->Llimbs : P->Ulimbs; A.idx = isL ? P->Li : P->Ui; A.nz = nz;
         A.colp = isL ? P->Lp : NULL; A.ncols = K; A.pinv = P->pinv.p_;
         A.slen = dslen; A.soff = dsoff; A.slimbs = dslimbs; A.oent = de; A.olimbs = dl; A.pividx = f->rspiv; A.row_perm = P->row_perm.p_;
-#ifndef SLIP_EMULATE
-        int64_t blocks = (nz + 3) / 4; if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(slip_rescale_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, A);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) rc = SLIP_HIP_DEVICE_ERROR;
-#else
-        emu::launch(2, 128, [A]() { slip_rescale_body(A); }, 256 * 1024, 1);
-#endif
+        A_(SERVICE_LAUNCH(rescale, wave_blocks(nz), stream, A));
+        HIP_(hipStreamSynchronize(stream));
     }
     if (!rc) {
         if (isL) { f->rsLe = de; f->rsLl = dl; f->rsLnl = o; }

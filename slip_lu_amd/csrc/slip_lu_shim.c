@@ -299,11 +299,18 @@ static int mpz_to_limbs(const mpz_t z, int32_t *len, uint64_t **limbs)
     return 0;
 }
 
-/* what SLIP_hip_solve_double and SLIP_hip_solve_mpq share: A factorised on the device (handle *f), b as a limb slab and the
- * scale A->scale / b->scale as two limb runs, a part that is 1 or 0 left out (SLIP_scale_x.c:29-31, :43-45).  The caller
- * destroys *f and frees the four arrays whatever comes back. */
-static SLIP_info factor_for_solve(SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option, slip_hip_factor **f,
-                                  int32_t **blen, uint64_t **blimbs, int32_t *snlen, uint64_t **snl, int32_t *sdlen, uint64_t **sdl)
+/* what the SLIP_hip_solve_* refuse first: a missing argument, then an empty system (x: the result matrix) */
+static int solve_args_ok(const void *x, const SLIP_sparse *A, const SLIP_LU_analysis *S, const SLIP_dense *b, const SLIP_options *option)
+{
+    return x && A && A->p && A->i && A->x && S && S->q && b && b->x && option && A->n > 0 && b->n > 0 && A->p[A->n] >= 1;
+}
+
+/* what the SLIP_hip_solve_* share: A factorised on the device (handle f), b as a limb slab and the scale A->scale / b->scale
+ * as two limb runs, a part that is 1 or 0 left out (SLIP_scale_x.c:29-31, :43-45).  The caller releases it with
+ * solve_input_free whatever factor_for_solve returns. */
+typedef struct { slip_hip_factor *f; int32_t *blen, snlen, sdlen; uint64_t *blimbs, *snl, *sdl; } solve_input;
+static void solve_input_free(solve_input *in) { if (in->f) slip_hip_factor_destroy(in->f); free(in->blen); free(in->blimbs); free(in->snl); free(in->sdl); }
+static SLIP_info factor_for_solve(SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option, solve_input *in)
 {
     const int32_t n = A->n, nrhs = b->n;
     SLIP_info ret = SLIP_OUT_OF_MEMORY;
@@ -315,14 +322,14 @@ static SLIP_info factor_for_solve(SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dens
     mpz_init_set_ui(sn, 1); mpz_init_set_ui(sd, 1);
     if (mpq_sgn(A->scale) != 0 && mpq_cmp_ui(A->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_numref(A->scale)); mpz_mul(sd, sd, mpq_denref(A->scale)); }
     if (mpq_sgn(b->scale) != 0 && mpq_cmp_ui(b->scale, 1, 1) != 0) { mpz_mul(sn, sn, mpq_denref(b->scale)); mpz_mul(sd, sd, mpq_numref(b->scale)); }
-    if (mpz_to_limbs(sn, snlen, snl) || mpz_to_limbs(sd, sdlen, sdl)) goto done;
-    if (matrix_to_slab(A, n, &Ap, &Alen, &Alimbs) || dense_to_slab(b, n, nrhs, blen, blimbs)) goto done;
+    if (mpz_to_limbs(sn, &in->snlen, &in->snl) || mpz_to_limbs(sd, &in->sdlen, &in->sdl)) goto done;
+    if (matrix_to_slab(A, n, &Ap, &Alen, &Alimbs) || dense_to_slab(b, n, nrhs, &in->blen, &in->blimbs)) goto done;
     slip_hip_default_options(&opt);
     opt.pivot = (int32_t) option->pivot;
     opt.tol = option->tol;
     opt.lnz_hint = S->lnz; opt.unz_hint = S->unz;
-    rc = slip_hip_factor_create(f, n, Ap, A->i, Alen, Alimbs, S->q, &opt);
-    if (rc == SLIP_HIP_OK) rc = slip_hip_factor_run(*f, 0, NULL);
+    rc = slip_hip_factor_create(&in->f, n, Ap, A->i, Alen, Alimbs, S->q, &opt);
+    if (rc == SLIP_HIP_OK) rc = slip_hip_factor_run(in->f, 0, NULL);
     ret = solve_status(rc);
 done:
     mpz_clear(sn); mpz_clear(sd);
@@ -332,21 +339,17 @@ done:
 
 SLIP_info SLIP_hip_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
 {
-    if (!x_doub || !A || !A->p || !A->i || !A->x || !S || !S->q || !b || !b->x || !option)
-        return SLIP_INCORRECT_INPUT;                      /* SLIP_solve_double.c:53-57 */
+    if (!solve_args_ok(x_doub, A, S, b, option)) return SLIP_INCORRECT_INPUT;      /* SLIP_solve_double.c:53-57 */
     const int32_t n = A->n, nrhs = b->n;
-    if (n <= 0 || nrhs <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
-    slip_hip_factor *f = NULL;
-    int32_t *blen = NULL, snlen = 0, sdlen = 0;
-    uint64_t *blimbs = NULL, *snl = NULL, *sdl = NULL;
+    solve_input in = {0};
     double *xd = (double *) malloc((size_t) n * nrhs * sizeof(double));
-    SLIP_info ret = xd ? factor_for_solve(A, S, b, option, &f, &blen, &blimbs, &snlen, &snl, &sdlen, &sdl) : SLIP_OUT_OF_MEMORY;
-    if (ret == SLIP_OK) ret = solve_status(slip_hip_factor_solve_double(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl, xd, NULL));
+    SLIP_info ret = xd ? factor_for_solve(A, S, b, option, &in) : SLIP_OUT_OF_MEMORY;
+    if (ret == SLIP_OK)
+        ret = solve_status(slip_hip_factor_solve_double(in.f, 0, nrhs, in.blen, in.blimbs, in.snlen, in.snl, in.sdlen, in.sdl, xd, NULL));
     if (ret == SLIP_OK)
         for (int32_t i = 0; i < n; i++)
             for (int32_t j = 0; j < nrhs; j++) x_doub[i][j] = xd[(int64_t) j * n + i];
-    if (f) slip_hip_factor_destroy(f);
-    free(xd); free(blen); free(blimbs); free(snl); free(sdl);
+    solve_input_free(&in); free(xd);
     return ret;
 }
 
@@ -361,17 +364,14 @@ SLIP_info SLIP_hip_solve_double(double **x_doub, SLIP_sparse *A, SLIP_LU_analysi
  * ------------------------------------------------------------------------------------------------ */
 SLIP_info SLIP_hip_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
 {
-    if (!x_mpq || !A || !A->p || !A->i || !A->x || !S || !S->q || !b || !b->x || !option)
-        return SLIP_INCORRECT_INPUT;                      /* SLIP_solve_mpq.c:51-55 */
+    if (!solve_args_ok(x_mpq, A, S, b, option)) return SLIP_INCORRECT_INPUT;       /* SLIP_solve_mpq.c:51-55 */
     const int32_t n = A->n, nrhs = b->n;
-    if (n <= 0 || nrhs <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
-    slip_hip_factor *f = NULL;
-    int32_t *blen = NULL, snlen = 0, sdlen = 0, *numlen = NULL, *denlen = NULL;
-    uint64_t *blimbs = NULL, *snl = NULL, *sdl = NULL, *numl = NULL, *denl = NULL;
+    solve_input in = {0};
+    int32_t *numlen = NULL, *denlen = NULL; uint64_t *numl = NULL, *denl = NULL;
     int64_t nnl = 0, dnl = 0;
-    SLIP_info ret = factor_for_solve(A, S, b, option, &f, &blen, &blimbs, &snlen, &snl, &sdlen, &sdl);
+    SLIP_info ret = factor_for_solve(A, S, b, option, &in);
     if (ret == SLIP_OK)
-        ret = solve_status(slip_hip_factor_solve_rational(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl,
+        ret = solve_status(slip_hip_factor_solve_rational(in.f, 0, nrhs, in.blen, in.blimbs, in.snlen, in.snl, in.sdlen, in.sdl,
                                                           &numlen, &numl, &nnl, &denlen, &denl, &dnl, NULL));
     if (ret == SLIP_OK) {
         int64_t on = 0, od = 0;
@@ -383,9 +383,8 @@ SLIP_info SLIP_hip_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S,
                 on += ln < 0 ? -ln : ln; od += ld;
             }
     }
-    if (f) slip_hip_factor_destroy(f);
+    solve_input_free(&in);
     slip_hip_free(numlen); slip_hip_free(numl); slip_hip_free(denlen); slip_hip_free(denl);
-    free(blen); free(blimbs); free(snl); free(sdl);
     return ret;
 }
 
@@ -403,10 +402,8 @@ SLIP_info SLIP_hip_solve_mpq(mpq_t **x_mpq, SLIP_sparse *A, SLIP_LU_analysis *S,
  * ------------------------------------------------------------------------------------------------ */
 SLIP_info SLIP_hip_solve_mpfr(mpfr_t **x_mpfr, SLIP_sparse *A, SLIP_LU_analysis *S, SLIP_dense *b, SLIP_options *option)
 {
-    if (!x_mpfr || !A || !A->p || !A->i || !A->x || !S || !S->q || !b || !b->x || !option)
-        return SLIP_INCORRECT_INPUT;                      /* SLIP_solve_mpfr.c:52-56 */
+    if (!solve_args_ok(x_mpfr, A, S, b, option)) return SLIP_INCORRECT_INPUT;      /* SLIP_solve_mpfr.c:52-56 */
     const int32_t n = A->n, nrhs = b->n;
-    if (n <= 0 || nrhs <= 0 || A->p[n] < 1) return SLIP_INCORRECT_INPUT;
     for (int32_t i = 0; i < n; i++) if (!x_mpfr[i]) return SLIP_INCORRECT_INPUT;
     const mpfr_prec_t prec = mpfr_get_prec(x_mpfr[0][0]);
     for (int32_t i = 0; i < n; i++)
@@ -414,15 +411,13 @@ SLIP_info SLIP_hip_solve_mpfr(mpfr_t **x_mpfr, SLIP_sparse *A, SLIP_LU_analysis 
     if (prec < 2 || prec > 65536) return SLIP_INCORRECT_INPUT;
     if (option->SLIP_MPFR_ROUND < 0 || option->SLIP_MPFR_ROUND > 4) return SLIP_INCORRECT_INPUT;      /* RNDN, Z, U, D, A: before any device work */
     const int64_t ne = (int64_t) n * nrhs, nl = ((int64_t) prec + 63) / 64;
-    slip_hip_factor *f = NULL;
-    int32_t *blen = NULL, snlen = 0, sdlen = 0;
-    uint64_t *blimbs = NULL, *snl = NULL, *sdl = NULL;
+    solve_input in = {0};
     int8_t *sign = (int8_t *) malloc((size_t) ne);
     int64_t *ex = (int64_t *) malloc((size_t) ne * 8);
     uint64_t *mant = (uint64_t *) malloc((size_t)(ne * nl) * 8);
-    SLIP_info ret = sign && ex && mant ? factor_for_solve(A, S, b, option, &f, &blen, &blimbs, &snlen, &snl, &sdlen, &sdl) : SLIP_OUT_OF_MEMORY;
+    SLIP_info ret = sign && ex && mant ? factor_for_solve(A, S, b, option, &in) : SLIP_OUT_OF_MEMORY;
     if (ret == SLIP_OK)
-        ret = solve_status(slip_hip_factor_solve_mpfr(f, 0, nrhs, blen, blimbs, snlen, snl, sdlen, sdl, (int32_t) prec,
+        ret = solve_status(slip_hip_factor_solve_mpfr(in.f, 0, nrhs, in.blen, in.blimbs, in.snlen, in.snl, in.sdlen, in.sdl, (int32_t) prec,
                                                       (int32_t) option->SLIP_MPFR_ROUND, sign, ex, mant, NULL, NULL));
     if (ret == SLIP_OK)
         for (int32_t j = 0; j < nrhs; j++)
@@ -433,8 +428,7 @@ SLIP_info SLIP_hip_solve_mpfr(mpfr_t **x_mpfr, SLIP_sparse *A, SLIP_LU_analysis 
                 mpz_roinit_n(z, (const mp_limb_t *)(mant + t * nl), sign[t] < 0 ? -(mp_size_t) nl : (mp_size_t) nl);
                 mpfr_set_z_2exp(x_mpfr[i][j], z, (mpfr_exp_t)(ex[t] - 64 * nl), MPFR_RNDN);      /* exact: prec bits at most */
             }
-    if (f) slip_hip_factor_destroy(f);
-    free(sign); free(ex); free(mant); free(blen); free(blimbs); free(snl); free(sdl);
+    solve_input_free(&in); free(sign); free(ex); free(mant);
     return ret;
 }
 
