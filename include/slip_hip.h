@@ -25,6 +25,8 @@
  *   slip_hip_factor_check_transpose           UMFPACK's A' system are the transposed solves of other sparse LUs)
  *   slip_hip_factor_rewind,              <->  no counterpart: the reference factorises from column 0 (KLU's klu_refactor,
  *   slip_hip_factor_replace_column            a simplex code's basis change are what other codes offer between two solves)
+ *   slip_hip_factor_multiply,            <->  no counterpart (SLIP_check_solution forms A x - b and keeps only the verdict):
+ *   slip_hip_matrix_*                         the exact sparse products of a simplex code's pricing and of a residual
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
  *
  * The GMP-typed drop-in  SLIP_LU_factorize(L,U,A,S,rhos,pinv,option)  built on
@@ -382,6 +384,54 @@ int slip_hip_factor_replace_column(slip_hip_factor *f, int32_t j, int32_t nz, co
  * limbs the slab can hold.  After any sequence of replacements out[1] <= 2 * out[0] + (entries at creation) and
  * out[3] <= 2 * out[2] + (limbs at creation). */
 int slip_hip_factor_a_storage(const slip_hip_factor *f, int64_t out[4]);
+
+/* Exact sparse products on the device, returned:  r_c = op(A) x_c - d_c b_c  for nvec vectors, every r an exact signed big
+ * integer (the residual slip_hip_factor_check only tests for zero; with blen == NULL the product op(A) x_c alone).  x, b and d
+ * are limb slabs as everywhere (signed limb counts, limbs back to back, x_limbs / b_limbs / d_limbs the limbs each array
+ * holds); the result is one such slab, normalised: the top limb of an entry is nonzero, a zero has count 0 and no limbs.
+ * *rlen_out (entries of one vector times nvec counts) and *rlimbs_out (*rnl_out limbs) are malloc'ed: slip_hip_free.
+ *
+ * slip_hip_factor_multiply works on the resident A of a handle made by slip_hip_factor_create, in the conventions of the
+ * solves and checks, so what a solve returns goes straight in:
+ *   transpose 0:  r = A(:,q) x - d b:    x[c*n + p] by pivot POSITION (as slip_hip_factor_solve returns it), r and b by
+ *                 original row;
+ *   transpose 1:  r = A(:,q)^T x - d b:  x[c*n + i] by original ROW id (as slip_hip_factor_solve_transpose returns it), r and b
+ *                 by position k (column q[k]).
+ * b given and dlen == NULL: every d_c is det = rho[n-1], which needs the complete factorisation (then a solve's output
+ * gives r = 0).  Without b, or with d given (one nonzero d_c per vector), only the resident A is used: any state of the
+ * factorisation will do, also after slip_hip_factor_rewind or slip_hip_factor_replace_column (the new matrix).  A row
+ * repeated in a column keeps its LAST value, as everywhere on a handle.
+ *
+ * slip_hip_matrix_*: an m x ncols CSC integer matrix kept resident without a factorisation (the non-basic columns a simplex
+ * code prices every iteration), prepared as slip_hip_factor_create prepares A (bounds, a repeated row keeps its LAST value,
+ * high zero limbs trimmed; m and ncols below 2^24 - 1).  transpose 0: r = M x (x: ncols entries per vector, r and b: m);
+ * transpose 1: r = M^T x (x: m, r and b: ncols).  With b, d is required.
+ *
+ * SLIP_HIP_INCORRECT_INPUT: a NULL required argument, nvec < 1, a limb array shorter than its counts say, d without b, a
+ * zero d_c, b without d on a matrix or on an incomplete factorisation, a handle from slip_hip_factor_from_factors; a broken
+ * handle answers SLIP_HIP_DEVICE_ERROR. */
+int slip_hip_factor_multiply(slip_hip_factor *f, int32_t transpose, int32_t nvec,
+                             const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                             const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,      /* optional */
+                             const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,      /* optional: one per vector */
+                             int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream);
+/* device time of the kernels of the last product of the handle / the matrix, milliseconds */
+double slip_hip_factor_multiply_ms(const slip_hip_factor *f);
+
+typedef struct slip_hip_matrix slip_hip_matrix;
+int slip_hip_matrix_create(slip_hip_matrix **out, int32_t m, int32_t ncols,
+                           const int64_t *Ap, const int32_t *Ai, const int32_t *Alen, const uint64_t *Alimbs);
+int slip_hip_matrix_multiply(slip_hip_matrix *M, int32_t transpose, int32_t nvec,
+                             const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                             const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                             const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                             int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream);
+double slip_hip_matrix_multiply_ms(const slip_hip_matrix *M);
+void slip_hip_matrix_destroy(slip_hip_matrix *M);
+/* that time of this thread's last product by pass: out[0] the widths, out[1] the offset scans, out[2] the products, out[3] the
+ * packing (the staging slab of a product is bounded: SLIP_HIP_PRODUCT_STAGE_KB kilobytes, environment, default 262144; vectors
+ * beyond it are taken in further groups) */
+int slip_hip_multiply_passes(double out[4]);
 
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize

@@ -5,6 +5,6 @@ and the GMP-typed drop-in shim (csrc/libslip_lu_hip.so); this package is the thi
 ctypes layer the tests and bench.py use.
 """
 from . import api  # noqa: F401
-from .api import (Factorization, SlipError, check_solution, factorize, ints_to_slab, matgen, read_triplet,  # noqa: F401
-                  solution_to_double, solution_to_mpfr, solution_to_mpfr_paths, solution_to_rational,
+from .api import (Factorization, SlipError, SparseMatrix, check_solution, factorize, ints_to_slab, matgen,  # noqa: F401
+                  multiply_passes, read_triplet, solution_to_double, solution_to_mpfr, solution_to_mpfr_paths, solution_to_rational,
                   solution_to_rational_paths, write_triplet)

@@ -44,7 +44,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_to_rational_paths", "slip_hip_solution_to_rational_paths",
            "slip_hip_factor_solve_mpfr", "slip_hip_solution_to_mpfr", "slip_hip_factor_to_mpfr_ms",
            "slip_hip_factor_to_mpfr_paths", "slip_hip_solution_to_mpfr_paths",
-           "slip_hip_factor_rewind", "slip_hip_factor_replace_column", "slip_hip_factor_a_storage")
+           "slip_hip_factor_rewind", "slip_hip_factor_replace_column", "slip_hip_factor_a_storage",
+           "slip_hip_factor_multiply", "slip_hip_factor_multiply_ms", "slip_hip_matrix_create", "slip_hip_matrix_multiply",
+           "slip_hip_matrix_multiply_ms", "slip_hip_matrix_destroy", "slip_hip_multiply_passes")
 
 _libs = {}
 
@@ -142,5 +144,20 @@ def load(path=None):
     lib.slip_hip_factor_replace_column.restype = C.c_int
     lib.slip_hip_factor_a_storage.argtypes = [vp, vp]
     lib.slip_hip_factor_a_storage.restype = C.c_int
+    lib.slip_hip_factor_multiply.argtypes = ([vp, C.c_int32, C.c_int32] + [vp, vp, i64] * 3
+                                             + [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp])
+    lib.slip_hip_factor_multiply.restype = C.c_int
+    lib.slip_hip_factor_multiply_ms.argtypes = [vp]
+    lib.slip_hip_factor_multiply_ms.restype = C.c_double
+    lib.slip_hip_matrix_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, vp, vp, vp, vp]
+    lib.slip_hip_matrix_create.restype = C.c_int
+    lib.slip_hip_matrix_multiply.argtypes = lib.slip_hip_factor_multiply.argtypes
+    lib.slip_hip_matrix_multiply.restype = C.c_int
+    lib.slip_hip_matrix_multiply_ms.argtypes = [vp]
+    lib.slip_hip_matrix_multiply_ms.restype = C.c_double
+    lib.slip_hip_matrix_destroy.argtypes = [vp]
+    lib.slip_hip_matrix_destroy.restype = None
+    lib.slip_hip_multiply_passes.argtypes = [vp]
+    lib.slip_hip_multiply_passes.restype = C.c_int
     _libs[path] = lib
     return lib

@@ -198,6 +198,83 @@ def solution_to_mpfr_paths(lib_path=None):
     return _paths(_lib.load(lib_path).slip_hip_solution_to_mpfr_paths)
 
 
+def _multiply(lib, fn, handle, nx, nout, xlen, xlimbs, nvec, transpose, b, d, stream):
+    """one call of slip_hip_factor_multiply / slip_hip_matrix_multiply: x holds nx entries per vector, b and the result nout;
+    b and d are None or (signed limb counts, limbs)"""
+    nvec = int(nvec)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    if nvec >= 1 and xlen.size != nx * nvec:
+        raise ValueError(f"{fn}: xlen must hold {nx} entries per vector")
+    args = [xlen.ctypes.data, xlimbs.ctypes.data, xcap]
+    keep = []
+    for name, part, count in (("b", b, nout * nvec), ("d", d, nvec)):
+        if part is None:
+            args += [None, None, 0]
+            continue
+        plen, plimbs, pcap = _limb_arrays(*part)
+        if nvec >= 1 and plen.size != count:
+            raise ValueError(f"{fn}: {name} must hold {count} entries")
+        keep.append((plen, plimbs))
+        args += [plen.ctypes.data, plimbs.ctypes.data, pcap]
+    pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+    rc = getattr(lib, fn)(handle, int(bool(transpose)), nvec, *args, C.byref(pl), C.byref(px), C.byref(nl), C.c_void_p(stream or 0))
+    if rc:
+        raise SlipError(rc, fn)
+    return _take_slab(lib, pl, px, nl, nout * nvec)
+
+
+def multiply_passes(lib_path=None):
+    """device ms of this thread's last product (Factorization.multiply, SparseMatrix.multiply) by pass: [the widths, the offset
+    scans, the products, the packing]"""
+    out = np.zeros(4, np.float64)
+    _lib.load(lib_path).slip_hip_multiply_passes(out.ctypes.data)
+    return [float(v) for v in out]
+
+
+class SparseMatrix:
+    """An m x ncols integer matrix resident on one GPU without a factorisation (handle of slip_hip_matrix_*): the CSC as
+    Factorization() takes it, a repeated row keeping its LAST value."""
+
+    def __init__(self, m, ncols, Ap, Ai, Alen, Alimbs, lib_path=None):
+        self.lib = _lib.load(lib_path)
+        self.m, self.ncols = int(m), int(ncols)
+        Ap = np.ascontiguousarray(Ap, dtype=np.int64)
+        Ai = np.ascontiguousarray(Ai, dtype=np.int32)
+        Alen, Alimbs, _ = _limb_arrays(Alen, Alimbs)
+        if self.ncols >= 0 and Ap.size != self.ncols + 1:
+            raise ValueError("SparseMatrix: Ap needs ncols+1 entries")
+        if Ai.size == 0:
+            Ai, Alen = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self.h = C.c_void_p()
+        rc = self.lib.slip_hip_matrix_create(C.byref(self.h), self.m, self.ncols, Ap.ctypes.data, Ai.ctypes.data,
+                                             Alen.ctypes.data, Alimbs.ctypes.data)
+        if rc:
+            self.h = None
+            raise SlipError(rc, "slip_hip_matrix_create")
+
+    def multiply(self, xlen, xlimbs, nvec=1, transpose=False, b=None, d=None, stream=None):
+        """The exact product on the device (slip_hip_matrix_multiply): r_c = M x_c - d_c b_c (x: ncols entries per vector, r
+        and b: m), with transpose=True r_c = M^T x_c - d_c b_c (x: m, r and b: ncols).  b, d: None or (signed limb counts,
+        limbs), d one nonzero value per vector and required with b.  Returns (rlen, rlimbs), normalised."""
+        nx, nout = (self.m, self.ncols) if transpose else (self.ncols, self.m)
+        return _multiply(self.lib, "slip_hip_matrix_multiply", self.h, nx, nout, xlen, xlimbs, nvec, transpose, b, d, stream)
+
+    def multiply_ms(self):
+        """device ms of the kernels of the last multiply"""
+        return self.lib.slip_hip_matrix_multiply_ms(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.slip_hip_matrix_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def matgen(n, density, bits, seed, lib_path=None):
     """The benchmark's synthetic CSC (slip_matgen.h) -> Ap, Ai, Ax (int64 values)."""
     lib = _lib.load(lib_path)
@@ -526,6 +603,18 @@ class Factorization:
 
     def check_ms(self):
         return self.lib.slip_hip_factor_check_ms(self.h)
+
+    def multiply(self, xlen, xlimbs, nvec=1, transpose=False, b=None, d=None, stream=None):
+        """The exact product with the resident A on the device (slip_hip_factor_multiply): r_c = A(:,q) x_c - d_c b_c with x
+        by pivot position as `solve` returns it, r and b by original row; with transpose=True r_c = A(:,q)^T x_c - d_c b_c
+        with x by original row id as `solve_transpose` returns it, r and b by position.  b, d: None or (signed limb counts,
+        limbs); b alone: d = det (needs the complete factorisation); without b the product alone, in any state of the
+        factorisation.  Returns (rlen, rlimbs), normalised: a zero has count 0 and no limbs."""
+        return _multiply(self.lib, "slip_hip_factor_multiply", self.h, self.n, self.n, xlen, xlimbs, nvec, transpose, b, d, stream)
+
+    def multiply_ms(self):
+        """device ms of the kernels of the last multiply"""
+        return self.lib.slip_hip_factor_multiply_ms(self.h)
 
     def solve_transpose_ms(self):
         """(device ms of the last transposed solve's substitution kernels, ms of that call's view build: 0 when it was reused)"""

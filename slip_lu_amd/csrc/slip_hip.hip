@@ -224,8 +224,24 @@ template <int D> SLIP_DEV WR<D> slip_check_mac_reg(WR<D> acc, const dig_t *a, in
     return wr_addsub<D>(acc, la <= ly ? wr_mul<D>(Av, la, Y) : wr_mul<D>(Y, ly, Av), sub);
 }
 
-/* nonzero when r_i != 0: register path, W <= 64*D */
-template <int D> SLIP_DEV int slip_check_row_reg(const SlipCheckArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1)
+/* The sums below are shared by slip_check_kernel and slip_product_kernel (Args: SlipCheckArgs or SlipProductArgs; xb: the
+ * vector's first entry of x; bi: the entry of b, negative for none). */
+
+/* the width of one (row, vector), from the operands' own lengths: W = max(max_e(|a_e| + |x_e|), |d| + |b_i|) + 1 */
+template <class Args> SLIP_DEV int slip_row_width(const Args &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1)
+{
+    uint32_t w = 0;
+    for (int64_t t = r0 + slip_lane(); t < r1; t += SLIP_WAVE) {
+        const uint32_t s = (uint32_t)(slip_abs(A.alen[A.re[t]]) + slip_abs(A.xlen[xb + A.rx[t]]));
+        if (s > w) w = s;
+    }
+    w = slip_wave_max_u32(w);
+    const uint32_t wdb = bi >= 0 ? (uint32_t)(slip_abs(A.dlen[c]) + slip_abs(A.blen[bi])) : 0u;
+    return (int)(w > wdb ? w : wdb) + 1;
+}
+
+/* r_i modulo B^(64*D): register path, W <= 64*D */
+template <int D, class Args> SLIP_DEV WR<D> slip_row_sum_reg(const Args &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1)
 {
     WR<D> acc = wr_zero<D>();
     for (int64_t t = r0; t < r1; t++) {
@@ -235,18 +251,19 @@ template <int D> SLIP_DEV int slip_check_row_reg(const SlipCheckArgs &A, int64_t
         acc = slip_check_mac_reg<D>(acc, (const dig_t *)(A.alimbs + A.aoff[e]), slip_abs(sa),
                                     (const dig_t *)(A.xlimbs + A.xoff[xe]), slip_abs(sx), (sa < 0) != (sx < 0));
     }
+    if (bi < 0) return acc;
     const int32_t sd = A.dlen[c], sb = A.blen[bi];
     if (sd != 0 && sb != 0) {
         const dig_t *d = (const dig_t *)(A.dlimbs + A.doff[c]), *b = (const dig_t *)(A.blimbs + A.boff[bi]);
         const int ld = slip_abs(sd), lb = slip_abs(sb), sub = (sd < 0) == (sb < 0);     /* acc -= d*b */
         acc = lb <= ld ? slip_check_mac_reg<D>(acc, b, lb, d, ld, sub) : slip_check_mac_reg<D>(acc, d, ld, b, lb, sub);
     }
-    return wr_len<D>(acc) != 0;
+    return acc;
 }
 
-/* the same on W-digit buffers in global memory (acc, prod: this wave's scratch) */
-SLIP_DEV int slip_check_row_wide(const SlipCheckArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1, int W,
-                                 dig_t *acc, dig_t *prod)
+/* the same modulo B^W on W-digit buffers in global memory (acc: the sum; prod: this wave's scratch) */
+template <class Args> SLIP_DEV void slip_row_sum_wide(const Args &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1, int W,
+                                                      dig_t *acc, dig_t *prod)
 {
     for (int k = slip_lane(); k < W; k += SLIP_WAVE) acc[k] = 0u;
     slip_wave_sync();
@@ -257,11 +274,25 @@ SLIP_DEV int slip_check_row_wide(const SlipCheckArgs &A, int64_t xb, int64_t bi,
         wb_mul_lo(prod, (const dig_t *)(A.alimbs + A.aoff[e]), slip_abs(sa), (const dig_t *)(A.xlimbs + A.xoff[xe]), slip_abs(sx), W);
         wb_addsub(acc, acc, W, prod, W, W, (sa < 0) != (sx < 0));
     }
+    if (bi < 0) return;
     const int32_t sd = A.dlen[c], sb = A.blen[bi];
     if (sd != 0 && sb != 0) {
         wb_mul_lo(prod, (const dig_t *)(A.dlimbs + A.doff[c]), slip_abs(sd), (const dig_t *)(A.blimbs + A.boff[bi]), slip_abs(sb), W);
         wb_addsub(acc, acc, W, prod, W, W, (sd < 0) == (sb < 0));
     }
+}
+
+/* nonzero when r_i != 0: register path, W <= 64*D */
+template <int D> SLIP_DEV int slip_check_row_reg(const SlipCheckArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1)
+{
+    return wr_len<D>(slip_row_sum_reg<D>(A, xb, bi, c, r0, r1)) != 0;
+}
+
+/* the same on the memory path (acc, prod: this wave's scratch) */
+SLIP_DEV int slip_check_row_wide(const SlipCheckArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1, int W,
+                                 dig_t *acc, dig_t *prod)
+{
+    slip_row_sum_wide(A, xb, bi, c, r0, r1, W, acc, prod);
     return wb_len(acc, W) != 0;
 }
 
@@ -279,15 +310,7 @@ static void slip_check_body(SlipCheckArgs A)
     for (int64_t it = wave0; it < items; it += nwaves) {
         const int c = (int)(it / A.n), i = (int)(it - (int64_t) c * A.n);
         const int64_t xb = (int64_t) c * A.n, bi = xb + i, r0 = A.rp[i], r1 = A.rp[i + 1];
-        /* the width of this (row, rhs), from the operands' own lengths */
-        uint32_t w = 0;
-        for (int64_t t = r0 + lane; t < r1; t += SLIP_WAVE) {
-            const uint32_t s = (uint32_t)(slip_abs(A.alen[A.re[t]]) + slip_abs(A.xlen[xb + A.rx[t]]));
-            if (s > w) w = s;
-        }
-        w = slip_wave_max_u32(w);
-        const uint32_t wdb = (uint32_t)(slip_abs(A.dlen[c]) + slip_abs(A.blen[bi]));
-        const int W = (int)(w > wdb ? w : wdb) + 1;
+        const int W = slip_row_width(A, xb, bi, c, r0, r1);
         int bad;
         if (W <= 64) bad = slip_check_row_reg<1>(A, xb, bi, c, r0, r1);
         else if (W <= 128) bad = slip_check_row_reg<2>(A, xb, bi, c, r0, r1);
@@ -298,6 +321,84 @@ static void slip_check_body(SlipCheckArgs A)
             slip_atomic_min_i32(&A.first_bad[c], i);
             slip_atomic_add_i32(&A.nbad[c], 1);
         }
+    }
+}
+
+/* Exact sparse product (slip_hip_factor_multiply, slip_hip_matrix_multiply): the residual of the check, kept.
+ *     r_i = sum_e A(i, j_e) * x_c[x(e)]  -  d_c * b_c[i]        (blen == NULL: the product alone)
+ * over the same kind of view and operand records as SlipCheckArgs, except that the output rows (nout) and the entries of one
+ * vector of x (nx) need not be as many: the view may be that of a rectangular matrix.  One wavefront per (row, vector),
+ * grid-stride, wave-uniform.
+ *
+ * The sign: |r_i| < 2^24 * B^(W-1) < B^W / 2 by the check's bound on the terms of a row, so the sum modulo B^M, M >= W, is
+ * r_i in two's complement: the top bit of digit M-1 is its sign, and 0 - acc its magnitude when that bit is set.
+ *
+ * phase 0 writes W per item (wlen); the host lays the staging slab out from it (slip_offscan_kernel: an item owns
+ * (W + 1) / 2 limbs at soff) and phase 1 leaves the magnitude there in whole limbs and the signed digit count in rlen.  On
+ * the memory path (W > 256) the sum is formed in the item's own staging region, M = its (W + 1) & ~1 digits, and only the
+ * product of a term lives in the wave's scratch (wcap digits, wcap even). */
+struct SlipProductArgs {
+    int32_t nout, nx, nvec, phase;
+    const int64_t *rp, *re; const int32_t *rx;                                     /* view of A: nout rows                   */
+    const int32_t *alen; const int64_t *aoff; const uint64_t *alimbs;              /* A: signed digit counts, limb offsets   */
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* x: entry c*nx + x(e)                   */
+    const int32_t *blen; const int64_t *boff; const uint64_t *blimbs;              /* b: entry c*nout + i, or NULL           */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* d_c: entry c (with b)                  */
+    int32_t *wlen;                                                                 /* W per item                             */
+    const int64_t *soff; uint64_t *stage; int32_t *rlen;                           /* phase 1: staging slab, signed digits   */
+    dig_t *scratch; int32_t wcap;                                                  /* memory path: wcap digits per wave      */
+};
+
+/* the sum of one item on the register path, W <= 64*D: its signed digit count; the magnitude goes to out in whole limbs */
+template <int D> SLIP_DEV int slip_product_row_reg(const SlipProductArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1, dig_t *out)
+{
+    WR<D> acc = slip_row_sum_reg<D>(A, xb, bi, c, r0, r1);
+    const int neg = (int)(wr_digit<D>(acc, 64 * D - 1) >> 31);
+    if (neg) acc = wr_addsub<D>(wr_zero<D>(), acc, 1);
+    const int len = wr_len<D>(acc);
+    wr_store<D>(out, acc, (len + 1) & ~1);
+    return neg ? -len : len;
+}
+
+/* the same on the memory path: the sum is formed in out, Wp = (W + 1) & ~1 digits */
+SLIP_DEV int slip_product_row_wide(const SlipProductArgs &A, int64_t xb, int64_t bi, int c, int64_t r0, int64_t r1, int Wp,
+                                   dig_t *out, dig_t *prod)
+{
+    slip_row_sum_wide(A, xb, bi, c, r0, r1, Wp, out, prod);
+    const int neg = (int)(out[Wp - 1] >> 31);
+    if (neg) wb_addsub(out, (const dig_t *) 0, 1, out, Wp, Wp, 1, 0u);
+    const int len = wb_len(out, Wp);
+    return neg ? -len : len;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_product_kernel(SlipProductArgs A)
+#else
+static void slip_product_body(SlipProductArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    dig_t *prod = A.scratch ? A.scratch + wave0 * A.wcap : (dig_t *) 0;
+    const int64_t items = (int64_t) A.nout * A.nvec;
+    for (int64_t it = wave0; it < items; it += nwaves) {
+        const int c = (int)(it / A.nout), i = (int)(it - (int64_t) c * A.nout);
+        const int64_t xb = (int64_t) c * A.nx, bi = A.blen ? it : -1, r0 = A.rp[i], r1 = A.rp[i + 1];
+        if (A.phase == 0) {
+            const int W = slip_row_width(A, xb, bi, c, r0, r1);
+            if (lane == 0) A.wlen[it] = W;
+            continue;
+        }
+        const int W = A.wlen[it];
+        dig_t *out = (dig_t *)(A.stage + A.soff[it]);
+        int len;
+        if (W <= 64) len = slip_product_row_reg<1>(A, xb, bi, c, r0, r1, out);
+        else if (W <= 128) len = slip_product_row_reg<2>(A, xb, bi, c, r0, r1, out);
+        else if (W <= 192) len = slip_product_row_reg<3>(A, xb, bi, c, r0, r1, out);
+        else if (W <= 256) len = slip_product_row_reg<4>(A, xb, bi, c, r0, r1, out);
+        else len = slip_product_row_wide(A, xb, bi, c, r0, r1, (W + 1) & ~1, out, prod);     /* at most wcap: the host sized it */
+        if (lane == 0) A.rlen[it] = len;
     }
 }
 
@@ -1498,6 +1599,8 @@ struct slip_hip_factor {
     /* slip_hip_factor_check: the row-ordered view of A, built on the first check (x index = pivot position) */
     int64_t *chk_rp, *chk_re; int32_t *chk_rx;
     double check_ms;
+    /* slip_hip_factor_multiply: device time of the last product's kernels (slip_hip_multiply_passes splits it) */
+    double multiply_ms;
     /* slip_hip_factor_solve_transpose: the transposed view of the complete factors (slip_tview_kernel), built on the first
      * transposed solve, dropped at reset; its own pivot records and inverse cache (stride tinvcap), the handle's limbs */
     int64_t *tLp, *tUp; int32_t *tLi, *tUi; SlipEnt *tLe, *tUe; SlipPiv *tpiv; uint32_t *tinvd; int32_t tinvcap;
@@ -2015,23 +2118,25 @@ static int make_ident(slip_hip_factor *f)
     return rc;
 }
 
-/* host-side preparation of A (slip_hip_factor_create, slip_hip_check_solution): bounds check, de-duplicate, digit counts.
- * out: the CSC with a repeated row of a column kept once, with its LAST value; signed DIGIT counts, limb offsets, high
- * zero limbs trimmed; maxdig = digits of the widest entry (at least 1).  Release with host_a_free. */
+/* host-side preparation of an m x n CSC (slip_hip_factor_create, slip_hip_check_solution: m = n; slip_hip_matrix_create): bounds
+ * check, de-duplicate, digit counts.  out: the CSC with a repeated row of a column kept once, with its LAST value; signed
+ * DIGIT counts, limb offsets, high zero limbs trimmed; maxdig = digits of the widest entry (at least 1).  Release with
+ * host_a_free. */
 struct SlipHostA { int64_t *Ap; int32_t *Ai, *Alen; int64_t *Aoff; uint64_t *Alimbs; int64_t nnz, nl; int32_t maxdig; };
 static void host_a_free(SlipHostA *a) { free(a->Ap); free(a->Ai); free(a->Alen); free(a->Aoff); free(a->Alimbs); memset(a, 0, sizeof *a); }
-static int prepare_A(int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *Alen, const uint64_t *Alimbs, SlipHostA *out)
+static int prepare_A(int32_t m, int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *Alen, const uint64_t *Alimbs, SlipHostA *out)
 {
     memset(out, 0, sizeof *out);
-    /* column and row numbers travel in 24-bit fields of the commit protocol (verdict words, package records) */
-    if (n >= (1 << 24) - 1) return SLIP_HIP_INCORRECT_INPUT;
+    /* column and row numbers travel in 24-bit fields of the commit protocol (verdict words, package records); a row or a
+     * column of fewer than 2^24 - 1 entries is also what the fixed-width sums of slip_check_kernel and slip_product_kernel need */
+    if (m >= (1 << 24) - 1 || n >= (1 << 24) - 1) return SLIP_HIP_INCORRECT_INPUT;
     const int64_t annz = Ap[n];
     if (Ap[0] != 0 || annz < 1) return SLIP_HIP_INCORRECT_INPUT;
 
     int64_t *hAp = (int64_t *) malloc(((size_t) n + 1) * 8);
     int32_t *hAi = (int32_t *) malloc((size_t) annz * 4), *hAlen = (int32_t *) malloc((size_t) annz * 4);
     int64_t *hAoff = (int64_t *) malloc((size_t) annz * 8), *inoff = (int64_t *) malloc(((size_t) annz + 1) * 8);
-    int32_t *last = (int32_t *) malloc((size_t) n * 4);
+    int32_t *last = (int32_t *) malloc((size_t) m * 4);
     if (!hAp || !hAi || !hAlen || !hAoff || !inoff || !last) {
         free(hAp); free(hAi); free(hAlen); free(hAoff); free(inoff); free(last);
         return SLIP_HIP_OUT_OF_MEMORY;
@@ -2039,7 +2144,7 @@ static int prepare_A(int32_t n, const int64_t *Ap, const int32_t *Ai, const int3
     int bad = 0;
     inoff[0] = 0;
     for (int64_t p = 0; p < annz; p++) inoff[p + 1] = inoff[p] + (Alen[p] < 0 ? -(int64_t) Alen[p] : Alen[p]);
-    for (int32_t i = 0; i < n; i++) last[i] = -1;
+    for (int32_t i = 0; i < m; i++) last[i] = -1;
     uint64_t *hAlimbs = (uint64_t *) malloc((size_t)(inoff[annz] > 0 ? inoff[annz] : 1) * 8);
     if (!hAlimbs) bad = 2;
     int64_t onz = 0, ol = 0;
@@ -2050,7 +2155,7 @@ static int prepare_A(int32_t n, const int64_t *Ap, const int32_t *Ai, const int3
         /* a repeated row keeps its LAST value (slip_get_column.c:22 overwrites) */
         for (int64_t p = Ap[j]; p < Ap[j + 1]; p++) {
             int32_t r = Ai[p];
-            if (r < 0 || r >= n) { bad = 1; break; }
+            if (r < 0 || r >= m) { bad = 1; break; }
             last[r] = (int32_t)(p - Ap[j]);
         }
         if (bad) break;
@@ -2089,7 +2194,7 @@ extern "C" int slip_hip_factor_create(slip_hip_factor **out, int32_t n,
     if (opt_in) opt = *opt_in; else slip_hip_default_options(&opt);
     if (opt.pivot < 0 || opt.pivot > 5) return SLIP_HIP_INCORRECT_INPUT;
     SlipHostA ha;
-    TRY_(prepare_A(n, Ap, Ai, Alen, Alimbs, &ha));
+    TRY_(prepare_A(n, n, Ap, Ai, Alen, Alimbs, &ha));
     {
         char *seen = (char *) calloc((size_t) n, 1);
         int bad = !seen ? 2 : 0;
@@ -2712,49 +2817,75 @@ extern "C" int slip_hip_factor_rewind(slip_hip_factor *f, int32_t K, const int32
     return SLIP_HIP_OK;
 }
 
-/* the limbs the device counted for the live entries must be the host's figure: it sized the new slab */
-static int a_compact_total(const unsigned long long *bsum, int64_t blocks, int64_t live, hipStream_t stream)
+/* the limbs a scan counted (the sum of its workgroups' chunks) */
+static int offscan_total(const unsigned long long *bsum, int64_t blocks, int64_t *total_out, hipStream_t stream)
 {
     unsigned long long h[1024], total = 0;
     CK(hipMemcpyAsync(h, bsum, (size_t) blocks * 8, hipMemcpyDeviceToHost, stream));
     CK(hipStreamSynchronize(stream));
     for (int64_t b = 0; b < blocks; b++) total += h[b];
-    return total == (unsigned long long) live ? 0 : SLIP_HIP_DEVICE_ERROR;
+    *total_out = (int64_t) total;
+    return 0;
+}
+
+/* the limbs the device counted for the live entries must be the host's figure: it sized the new slab */
+static int a_compact_total(const unsigned long long *bsum, int64_t blocks, int64_t live, hipStream_t stream)
+{
+    int64_t total = 0;
+    TRY_(offscan_total(bsum, blocks, &total, stream));
+    return total == live ? 0 : SLIP_HIP_DEVICE_ERROR;
+}
+
+/* the workgroups of a scan over `count` entries (at most 1024: bsum is read back into a fixed array) */
+static int64_t offscan_blocks(int64_t count)
+{
+#ifndef SLIP_EMULATE
+    int64_t blocks = (count + 2047) / 2048; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
+    return blocks;
+#else
+    (void) count;
+    return 2;
+#endif
+}
+
+/* both phases of slip_offscan_kernel: off[t] = the limbs of the entries before t, bsum[b] = the limbs of workgroup b's chunk
+ * (by hand: the emulated scan takes a block's share of tmp, which is __shared__ on the device) */
+static int offscan_run(int64_t count, const int32_t *len, int64_t *off, unsigned long long *bsum, int64_t blocks, hipStream_t stream)
+{
+    SlipOffScanArgs S; memset(&S, 0, sizeof S);
+    S.count = count; S.len = len; S.off = off; S.bsum = bsum;
+    int rc = 0;
+#ifndef SLIP_EMULATE
+    for (int phase = 0; phase < 2 && !rc; phase++) {
+        S.phase = phase;
+        hipLaunchKernelGGL(slip_offscan_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, S);
+        HIP_(hipGetLastError());
+    }
+#else
+    (void) stream;
+    uint64_t *tmp = (uint64_t *) calloc((size_t) blocks * 40, 8);
+    if (!tmp) rc = SLIP_HIP_OUT_OF_MEMORY;
+    for (int phase = 0; phase < 2 && !rc; phase++) {
+        S.phase = phase;
+        emu::launch((int) blocks, 128, [S, tmp]() { slip_offscan_body(S, tmp + 40 * slip_block()); }, 256 * 1024, 1);
+    }
+    free(tmp);
+#endif
+    return rc;
 }
 
 /* the dead limbs squeezed out of the slab of A: new offsets by a scan over the entries, the limbs moved entry by entry */
 static int a_compact(slip_hip_factor *f, hipStream_t stream)
 {
     const int64_t nnz = f->annz, live = f->alimbs, newcap = live + live / 2 + 1;
-#ifndef SLIP_EMULATE
-    int64_t blocks = (nnz + 2047) / 2048; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
-#else
-    const int64_t blocks = 2;
-#endif
+    const int64_t blocks = offscan_blocks(nnz);
     uint64_t *nl = NULL; int64_t *noff = NULL; unsigned long long *bsum = NULL;
     int rc = 0;
     A_(dev_alloc(&nl, newcap)); A_(dev_alloc(&noff, f->Acap_nz)); A_(dev_alloc(&bsum, blocks));
     if (!rc) {
-        SlipOffScanArgs S; memset(&S, 0, sizeof S);
-        S.count = nnz; S.len = f->dAlen; S.off = noff; S.bsum = bsum;
         SlipPackArgs A; memset(&A, 0, sizeof A);
         A.count = nnz; A.len = f->dAlen; A.soff = f->dAoff; A.doff = noff; A.src = f->dAlimbs; A.dst = nl;
-        /* (by hand: the emulated scan takes a block's share of tmp, which is __shared__ on the device) */
-#ifndef SLIP_EMULATE
-        for (int phase = 0; phase < 2 && !rc; phase++) {
-            S.phase = phase;
-            hipLaunchKernelGGL(slip_offscan_kernel, dim3((unsigned) blocks), dim3(256), 0, stream, S);
-            HIP_(hipGetLastError());
-        }
-#else
-        uint64_t *tmp = (uint64_t *) calloc((size_t) blocks * 40, 8);
-        if (!tmp) rc = SLIP_HIP_OUT_OF_MEMORY;
-        for (int phase = 0; phase < 2 && !rc; phase++) {
-            S.phase = phase;
-            emu::launch((int) blocks, 128, [S, tmp]() { slip_offscan_body(S, tmp + 40 * slip_block()); }, 256 * 1024, 1);
-        }
-        free(tmp);
-#endif
+        A_(offscan_run(nnz, f->dAlen, noff, bsum, blocks, stream));
         A_(a_compact_total(bsum, blocks, live, stream));
         A_(SERVICE_LAUNCH(pack, wave_blocks(nnz), stream, A));
         HIP_(hipStreamSynchronize(stream));
@@ -3458,8 +3589,9 @@ static thread_local int64_t slip_rational_paths_last[4];
 /* one slab of the result: the digit counts come down, the compact layout goes up, slip_pack_kernel moves the limbs and the
  * compact slab is all that is downloaded.  dlen: signed digit counts by slot (device); on return len_out holds signed LIMB counts. */
 static int pack_download(int64_t ne, const int32_t *dlen, const int64_t *dsoff, const uint64_t *dsrc, int min_one,
-                         int32_t **len_out, uint64_t **limbs_out, int64_t *nl_out, hipStream_t stream)
+                         int32_t **len_out, uint64_t **limbs_out, int64_t *nl_out, hipStream_t stream, double *pack_ms = NULL)
 {
+    SlipTimed timed;
     int32_t *hl = (int32_t *) malloc((size_t) ne * 4); int64_t *ho = (int64_t *) malloc((size_t) ne * 8);
     int64_t *dcoff = NULL; uint64_t *dpacked = NULL, *out = NULL;
     int rc = !hl || !ho ? SLIP_HIP_OUT_OF_MEMORY : 0;
@@ -3475,8 +3607,9 @@ static int pack_download(int64_t ne, const int32_t *dlen, const int64_t *dsoff, 
     if (!rc) {
         SlipPackArgs A; memset(&A, 0, sizeof A);
         A.count = ne; A.len = dlen; A.soff = dsoff; A.doff = dcoff; A.src = dsrc; A.dst = dpacked;
+        A_(timed.begin(stream));
         A_(SERVICE_LAUNCH(pack, wave_blocks(ne), stream, A));
-        HIP_(hipStreamSynchronize(stream));
+        A_(timed.end(stream, pack_ms));
     }
     out = (uint64_t *) malloc((size_t)(total > 0 ? total : 1) * 8);
     if (!out) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
@@ -3611,17 +3744,17 @@ extern "C" int slip_hip_solution_to_rational_paths(int64_t out[4])
 
 /* ---- exact solution check (SLIP_check_solution.c:31-113 as one integer test; kernel: slip_check_kernel) ---- */
 
-/* the row-ordered view of a CSC pattern (counting sort on the rows): rp[n+1]; per term its CSC entry and the index of x it
- * multiplies (xidx[j] for column j, or j itself when xidx is NULL) */
-static int build_row_view(int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *xidx, int64_t **rp_out, int64_t **re_out, int32_t **rx_out)
+/* the row-ordered view of an m x n CSC pattern (counting sort on the rows): rp[m+1]; per term its CSC entry and the index of
+ * x it multiplies (xidx[j] for column j, or j itself when xidx is NULL) */
+static int build_row_view(int32_t m, int32_t n, const int64_t *Ap, const int32_t *Ai, const int32_t *xidx, int64_t **rp_out, int64_t **re_out, int32_t **rx_out)
 {
     const int64_t nz = Ap[n];
-    int64_t *rp = (int64_t *) calloc((size_t) n + 1, 8), *re = (int64_t *) malloc((size_t)(nz > 0 ? nz : 1) * 8), *w = (int64_t *) malloc((size_t) n * 8);
+    int64_t *rp = (int64_t *) calloc((size_t) m + 1, 8), *re = (int64_t *) malloc((size_t)(nz > 0 ? nz : 1) * 8), *w = (int64_t *) malloc((size_t) m * 8);
     int32_t *rx = (int32_t *) malloc((size_t)(nz > 0 ? nz : 1) * 4);
     if (!rp || !re || !w || !rx) { free(rp); free(re); free(w); free(rx); return SLIP_HIP_OUT_OF_MEMORY; }
     for (int64_t e = 0; e < nz; e++) rp[Ai[e] + 1]++;
-    for (int32_t i = 0; i < n; i++) rp[i + 1] += rp[i];
-    memcpy(w, rp, (size_t) n * 8);
+    for (int32_t i = 0; i < m; i++) rp[i + 1] += rp[i];
+    memcpy(w, rp, (size_t) m * 8);
     for (int32_t j = 0; j < n; j++)
         for (int64_t e = Ap[j]; e < Ap[j + 1]; e++) { const int64_t t = w[Ai[e]]++; re[t] = e; rx[t] = xidx ? xidx[j] : j; }
     free(w);
@@ -3708,6 +3841,50 @@ static int build_col_view(slip_hip_factor *f)
     return rc;
 }
 
+/* the row view of the resident A, once per handle: x is indexed by pivot position, column q[p] -> p */
+static int build_pos_row_view(slip_hip_factor *f)
+{
+    const int32_t n = f->n;
+    int64_t *hAp = (int64_t *) malloc(((size_t) n + 1) * 8), *rp = NULL, *re = NULL;
+    int32_t *hAi = (int32_t *) malloc((size_t)(f->annz > 0 ? f->annz : 1) * 4), *hq = (int32_t *) malloc((size_t) n * 4), *qinv = (int32_t *) malloc((size_t) n * 4), *rx = NULL;
+    int rc = !hAp || !hAi || !hq || !qinv ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    DOWN_(hAp, f->dAp, ((size_t) n + 1) * 8); DOWN_(hAi, f->dAi, (size_t) f->annz * 4); DOWN_(hq, f->dq, (size_t) n * 4);
+    if (!rc) { for (int32_t p = 0; p < n; p++) qinv[hq[p]] = p; rc = build_row_view(n, n, hAp, hAi, qinv, &rp, &re, &rx); }
+    if (!rc) {
+        const int64_t nz = hAp[n];
+        if (dev_alloc(&f->chk_rp, (int64_t) n + 1) || dev_alloc(&f->chk_re, nz) || dev_alloc(&f->chk_rx, nz)) rc = SLIP_HIP_OUT_OF_MEMORY;
+        UP_(f->chk_rp, rp, ((size_t) n + 1) * 8); UP_(f->chk_re, re, (size_t) nz * 8); UP_(f->chk_rx, rx, (size_t) nz * 4);
+        if (rc) { dev_free(f->chk_rp); dev_free(f->chk_re); dev_free(f->chk_rx); f->chk_rp = NULL; f->chk_re = NULL; f->chk_rx = NULL; }
+    }
+    free(hAp); free(hAi); free(hq); free(qinv); free(rp); free(re); free(rx);
+    return rc;
+}
+
+/* d = det = rho[n-1] of a complete handle, read in place from the L slab through its pivot record: the records of nrhs
+ * denominators (device; limbs: P.Llimbs), dmaxdig its digits */
+static int det_records(slip_hip_factor *f, int32_t nrhs, int32_t **ddlen_out, int64_t **ddoff_out, int32_t *dmaxdig_out)
+{
+    SlipParams *P = &f->P;
+    const int32_t n = f->n;
+    int32_t *ddlen = NULL; int64_t *ddoff = NULL;
+    int rc = 0;
+    SlipPiv pr;
+    DOWN_(&pr, P->piv.p_ + (n - 1), sizeof pr);
+    if (!rc && (pr.len == 0 || pr.off < 0 || pr.off + (((pr.len < 0 ? -pr.len : pr.len) + 1) >> 1) > P->Lcap_nl)) rc = SLIP_HIP_DEVICE_ERROR;
+    int32_t *hl = (int32_t *) malloc((size_t) nrhs * 4); int64_t *ho = (int64_t *) malloc((size_t) nrhs * 8);
+    if (!rc && (!hl || !ho)) rc = SLIP_HIP_OUT_OF_MEMORY;
+    if (!rc) {
+        for (int32_t c = 0; c < nrhs; c++) { hl[c] = pr.len; ho[c] = pr.off; }
+        *dmaxdig_out = pr.len < 0 ? -pr.len : pr.len;
+        A_(dev_alloc(&ddlen, nrhs)); A_(dev_alloc(&ddoff, nrhs));
+        UP_(ddlen, hl, (size_t) nrhs * 4); UP_(ddoff, ho, (size_t) nrhs * 8);
+    }
+    free(hl); free(ho);
+    if (rc) { dev_free(ddlen); dev_free(ddoff); return rc; }
+    *ddlen_out = ddlen; *ddoff_out = ddoff;
+    return SLIP_HIP_OK;
+}
+
 /* slip_hip_factor_check (transpose 0: A(:,q) xnum == det b by row) and slip_hip_factor_check_transpose (1: A(:,q)^T xnum ==
  * det b by position): the same kernel over the row view or the column view of the resident A */
 static int check_on_handle(slip_hip_factor *f, int transpose, int32_t nrhs,
@@ -3726,37 +3903,9 @@ static int check_on_handle(slip_hip_factor *f, int transpose, int32_t nrhs,
     else memset(&xs, 0, sizeof xs);
     SlipParams *P = &f->P;
     if (!rc && transpose && !f->chkt_rp) rc = build_col_view(f);
-    /* the row view of the resident A, once per handle: x is indexed by pivot position, column q[p] -> p */
-    if (!rc && !transpose && !f->chk_rp) {
-        int64_t *hAp = (int64_t *) malloc(((size_t) n + 1) * 8), *rp = NULL, *re = NULL;
-        int32_t *hAi = (int32_t *) malloc((size_t)(f->annz > 0 ? f->annz : 1) * 4), *hq = (int32_t *) malloc((size_t) n * 4), *qinv = (int32_t *) malloc((size_t) n * 4), *rx = NULL;
-        if (!hAp || !hAi || !hq || !qinv) rc = SLIP_HIP_OUT_OF_MEMORY;
-        DOWN_(hAp, f->dAp, ((size_t) n + 1) * 8); DOWN_(hAi, f->dAi, (size_t) f->annz * 4); DOWN_(hq, f->dq, (size_t) n * 4);
-        if (!rc) { for (int32_t p = 0; p < n; p++) qinv[hq[p]] = p; rc = build_row_view(n, hAp, hAi, qinv, &rp, &re, &rx); }
-        if (!rc) {
-            const int64_t nz = hAp[n];
-            if (dev_alloc(&f->chk_rp, (int64_t) n + 1) || dev_alloc(&f->chk_re, nz) || dev_alloc(&f->chk_rx, nz)) rc = SLIP_HIP_OUT_OF_MEMORY;
-            UP_(f->chk_rp, rp, ((size_t) n + 1) * 8); UP_(f->chk_re, re, (size_t) nz * 8); UP_(f->chk_rx, rx, (size_t) nz * 4);
-            if (rc) { dev_free(f->chk_rp); dev_free(f->chk_re); dev_free(f->chk_rx); f->chk_rp = NULL; f->chk_re = NULL; f->chk_rx = NULL; }
-        }
-        free(hAp); free(hAi); free(hq); free(qinv); free(rp); free(re); free(rx);
-    }
-    /* d = det = rho[n-1], read in place from the L slab through its pivot record */
+    if (!rc && !transpose && !f->chk_rp) rc = build_pos_row_view(f);
     int32_t *ddlen = NULL; int64_t *ddoff = NULL; int32_t dmaxdig = 0;
-    if (!rc) {
-        SlipPiv pr;
-        DOWN_(&pr, P->piv.p_ + (n - 1), sizeof pr);
-        if (!rc && (pr.len == 0 || pr.off < 0 || pr.off + (((pr.len < 0 ? -pr.len : pr.len) + 1) >> 1) > P->Lcap_nl)) rc = SLIP_HIP_DEVICE_ERROR;
-        int32_t *hl = (int32_t *) malloc((size_t) nrhs * 4); int64_t *ho = (int64_t *) malloc((size_t) nrhs * 8);
-        if (!rc && (!hl || !ho)) rc = SLIP_HIP_OUT_OF_MEMORY;
-        if (!rc) {
-            for (int32_t c = 0; c < nrhs; c++) { hl[c] = pr.len; ho[c] = pr.off; }
-            dmaxdig = pr.len < 0 ? -pr.len : pr.len;
-            A_(dev_alloc(&ddlen, nrhs)); A_(dev_alloc(&ddoff, nrhs));
-            UP_(ddlen, hl, (size_t) nrhs * 4); UP_(ddoff, ho, (size_t) nrhs * 8);
-        }
-        free(hl); free(ho);
-    }
+    A_(det_records(f, nrhs, &ddlen, &ddoff, &dmaxdig));
     if (!rc && !transpose) {
         f->check_ms = 0;
         rc = check_core(n, nrhs, f->chk_rp, f->chk_re, f->chk_rx, f->dAlen, f->dAoff, f->dAlimbs, f->amaxdig,
@@ -3803,9 +3952,9 @@ extern "C" int slip_hip_check_solution(int32_t n, const int64_t *Ap, const int32
     if (!rc) rc = slab_prepare(nrhs, dlen, dlimbs, d_limbs, &ds);
     for (int32_t c = 0; c < nrhs && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;     /* x_c / 0 is no solution */
     SlipHostA ha; memset(&ha, 0, sizeof ha);
-    if (!rc) rc = prepare_A(n, Ap, Ai, Alen, Alimbs, &ha);
+    if (!rc) rc = prepare_A(n, n, Ap, Ai, Alen, Alimbs, &ha);
     int64_t *rp = NULL, *re = NULL; int32_t *rx = NULL;
-    if (!rc) rc = build_row_view(n, ha.Ap, ha.Ai, NULL, &rp, &re, &rx);
+    if (!rc) rc = build_row_view(n, n, ha.Ap, ha.Ai, NULL, &rp, &re, &rx);
     int64_t *drp = NULL, *dre = NULL, *daoff = NULL, *ddoff = NULL; int32_t *drx = NULL, *dalen = NULL, *ddlen = NULL; uint64_t *dal = NULL, *ddl = NULL;
     const int64_t nz = ha.nnz;
     A_(dev_alloc(&drp, (int64_t) n + 1)); A_(dev_alloc(&dre, nz)); A_(dev_alloc(&drx, nz));
@@ -3822,6 +3971,257 @@ extern "C" int slip_hip_check_solution(int32_t n, const int64_t *Ap, const int32
     slab_free(&bs); slab_free(&xs); slab_free(&ds);
     return rc;
 }
+
+/* ---- exact sparse products r_c = op(A) x_c - d_c b_c returned (no counterpart in the reference; kernel: slip_product_kernel,
+ * DESIGN 3i) ---- */
+
+/* device ms of this thread's last product by pass: the widths, the offset scans, the products, the packing */
+static thread_local double slip_product_passes_last[4];
+
+/* a view of a resident matrix: nout output rows, nx entries in a vector of x */
+struct SlipProductView {
+    int32_t nout, nx; const int64_t *rp, *re; const int32_t *rx;
+    const int32_t *alen; const int64_t *aoff; const uint64_t *alimbs; int32_t amaxdig;
+};
+
+/* the limbs one group of vectors may stage (fit_scratch's 256 MiB; SLIP_HIP_PRODUCT_STAGE_KB overrides it: tests of the grouping) */
+static int64_t product_stage_limbs(void)
+{
+    const char *e = getenv("SLIP_HIP_PRODUCT_STAGE_KB");
+    const long long kb = e ? atoll(e) : 0;
+    return kb > 0 ? (int64_t) kb * 128 : ((int64_t) 256 << 20) / 8;
+}
+
+/* one product on the device: x (and b, with bs != NULL) prepared on the host; d_c as device records into ddlimbs (with b).
+ * The result is one compact malloc'ed slab of V.nout * nvec entries, signed limb counts. */
+static int product_core(const SlipProductView &V, int32_t nvec, const SlipSlab &xs, const uint64_t *xlimbs,
+                        const SlipSlab *bs, const uint64_t *blimbs,
+                        const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
+                        int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, hipStream_t stream, double *ms_out)
+{
+    const int64_t nout = V.nout, ne = nout * nvec, nxe = (int64_t) V.nx * nvec;
+    /* every width is at most wtop (slip_product_kernel), wcap in whole limbs: the staging of a group and the memory path's scratch
+     * are sized from it */
+    const int64_t wtop = (bs && dmaxdig + bs->maxdig > V.amaxdig + xs.maxdig ? dmaxdig + bs->maxdig : V.amaxdig + xs.maxdig) + 1;
+    const int64_t wcap = (wtop + 1) & ~(int64_t) 1;
+    if (wcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
+    int64_t group = product_stage_limbs() / (nout * (wcap / 2));                  /* vectors staged together */
+    if (group < 1) group = 1;
+    if (group > nvec) group = nvec;
+    const int64_t blocks = wtop > 256 ? fit_scratch(wave_blocks(ne), wcap) : wave_blocks(ne), sblocks = offscan_blocks(nout * group);
+    int32_t *dxl = NULL, *dbl = NULL, *dw = NULL, *drl = NULL; int64_t *dxo = NULL, *dbo = NULL, *dso = NULL; uint64_t *dxv = NULL, *dbv = NULL;
+    dig_t *dscr = NULL; unsigned long long *bsum = NULL;
+    int32_t *rl = (int32_t *) malloc((size_t) ne * 4); uint64_t *rv = NULL; int64_t rn = 0;
+    double ms[4] = {0, 0, 0, 0};
+    int rc = !rl ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    A_(dev_alloc(&dxl, nxe)); A_(dev_alloc(&dxo, nxe)); A_(dev_alloc(&dxv, xs.total));
+    if (bs) { A_(dev_alloc(&dbl, ne)); A_(dev_alloc(&dbo, ne)); A_(dev_alloc(&dbv, bs->total)); }
+    A_(dev_alloc(&dw, ne)); A_(dev_alloc(&dso, ne)); A_(dev_alloc(&drl, ne)); A_(dev_alloc(&bsum, sblocks));
+    if (wtop > 256) A_(dev_alloc(&dscr, blocks * SERVICE_WAVES * wcap));
+    UP_(dxl, xs.dig, (size_t) nxe * 4); UP_(dxo, xs.off, (size_t) nxe * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
+    if (bs) { UP_(dbl, bs->dig, (size_t) ne * 4); UP_(dbo, bs->off, (size_t) ne * 8); UP_(dbv, blimbs, (size_t) bs->total * 8); }
+    SlipProductArgs A; memset(&A, 0, sizeof A);
+    A.nout = V.nout; A.nx = V.nx; A.rp = V.rp; A.re = V.re; A.rx = V.rx; A.alen = V.alen; A.aoff = V.aoff; A.alimbs = V.alimbs;
+    A.xlimbs = dxv; A.blimbs = dbv; A.dlimbs = ddlimbs; A.scratch = dscr; A.wcap = (int32_t) wcap;
+    /* the vectors c0 .. c0 + nv of the operands */
+    auto slice = [&](int64_t c0, int64_t nv, int phase) {
+        A.nvec = (int32_t) nv; A.phase = phase;
+        A.xlen = dxl + c0 * V.nx; A.xoff = dxo + c0 * V.nx;
+        A.blen = bs ? dbl + c0 * nout : NULL; A.boff = bs ? dbo + c0 * nout : NULL;
+        A.dlen = bs ? ddlen + c0 : NULL; A.doff = bs ? ddoff + c0 : NULL;
+        A.wlen = dw + c0 * nout; A.soff = dso + c0 * nout; A.rlen = drl + c0 * nout;
+    };
+    if (!rc) {                                             /* pass 1: the widths of all items */
+        SlipTimed timed;
+        slice(0, nvec, 0);
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(product, wave_blocks(ne), stream, A));
+        A_(timed.end(stream, &ms[0]));
+    }
+    for (int64_t c0 = 0; c0 < nvec && !rc; c0 += group) {
+        const int64_t nv = c0 + group <= nvec ? group : nvec - c0, cnt = nout * nv;
+        uint64_t *dstage = NULL; int32_t *gl = NULL; uint64_t *gv = NULL; int64_t gn = 0, total = 0;
+        double t = 0;
+        slice(c0, nv, 1);
+        {                                                  /* pass 2: the staging offsets from the widths */
+            SlipTimed timed;
+            A_(timed.begin(stream));
+            A_(offscan_run(cnt, A.wlen, dso + c0 * nout, bsum, sblocks, stream));
+            A_(timed.end(stream, &t));
+            ms[1] += t;
+        }
+        A_(offscan_total(bsum, sblocks, &total, stream));
+        if (!rc && total > nout * nv * (wcap / 2)) rc = SLIP_HIP_DEVICE_ERROR;     /* (the widths' bound: the host's own figure) */
+        A_(dev_alloc(&dstage, total));
+        if (!rc) {                                         /* pass 3: the products into the staging slab */
+            SlipTimed timed;
+            A.stage = dstage;
+            A_(timed.begin(stream));
+            A_(SERVICE_LAUNCH(product, blocks, stream, A));
+            A_(timed.end(stream, &t));
+            ms[2] += t;
+        }
+        A_(pack_download(cnt, A.rlen, A.soff, dstage, 0, &gl, &gv, &gn, stream, &t));
+        if (!rc) {
+            ms[3] += t;
+            uint64_t *grown = (uint64_t *) realloc(rv, (size_t)(rn + gn > 0 ? rn + gn : 1) * 8);
+            if (!grown) rc = SLIP_HIP_OUT_OF_MEMORY;
+            else {
+                rv = grown;
+                memcpy(rl + c0 * nout, gl, (size_t) cnt * 4);
+                if (gn > 0) memcpy(rv + rn, gv, (size_t) gn * 8);
+                rn += gn;
+            }
+        }
+        free(gl); free(gv);
+        dev_free(dstage);
+    }
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dbl); dev_free(dbo); dev_free(dbv);
+    dev_free(dw); dev_free(dso); dev_free(drl); dev_free(bsum); dev_free(dscr);
+    if (rc) { free(rl); free(rv); return rc; }
+    memcpy(slip_product_passes_last, ms, sizeof ms);
+    if (ms_out) *ms_out = ms[0] + ms[1] + ms[2] + ms[3];
+    *rlen_out = rl; *rlimbs_out = rv; *rnl_out = rn;
+    return SLIP_HIP_OK;
+}
+
+/* the operands of one product checked and brought to the device, then product_core.  f != NULL: a handle whose det stands in
+ * for a missing d (the caller has seen to it that the factorisation is complete). */
+static int product_entry(const SlipProductView &V, slip_hip_factor *f, int32_t nvec,
+                         const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                         const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                         const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                         int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, hipStream_t stream, double *ms_out)
+{
+    SlipSlab xs, bs, ds;
+    memset(&bs, 0, sizeof bs); memset(&ds, 0, sizeof ds);
+    int rc = slab_prepare((int64_t) V.nx * nvec, xlen, xlimbs, x_limbs, &xs);
+    if (!rc && blen) rc = slab_prepare((int64_t) V.nout * nvec, blen, blimbs, b_limbs, &bs);
+    if (!rc && dlen) rc = slab_prepare(nvec, dlen, dlimbs, d_limbs, &ds);
+    for (int32_t c = 0; c < nvec && !rc && dlen; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    int32_t *ddlen = NULL; int64_t *ddoff = NULL; uint64_t *ddl = NULL; const uint64_t *ddlimbs = NULL; int32_t dmaxdig = 0;
+    if (blen && dlen) {
+        A_(dev_alloc(&ddlen, nvec)); A_(dev_alloc(&ddoff, nvec)); A_(dev_alloc(&ddl, ds.total));
+        UP_(ddlen, ds.dig, (size_t) nvec * 4); UP_(ddoff, ds.off, (size_t) nvec * 8); UP_(ddl, dlimbs, (size_t) ds.total * 8);
+        ddlimbs = ddl; dmaxdig = ds.maxdig;
+    } else if (blen) {
+        A_(det_records(f, nvec, &ddlen, &ddoff, &dmaxdig));
+        ddlimbs = f->P.Llimbs;
+    }
+    A_(product_core(V, nvec, xs, xlimbs, blen ? &bs : NULL, blimbs, ddlen, ddoff, ddlimbs, dmaxdig,
+                    rlen_out, rlimbs_out, rnl_out, stream, ms_out));
+    dev_free(ddlen); dev_free(ddoff); dev_free(ddl);
+    slab_free(&xs); slab_free(&bs); slab_free(&ds);
+    return rc;
+}
+
+/* what every product entry refuses before it looks at its object */
+static int product_args_bad(int32_t nvec, const int32_t *xlen, const uint64_t *xlimbs, const int32_t *blen, const uint64_t *blimbs,
+                            const int32_t *dlen, const uint64_t *dlimbs, int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out)
+{
+    return nvec < 1 || !xlen || !xlimbs || !rlen_out || !rlimbs_out || !rnl_out || (blen && !blimbs) || (dlen && !dlimbs) || (dlen && !blen);
+}
+
+extern "C" int slip_hip_factor_multiply(slip_hip_factor *f, int32_t transpose, int32_t nvec,
+                                        const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                        const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                                        const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                        int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream_v)
+{
+    if (!f || f->factors_only || product_args_bad(nvec, xlen, xlimbs, blen, blimbs, dlen, dlimbs, rlen_out, rlimbs_out, rnl_out))
+        return SLIP_HIP_INCORRECT_INPUT;
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
+    if (f->last_status == SLIP_HIP_DEVICE_ERROR) return SLIP_HIP_INCORRECT_INPUT;
+    if (blen && !dlen && f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;         /* d = det needs the complete factorisation */
+    int rc = 0;
+    if (transpose && !f->chkt_rp) rc = build_col_view(f);
+    if (!transpose && !f->chk_rp) rc = build_pos_row_view(f);
+    SlipProductView V;
+    V.nout = V.nx = f->n; V.alen = f->dAlen; V.aoff = f->dAoff; V.alimbs = f->dAlimbs; V.amaxdig = f->amaxdig;
+    V.rp = transpose ? f->chkt_rp : f->chk_rp; V.re = transpose ? f->chkt_re : f->chk_re; V.rx = transpose ? f->chkt_rx : f->chk_rx;
+    f->multiply_ms = 0;
+    A_(product_entry(V, f, nvec, xlen, xlimbs, x_limbs, blen, blimbs, b_limbs, dlen, dlimbs, d_limbs,
+                     rlen_out, rlimbs_out, rnl_out, (hipStream_t) stream_v, &f->multiply_ms));
+    return rc;
+}
+
+extern "C" double slip_hip_factor_multiply_ms(const slip_hip_factor *f) { return f ? f->multiply_ms : 0.0; }
+
+extern "C" int slip_hip_multiply_passes(double out[4])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_product_passes_last, sizeof slip_product_passes_last);
+    return SLIP_HIP_OK;
+}
+
+/* a resident m x ncols integer matrix with both of its views, no factorisation */
+struct slip_hip_matrix {
+    int32_t m, ncols, amaxdig;
+    int32_t *dAlen; int64_t *dAoff; uint64_t *dAlimbs;
+    int64_t *row_rp, *row_re; int32_t *row_rx;            /* M x:   row i, its terms' entries, their columns */
+    int64_t *col_rp, *col_re; int32_t *col_rx;            /* M^T x: column j, its entries, their rows        */
+    double multiply_ms;
+};
+
+extern "C" void slip_hip_matrix_destroy(slip_hip_matrix *M)
+{
+    if (!M) return;
+    dev_free(M->dAlen); dev_free(M->dAoff); dev_free(M->dAlimbs);
+    dev_free(M->row_rp); dev_free(M->row_re); dev_free(M->row_rx);
+    dev_free(M->col_rp); dev_free(M->col_re); dev_free(M->col_rx);
+    free(M);
+}
+
+extern "C" int slip_hip_matrix_create(slip_hip_matrix **out, int32_t m, int32_t ncols,
+                                      const int64_t *Ap, const int32_t *Ai, const int32_t *Alen, const uint64_t *Alimbs)
+{
+    if (!out || m <= 0 || ncols <= 0 || !Ap || !Ai || !Alen || !Alimbs) return SLIP_HIP_INCORRECT_INPUT;
+    *out = NULL;
+    TRY_(need_device());
+    SlipHostA ha;
+    /* (its bound on m and ncols is the bound on the terms of an output row of either view: a repeated row is kept once) */
+    TRY_(prepare_A(m, ncols, Ap, Ai, Alen, Alimbs, &ha));
+    const int64_t nz = ha.nnz;
+    int64_t *rp = NULL, *re = NULL, *ce = (int64_t *) malloc((size_t) nz * 8); int32_t *rx = NULL;
+    int rc = !ce ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    A_(build_row_view(m, ncols, ha.Ap, ha.Ai, NULL, &rp, &re, &rx));
+    if (!rc) for (int64_t e = 0; e < nz; e++) ce[e] = e;
+    slip_hip_matrix *M = rc ? NULL : (slip_hip_matrix *) calloc(1, sizeof(slip_hip_matrix));
+    if (!rc && !M) rc = SLIP_HIP_OUT_OF_MEMORY;
+    if (!rc) {
+        M->m = m; M->ncols = ncols; M->amaxdig = ha.maxdig;
+        A_(dev_alloc(&M->dAlen, nz)); A_(dev_alloc(&M->dAoff, nz)); A_(dev_alloc(&M->dAlimbs, ha.nl));
+        A_(dev_alloc(&M->row_rp, (int64_t) m + 1)); A_(dev_alloc(&M->row_re, nz)); A_(dev_alloc(&M->row_rx, nz));
+        A_(dev_alloc(&M->col_rp, (int64_t) ncols + 1)); A_(dev_alloc(&M->col_re, nz)); A_(dev_alloc(&M->col_rx, nz));
+        UP_(M->dAlen, ha.Alen, (size_t) nz * 4); UP_(M->dAoff, ha.Aoff, (size_t) nz * 8); UP_(M->dAlimbs, ha.Alimbs, (size_t) ha.nl * 8);
+        UP_(M->row_rp, rp, ((size_t) m + 1) * 8); UP_(M->row_re, re, (size_t) nz * 8); UP_(M->row_rx, rx, (size_t) nz * 4);
+        UP_(M->col_rp, ha.Ap, ((size_t) ncols + 1) * 8); UP_(M->col_re, ce, (size_t) nz * 8); UP_(M->col_rx, ha.Ai, (size_t) nz * 4);
+    }
+    free(rp); free(re); free(rx); free(ce);
+    host_a_free(&ha);
+    if (rc) { slip_hip_matrix_destroy(M); return rc; }
+    *out = M;
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_matrix_multiply(slip_hip_matrix *M, int32_t transpose, int32_t nvec,
+                                        const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                        const int32_t *blen, const uint64_t *blimbs, int64_t b_limbs,
+                                        const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                        int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream_v)
+{
+    if (!M || product_args_bad(nvec, xlen, xlimbs, blen, blimbs, dlen, dlimbs, rlen_out, rlimbs_out, rnl_out) || (blen && !dlen))
+        return SLIP_HIP_INCORRECT_INPUT;
+    SlipProductView V;
+    V.nout = transpose ? M->ncols : M->m; V.nx = transpose ? M->m : M->ncols;
+    V.alen = M->dAlen; V.aoff = M->dAoff; V.alimbs = M->dAlimbs; V.amaxdig = M->amaxdig;
+    V.rp = transpose ? M->col_rp : M->row_rp; V.re = transpose ? M->col_re : M->row_re; V.rx = transpose ? M->col_rx : M->row_rx;
+    M->multiply_ms = 0;
+    return product_entry(V, NULL, nvec, xlen, xlimbs, x_limbs, blen, blimbs, b_limbs, dlen, dlimbs, d_limbs,
+                         rlen_out, rlimbs_out, rnl_out, (hipStream_t) stream_v, &M->multiply_ms);
+}
+
+extern "C" double slip_hip_matrix_multiply_ms(const slip_hip_matrix *M) { return M ? M->multiply_ms : 0.0; }
 
 /* ---- subtree farm: multiply the committed factors by per-column scales ---- */
 static void rescale_drop(slip_hip_factor *f)
