@@ -27,6 +27,8 @@
  *   slip_hip_factor_replace_column            a simplex code's basis change are what other codes offer between two solves)
  *   slip_hip_factor_multiply,            <->  no counterpart (SLIP_check_solution forms A x - b and keeps only the verdict):
  *   slip_hip_matrix_*                         the exact sparse products of a simplex code's pricing and of a residual
+ *   slip_hip_ratio_test,                 <->  no counterpart: the exact ratio test of a simplex step (the leaving row, the
+ *   slip_hip_factor_ratio_test                most negative reduced cost, the dual ratio test); only the choice comes back
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
  *
  * The GMP-typed drop-in  SLIP_LU_factorize(L,U,A,S,rhos,pinv,option)  built on
@@ -432,6 +434,49 @@ void slip_hip_matrix_destroy(slip_hip_matrix *M);
  * packing (the staging slab of a product is bounded: SLIP_HIP_PRODUCT_STAGE_KB kilobytes, environment, default 262144; vectors
  * beyond it are taken in further groups) */
 int slip_hip_multiply_passes(double out[4]);
+
+/* Exact ratio test on the device: per problem c, over n pairs of signed big integers (x_i, a_i), the entry with the smallest
+ * ratio, compared exactly.  Entry i is ELIGIBLE iff sense * a_i > 0 (a zero a_i never is); its ratio is r_i = x_i / (sense *
+ * a_i), a positive denominator under a numerator of any sign.  best[c] is the eligible i with the smallest r_i, among exact ties
+ * the smallest (key[i], i) (key == NULL: the smallest i), or -1 when nothing is eligible (the unbounded ray); nties[c] counts the
+ * eligible entries whose ratio equals the minimum exactly, the winner included (0 with best = -1); neligible[c] the eligible
+ * entries.  sense is +1 or -1; key (n values, optional) is shared by all problems.  Only these 3 * nprob integers come back.
+ *
+ * slip_hip_ratio_test: x and a are limb slabs of nprob * n entries each (entry c*n + i), with the limbs each array holds as
+ * slip_hip_solution_to_double takes its x; high zero limbs are allowed.  alen == alimbs == NULL: no denominators -- every
+ * entry is eligible and r_i = sense * x_i, the argmin (sense +1) or argmax (-1) of a signed integer vector (Dantzig pricing on
+ * the result of slip_hip_factor_multiply).
+ *
+ * slip_hip_factor_ratio_test: the fused form.  b holds 2 * nprob right-hand sides as slip_hip_factor_solve (transpose 0) or
+ * slip_hip_factor_solve_transpose (1) takes them: column 2c is the x side of problem c, column 2c + 1 its a side.  The
+ * substitution runs, its numerators stay on the device and the selection runs on them.  Both sides are numerators over the
+ * same det = rho[n-1]: det cancels in the ratio but not in the eligibility -- entry i is eligible iff sense * sign(det) *
+ * anum_i > 0 (the true alpha_i = anum_i / det), and r_i = xnum_i / (sense * anum_i).  The indices reported, and the indices
+ * into key, are those of the matching solve's output: pivot POSITION p for transpose 0 (what slip_hip_factor_replace_column
+ * and _rewind work with through q[p]), original ROW id for transpose 1.  wlen_out / wlimbs_out / wnl_out (all three or
+ * none): the winners' two numerators, xnum_best and anum_best of problem c as entries 2c and 2c + 1 of one malloc'ed slab
+ * (slip_hip_free), both of length 0 when best = -1 -- the step theta = xnum_best / anum_best without a second solve.  Needs the
+ * complete factorisation; transpose 0 is refused on a handle from slip_hip_factor_from_factors (it holds no q), transpose 1
+ * works there.
+ *
+ * SLIP_HIP_INCORRECT_INPUT: n <= 0, nprob < 1, sense not +1 or -1, exactly one of alen / alimbs NULL, a limb array shorter than
+ * its counts say, a NULL result array, an incomplete factorisation; a broken handle answers SLIP_HIP_DEVICE_ERROR.  Nothing is
+ * written to the results then.
+ *
+ * _ms: device time of the selection kernels of the handle's last call (the substitution before them is in
+ * slip_hip_factor_solve_ms / _solve_transpose_ms).  _paths (of the handle's last call; of this thread's last handle-less
+ * call): out[0] eligible entries, out[1] entries the bound pass left to the exact pass, out[2] exact comparisons that formed
+ * products, out[3] of those, the comparisons on the memory path (products above 256 digits). */
+int slip_hip_ratio_test(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                        const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,             /* optional */
+                        int32_t sense, const int32_t *key,
+                        int32_t *best, int32_t *nties, int32_t *neligible, void *stream);
+int slip_hip_ratio_test_paths(int64_t out[4]);
+int slip_hip_factor_ratio_test(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                               int32_t sense, const int32_t *key, int32_t *best, int32_t *nties, int32_t *neligible,
+                               int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+double slip_hip_factor_ratio_test_ms(const slip_hip_factor *f);
+int slip_hip_factor_ratio_test_paths(const slip_hip_factor *f, int64_t out[4]);
 
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize

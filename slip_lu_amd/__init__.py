@@ -6,5 +6,5 @@ ctypes layer the tests and bench.py use.
 """
 from . import api  # noqa: F401
 from .api import (Factorization, SlipError, SparseMatrix, check_solution, factorize, ints_to_slab, matgen,  # noqa: F401
-                  multiply_passes, read_triplet, solution_to_double, solution_to_mpfr, solution_to_mpfr_paths, solution_to_rational,
-                  solution_to_rational_paths, write_triplet)
+                  multiply_passes, ratio_test, ratio_test_paths, read_triplet, solution_to_double, solution_to_mpfr,
+                  solution_to_mpfr_paths, solution_to_rational, solution_to_rational_paths, write_triplet)

@@ -46,7 +46,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_to_mpfr_paths", "slip_hip_solution_to_mpfr_paths",
            "slip_hip_factor_rewind", "slip_hip_factor_replace_column", "slip_hip_factor_a_storage",
            "slip_hip_factor_multiply", "slip_hip_factor_multiply_ms", "slip_hip_matrix_create", "slip_hip_matrix_multiply",
-           "slip_hip_matrix_multiply_ms", "slip_hip_matrix_destroy", "slip_hip_multiply_passes")
+           "slip_hip_matrix_multiply_ms", "slip_hip_matrix_destroy", "slip_hip_multiply_passes",
+           "slip_hip_ratio_test", "slip_hip_ratio_test_paths", "slip_hip_factor_ratio_test", "slip_hip_factor_ratio_test_ms",
+           "slip_hip_factor_ratio_test_paths")
 
 _libs = {}
 
@@ -159,5 +161,16 @@ def load(path=None):
     lib.slip_hip_matrix_destroy.restype = None
     lib.slip_hip_multiply_passes.argtypes = [vp]
     lib.slip_hip_multiply_passes.restype = C.c_int
+    lib.slip_hip_ratio_test.argtypes = [C.c_int32, C.c_int32, vp, vp, i64, vp, vp, i64, C.c_int32, vp, vp, vp, vp, vp]
+    lib.slip_hip_ratio_test.restype = C.c_int
+    lib.slip_hip_ratio_test_paths.argtypes = [vp]
+    lib.slip_hip_ratio_test_paths.restype = C.c_int
+    lib.slip_hip_factor_ratio_test.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp,
+                                               C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
+    lib.slip_hip_factor_ratio_test.restype = C.c_int
+    lib.slip_hip_factor_ratio_test_ms.argtypes = [vp]
+    lib.slip_hip_factor_ratio_test_ms.restype = C.c_double
+    lib.slip_hip_factor_ratio_test_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_ratio_test_paths.restype = C.c_int
     _libs[path] = lib
     return lib

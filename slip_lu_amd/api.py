@@ -231,6 +231,49 @@ def multiply_passes(lib_path=None):
     return [float(v) for v in out]
 
 
+def _ratio_key(n, key):
+    """the optional tie-break keys of a ratio test as an int32 array of n entries (None stays None)"""
+    if key is None:
+        return None
+    key = np.ascontiguousarray(key, dtype=np.int32)
+    if key.size != n:
+        raise ValueError("ratio_test: key must hold n entries")
+    return key
+
+
+def ratio_test(n, xlen, xlimbs, alen=None, alimbs=None, nprob=1, sense=1, key=None, lib_path=None):
+    """The exact ratio test on the device (slip_hip_ratio_test): per problem the eligible entry (sense * a_i > 0) with the
+    smallest x_i / (sense * a_i), among exact ties the smallest (key[i], i).  x and a as limb slabs of nprob * n entries;
+    without a every entry is eligible and the ratio is sense * x_i (argmin / argmax of an integer vector).  Returns
+    (best, nties, neligible), int32[nprob] each: best -1 and nties 0 when nothing is eligible."""
+    lib = _lib.load(lib_path)
+    n, nprob = int(n), int(nprob)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    if n >= 1 and nprob >= 1 and xlen.size != n * nprob:
+        raise ValueError("ratio_test: xlen must hold n*nprob entries")
+    args = [xlen.ctypes.data, xlimbs.ctypes.data, xcap]
+    if alen is None and alimbs is None:
+        args += [None, None, 0]
+    else:
+        alen, alimbs, acap = _limb_arrays(alen, alimbs)
+        if n >= 1 and nprob >= 1 and alen.size != n * nprob:
+            raise ValueError("ratio_test: alen must hold n*nprob entries")
+        args += [alen.ctypes.data, alimbs.ctypes.data, acap]
+    key = _ratio_key(n, key) if n >= 1 else None
+    best, nties, nelig = (np.zeros(max(nprob, 1), np.int32) for _ in range(3))
+    rc = lib.slip_hip_ratio_test(n, nprob, *args, int(sense), None if key is None else key.ctypes.data,
+                                 best.ctypes.data, nties.ctypes.data, nelig.ctypes.data, None)
+    if rc:
+        raise SlipError(rc, "slip_hip_ratio_test")
+    return best[:nprob], nties[:nprob], nelig[:nprob]
+
+
+def ratio_test_paths(lib_path=None):
+    """this thread's last ratio_test: [eligible entries, entries the bound pass left to the exact pass, exact comparisons that
+    formed products, of those the comparisons on the memory path]"""
+    return _paths(_lib.load(lib_path).slip_hip_ratio_test_paths)
+
+
 class SparseMatrix:
     """An m x ncols integer matrix resident on one GPU without a factorisation (handle of slip_hip_matrix_*): the CSC as
     Factorization() takes it, a repeated row keeping its LAST value."""
@@ -615,6 +658,37 @@ class Factorization:
     def multiply_ms(self):
         """device ms of the kernels of the last multiply"""
         return self.lib.slip_hip_factor_multiply_ms(self.h)
+
+    def ratio_test(self, blen, blimbs, nprob=1, transpose=False, sense=1, key=None, winners=False, stream=None):
+        """Solve and select on the device (slip_hip_factor_ratio_test): b holds 2 * nprob right-hand sides as `solve` (or with
+        transpose=True `solve_transpose`) takes them, column 2c the x side and column 2c + 1 the a side of problem c.  Per
+        problem the entry with the smallest xnum_i / (sense * anum_i) among those with sense * sign(det) * anum_i > 0, exact
+        ties broken by the smallest (key[i], i); indices are those of the matching solve's output (pivot position, or
+        original row id when transposed).  Returns (best, nties, neligible), int32[nprob] each; with winners=True also
+        (wlen, wlimbs), the slab of the winners' numerators: xnum_best and anum_best of problem c as entries 2c and 2c + 1,
+        empty where best is -1.  No numerator of the solve is downloaded otherwise."""
+        nprob = int(nprob)
+        blen, blimbs, _ = _rhs(self.n, blen, blimbs, 2 * nprob if nprob >= 1 else nprob)
+        key = _ratio_key(self.n, key)
+        best, nties, nelig = (np.zeros(max(nprob, 1), np.int32) for _ in range(3))
+        pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+        outs = (C.byref(pl), C.byref(px), C.byref(nl)) if winners else (None, None, None)
+        rc = self.lib.slip_hip_factor_ratio_test(self.h, int(bool(transpose)), nprob, blen.ctypes.data, blimbs.ctypes.data,
+                                                 int(sense), None if key is None else key.ctypes.data,
+                                                 best.ctypes.data, nties.ctypes.data, nelig.ctypes.data, *outs, C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_ratio_test")
+        res = (best[:nprob], nties[:nprob], nelig[:nprob])
+        return res + _take_slab(self.lib, pl, px, nl, 2 * nprob) if winners else res
+
+    def ratio_test_ms(self):
+        """device ms of the selection kernels of the last ratio_test (the substitution: solve_ms / solve_transpose_ms)"""
+        return self.lib.slip_hip_factor_ratio_test_ms(self.h)
+
+    def ratio_test_paths(self):
+        """the last ratio_test: [eligible entries, entries the bound pass left to the exact pass, exact comparisons that formed
+        products, of those the comparisons on the memory path]"""
+        return _paths(self.lib.slip_hip_factor_ratio_test_paths, self.h)
 
     def solve_transpose_ms(self):
         """(device ms of the last transposed solve's substitution kernels, ms of that call's view build: 0 when it was reused)"""

@@ -1244,6 +1244,231 @@ static void slip_pack_body(SlipPackArgs A)
     }
 }
 
+/* Exact ratio test (slip_hip_ratio_test, slip_hip_factor_ratio_test): per problem c the eligible entry i with the
+ * smallest ratio  r_i = x_i / |a_i|  (negated when xflip is set), ties broken by the smallest (key[idx], idx), idx = oidx[i]
+ * being the index that is reported; the number of eligible entries that tie with it; the number of eligible entries.  Entry
+ * i of problem c is entry c * pstride + i of the x records and of the a records.  An entry is eligible when sign(a_i) ==
+ * asense; with alen == NULL every entry is eligible and a_i = 1.  The host turns sense and the sign of det into asense and
+ * xflip.  Nothing depends on the launch geometry: (r_i, key, idx) is a total order and the tie count is a count.
+ *
+ * phase 0, the bound pass, one lane per entry (a wave's 64 entries are of one problem): from the signs, the bit lengths and
+ *   the leading 64 bits of both parts (the lane pass of slip_todouble_kernel: T = |r| * 2^(k - bn + bd), floor(T) is one of
+ *   Q-2 .. Q+2) an enclosure (Qs - 1) * 2^e < |r| < (Qs + 2) * 2^e, Qs = Q >> 2, e = bn - bd - k + 2, is packed into two
+ *   monotone 64-bit keys (slip_ratio_key: a biased exponent above 22 bits of mantissa, truncated for the lower end, truncated
+ *   plus one for the upper end; negated and swapped for a negative ratio; x_i = 0 is the point 0).  The lower key is kept per
+ *   entry (INT64_MAX: not eligible); the minimum of the upper keys goes to minhi[c], one atomic per wave.
+ * phase 1, the filter: an eligible entry whose lower key is at most minhi[c] is appended to the problem's candidates (an
+ *   atomic cursor; their order does not matter).  The winner and all that tie with it pass: no enclosure of theirs lies above
+ *   another entry's.
+ * phase 2, the exact fold, one wave per chunk of SLIP_RATIO_CHUNK candidates: a running best by slip_ratio_cmp.
+ * phase 3, one wave per problem: the chunk winners folded by the same comparison, the tie counts of equal winners added.
+ *
+ * slip_ratio_cmp settles sign(r_i - r_j) = sign(x_i |a_j| - x_j |a_i|) without a product when the numerators differ in sign,
+ * both are zero, or bits(x_i) + bits(a_j) and bits(x_j) + bits(a_i) differ by two or more (a product of p-bit and q-bit factors
+ * has p + q - 1 or p + q bits); without denominators it compares the numerators themselves.  Otherwise both products are
+ * formed, in registers up to 256 digits, above that with wb_mul_lo into this wave's scratch (2 * wcap digits).
+ * paths: [0] eligible entries, [1] candidates, [2] comparisons that formed products, [3] of those on the memory path. */
+#define SLIP_RATIO_CHUNK 64
+struct SlipRatioArgs {
+    int32_t n, nprob, phase, asense, xflip;
+    int64_t pstride;
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* x: signed digit counts, limb offsets   */
+    const int32_t *alen; const int64_t *aoff; const uint64_t *alimbs;              /* a likewise, or alen NULL               */
+    const int32_t *oidx, *key;                                                     /* reported index of entry i; key by it   */
+    int64_t *lokey, *minhi;                                                        /* per entry c*n + i; per problem         */
+    int32_t *ncand, *cand;                                                         /* per problem; candidates at c*n + t     */
+    int32_t nchunk; int32_t *cwpos, *cwties;                                       /* chunk winners at c*nchunk + k          */
+    int32_t *best, *nties, *nelig;                                                 /* the result, per problem                */
+    int32_t *wlen; int64_t *woff;                                                  /* the winner's records at 2c, 2c+1, or NULL */
+    int32_t *maxdig;                                                               /* [0], [1]: widest eligible x, a         */
+    dig_t *scratch; int32_t wcap; int32_t *err;                                    /* memory path; a product wider than wcap */
+    unsigned long long *paths;
+};
+
+/* the monotone key of q * 2^e, 0 < q < 2^63: the exponent of its leading bit, biased, above the 22 bits that follow that bit */
+SLIP_DEV int64_t slip_ratio_key(uint64_t q, int64_t e)
+{
+    const int z = slip_clz64(q);
+    const uint64_t norm = q << z;
+    return ((e + 63 - z + ((int64_t) 1 << 40)) << 22) | (int64_t)((norm >> 41) & 0x3FFFFFu);
+}
+
+/* one side of a comparison: the trimmed numerator and denominator of entry i of problem c */
+struct SlipRatioEnt { const dig_t *x, *a; int lx, la, sx; };
+SLIP_DEV SlipRatioEnt slip_ratio_ent(const SlipRatioArgs &A, int c, int i)
+{
+    SlipRatioEnt E;
+    const int64_t e = (int64_t) c * A.pstride + i;
+    const int32_t sx = A.xlen[e];
+    E.x = (const dig_t *)(A.xlimbs + A.xoff[e]);
+    E.lx = slip_trim_digits(E.x, slip_abs(sx));
+    E.sx = E.lx == 0 ? 0 : (((sx < 0) != (A.xflip != 0)) ? -1 : 1);
+    E.a = (const dig_t *) 0; E.la = 0;
+    if (A.alen) { E.a = (const dig_t *)(A.alimbs + A.aoff[e]); E.la = slip_trim_digits(E.a, slip_abs(A.alen[e])); }
+    return E;
+}
+
+/* sign(P - Q) of the two products in registers, all of them at most 64*D digits */
+template <int D> SLIP_DEV int slip_ratio_cmp_reg(const dig_t *x1, int lx1, const dig_t *a2, int la2, const dig_t *x2, int lx2, const dig_t *a1, int la1)
+{
+    const WR<D> X1 = wr_load<D>(x1, lx1), A2 = wr_load<D>(a2, la2), X2 = wr_load<D>(x2, lx2), A1 = wr_load<D>(a1, la1);
+    const WR<D> P = lx1 <= la2 ? wr_mul<D>(X1, lx1, A2) : wr_mul<D>(A2, la2, X1);
+    const WR<D> Q = lx2 <= la1 ? wr_mul<D>(X2, lx2, A1) : wr_mul<D>(A1, la1, X2);
+#pragma unroll
+    for (int q = D - 1; q >= 0; q--) {
+        const uint64_t df = slip_ballot(P.d[q] != Q.d[q]);
+        if (df) {
+            const int t = 63 - slip_clz64(df);
+            return slip_readlane(P.d[q], t) > slip_readlane(Q.d[q], t) ? 1 : -1;
+        }
+    }
+    return 0;
+}
+
+/* sign(r_i - r_j) for two eligible entries of problem c (all arguments wave-uniform); cnt[0], cnt[1]: paths 2 and 3 */
+SLIP_DEV int slip_ratio_cmp(const SlipRatioArgs &A, int c, int i, int j, dig_t *scr, unsigned long long *cnt)
+{
+    const SlipRatioEnt I = slip_ratio_ent(A, c, i), J = slip_ratio_ent(A, c, j);
+    if (I.sx != J.sx) return I.sx < J.sx ? -1 : 1;
+    if (I.sx == 0) return 0;
+    if (!A.alen) return I.sx * wb_cmp(I.x, I.lx, J.x, J.lx);
+    const int64_t s1 = (int64_t) wb_bits(I.x, I.lx) + wb_bits(J.a, J.la), s2 = (int64_t) wb_bits(J.x, J.lx) + wb_bits(I.a, I.la);
+    if (s1 >= s2 + 2) return I.sx;
+    if (s2 >= s1 + 2) return -I.sx;
+    const int w1 = I.lx + J.la, w2 = J.lx + I.la, W = w1 > w2 ? w1 : w2;
+    int cm;
+    cnt[0]++;
+    if (W <= 64) cm = slip_ratio_cmp_reg<1>(I.x, I.lx, J.a, J.la, J.x, J.lx, I.a, I.la);
+    else if (W <= 128) cm = slip_ratio_cmp_reg<2>(I.x, I.lx, J.a, J.la, J.x, J.lx, I.a, I.la);
+    else if (W <= 192) cm = slip_ratio_cmp_reg<3>(I.x, I.lx, J.a, J.la, J.x, J.lx, I.a, I.la);
+    else if (W <= 256) cm = slip_ratio_cmp_reg<4>(I.x, I.lx, J.a, J.la, J.x, J.lx, I.a, I.la);
+    else {
+        cnt[1]++;
+        if (!scr || W > A.wcap) {                                    /* (W <= wcap: the host sized it from maxdig) */
+            if (slip_lane() == 0) *A.err = 1;
+            return 0;
+        }
+        dig_t *P = scr, *Q = scr + A.wcap;
+        wb_mul_lo(P, I.x, I.lx, J.a, J.la, W);
+        wb_mul_lo(Q, J.x, J.lx, I.a, I.la, W);
+        const int lp = wb_len(P, W), lq = wb_len(Q, W);
+        cm = wb_cmp(P, lp, Q, lq);
+        slip_wave_sync();
+    }
+    return I.sx * cm;
+}
+
+/* does entry i come before entry j among equal ratios: the smaller (key[idx], idx) */
+SLIP_DEV int slip_ratio_before(const SlipRatioArgs &A, int i, int j)
+{
+    const int32_t ii = A.oidx ? A.oidx[i] : i, ij = A.oidx ? A.oidx[j] : j;
+    const int32_t ki = A.key ? A.key[ii] : 0, kj = A.key ? A.key[ij] : 0;
+    return ki != kj ? ki < kj : ii < ij;
+}
+
+/* the best of count >= 1 entries pos[0..count) of problem c and the ties it stands for; wt[t]: the entries that pos[t]
+ * already stands for (NULL: one each) */
+SLIP_DEV void slip_ratio_fold(const SlipRatioArgs &A, int c, const int32_t *pos, const int32_t *wt, int count, dig_t *scr,
+                              unsigned long long *cnt, int *best_out, int *ties_out)
+{
+    int best = pos[0], ties = wt ? wt[0] : 1;
+    for (int t = 1; t < count; t++) {
+        const int p = pos[t], w = wt ? wt[t] : 1;
+        const int cm = slip_ratio_cmp(A, c, p, best, scr, cnt);
+        if (cm < 0) { best = p; ties = w; }
+        else if (cm == 0) { ties += w; if (slip_ratio_before(A, p, best)) best = p; }
+    }
+    *best_out = best; *ties_out = ties;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_ratio_kernel(SlipRatioArgs A)
+#else
+static void slip_ratio_body(SlipRatioArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    unsigned long long cnt[2] = {0, 0};
+    if (A.phase <= 1) {
+        const int64_t rpp = ((int64_t) A.n + SLIP_WAVE - 1) / SLIP_WAVE, rounds = rpp * A.nprob;
+        unsigned long long total = 0;
+        for (int64_t r = wave0; r < rounds; r += nwaves) {
+            const int c = (int)(r / rpp);
+            const int64_t i = (r - (int64_t) c * rpp) * SLIP_WAVE + lane, it = (int64_t) c * A.n + i;
+            if (A.phase == 1) {
+                const int take = i < A.n && A.lokey[it] != INT64_MAX && A.lokey[it] <= A.minhi[c];
+                if (take) A.cand[(int64_t) c * A.n + slip_atomic_add_i32(A.ncand + c, 1)] = (int32_t) i;
+                total += (unsigned long long) slip_popc64(slip_ballot(take));
+                continue;
+            }
+            int64_t lo = INT64_MAX, hi = INT64_MAX;
+            int el = 0;
+            uint32_t dx = 0, da = 0;
+            if (i < A.n) {
+                const SlipRatioEnt E = slip_ratio_ent(A, c, (int) i);
+                el = !A.alen || (E.la > 0 && (A.alen[(int64_t) c * A.pstride + i] < 0 ? -1 : 1) == A.asense);
+                if (el && E.sx == 0) lo = hi = 0;
+                else if (el) {
+                    const int64_t bn = 32 * (int64_t) E.lx - slip_clz32(E.x[E.lx - 1]), bd = E.a ? 32 * (int64_t) E.la - slip_clz32(E.a[E.la - 1]) : 1;
+                    const uint64_t n64 = slip_lead64(E.x, E.lx), d64 = E.a ? slip_lead64(E.a, E.la) : 1ull << 63;
+                    const int k = n64 < d64 ? 64 : 63;
+                    const uint64_t Qs = (k == 64 ? slip_div128by64(n64, 0, d64) : slip_div128by64(n64 >> 1, n64 << 63, d64)) >> 2;
+                    const int64_t e = bn - bd - k + 2, kd = slip_ratio_key(Qs - 1, e), ku = slip_ratio_key(Qs + 2, e) + 1;
+                    lo = E.sx < 0 ? -ku : kd; hi = E.sx < 0 ? -kd : ku;
+                }
+                if (el) { dx = (uint32_t) E.lx; da = (uint32_t) E.la; }
+                A.lokey[it] = lo;
+            }
+            const int nel = slip_popc64(slip_ballot(el));
+            const int64_t mh = slip_wave_min_i64(hi);
+            dx = slip_wave_max_u32(dx); da = slip_wave_max_u32(da);
+            if (lane == 0 && nel) {
+                slip_agent_min_i64(A.minhi + c, mh);
+                slip_atomic_add_i32(A.nelig + c, nel);
+                slip_atomic_max_i32(A.maxdig + 0, (int32_t) dx); slip_atomic_max_i32(A.maxdig + 1, (int32_t) da);
+            }
+            total += (unsigned long long) nel;
+        }
+        if (lane == 0 && total) slip_atomic_add_u64(A.paths + A.phase, total);
+        return;
+    }
+    dig_t *scr = A.scratch ? A.scratch + wave0 * 2 * (int64_t) A.wcap : (dig_t *) 0;
+    if (A.phase == 2) {
+        const int64_t items = (int64_t) A.nprob * A.nchunk;
+        for (int64_t it = wave0; it < items; it += nwaves) {
+            const int c = (int)(it / A.nchunk), k = (int)(it - (int64_t) c * A.nchunk);
+            const int nc = A.ncand[c], t0 = k * SLIP_RATIO_CHUNK;
+            if (t0 >= nc) continue;
+            int best, ties;
+            slip_ratio_fold(A, c, A.cand + (int64_t) c * A.n + t0, (const int32_t *) 0, nc - t0 < SLIP_RATIO_CHUNK ? nc - t0 : SLIP_RATIO_CHUNK,
+                            scr, cnt, &best, &ties);
+            if (lane == 0) { A.cwpos[it] = best; A.cwties[it] = ties; }
+        }
+    } else {
+        for (int64_t c = wave0; c < A.nprob; c += nwaves) {
+            const int nc = A.ncand[c];
+            int best = -1, ties = 0;
+            if (nc > 0) slip_ratio_fold(A, (int) c, A.cwpos + c * A.nchunk, A.cwties + c * A.nchunk, (nc + SLIP_RATIO_CHUNK - 1) / SLIP_RATIO_CHUNK,
+                                        scr, cnt, &best, &ties);
+            if (lane == 0) {
+                A.best[c] = best < 0 ? -1 : (A.oidx ? A.oidx[best] : best);
+                A.nties[c] = ties;
+                if (A.wlen) {
+                    const int64_t e = c * A.pstride + (best < 0 ? 0 : best);
+                    A.wlen[2 * c] = best < 0 ? 0 : A.xlen[e]; A.woff[2 * c] = best < 0 ? 0 : A.xoff[e];
+                    A.wlen[2 * c + 1] = best < 0 ? 0 : A.alen[e]; A.woff[2 * c + 1] = best < 0 ? 0 : A.aoff[e];
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        if (cnt[0]) slip_atomic_add_u64(A.paths + 2, cnt[0]);
+        if (cnt[1]) slip_atomic_add_u64(A.paths + 3, cnt[1]);
+    }
+}
+
 /* The transposed view of complete factors (slip_hip_factor_solve_transpose).  With M = A(row_perm, q) the matrix that was
  * factorised, every entry of a REF factorisation is a minor of M (L(i,k) = det M[{0..k-1,i},{0..k}], U(k,j) =
  * det M[{0..k},{0..k-1,j}], rho_k = det M[0..k,0..k]); transposing swaps the rows and columns of every minor, so the REF
@@ -1615,6 +1840,8 @@ struct slip_hip_factor {
     double torational_ms; int64_t torational_paths[4];
     /* slip_hip_factor_solve_mpfr: device time of the last conversion kernel, entries of it by the path that settled them */
     double tompfr_ms; int64_t tompfr_paths[4];
+    /* slip_hip_factor_ratio_test: device time of the last selection's kernels, its path counts */
+    double ratio_ms; int64_t ratio_paths[4];
     /* slip_hip_factor_rewind / _replace_column: the host copy of q; the storage of the resident A -- annz / alimbs are its
      * LIVE entries and limbs, Acap_nz / Acap_nl what dAi, dAlen, dAoff / dAlimbs can hold, Anl_used the limbs of the slab
      * handed out (live ones and the dead ones of replaced columns: new limbs are appended there), A0_nz / A0_nl the initial
@@ -4222,6 +4449,159 @@ extern "C" int slip_hip_matrix_multiply(slip_hip_matrix *M, int32_t transpose, i
 }
 
 extern "C" double slip_hip_matrix_multiply_ms(const slip_hip_matrix *M) { return M ? M->multiply_ms : 0.0; }
+
+/* ---- exact ratio test: the leaving row, the most negative reduced cost, the dual ratio test of a simplex step chosen on
+ * the device (no counterpart in the reference; kernel: slip_ratio_kernel) ---- */
+
+/* the counts of the last slip_hip_ratio_test of this thread (the handle-less entry has nowhere else to keep them) */
+static thread_local int64_t slip_ratio_paths_last[4];
+
+/* one selection on the device.  A: n, nprob, asense, xflip, pstride, the x and a records and oidx are set (device arrays);
+ * key: the host's n keys or NULL.  best, nties, neligible (host) receive nprob values each; with wlen_out the two numerators of
+ * every winner come back as one compact malloc'ed slab (both read from A.xlimbs: the fused call, whose sides share a slab). */
+static int ratio_core(SlipRatioArgs A, const int32_t *key, int32_t *best, int32_t *nties, int32_t *neligible,
+                      int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, hipStream_t stream, double *ms_out, int64_t *paths_out)
+{
+    const int32_t n = A.n, nprob = A.nprob;
+    const int64_t ne = (int64_t) n * nprob, nchunk = ((int64_t) n + SLIP_RATIO_CHUNK - 1) / SLIP_RATIO_CHUNK;
+    const int64_t rounds = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE * nprob, nint = 4 * (int64_t) nprob + 3;
+    int32_t *dkey = NULL, *dint = NULL, *dcand = NULL, *dcw = NULL, *dwlen = NULL; int64_t *dlokey = NULL, *dminhi = NULL, *dwoff = NULL;
+    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
+    int64_t *hminhi = (int64_t *) malloc((size_t) nprob * 8);
+    int32_t *hres = (int32_t *) malloc((size_t) nint * 4);
+    int32_t hmax[2] = {0, 0};
+    int rc = !hminhi || !hres ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    /* dint: the candidate cursors, best, nties, neligible (nprob each, in this order), the two widths, the error flag */
+    A_(dev_alloc(&dint, nint)); A_(dev_alloc(&dcand, ne)); A_(dev_alloc(&dcw, 2 * nprob * nchunk));
+    A_(dev_alloc(&dlokey, ne)); A_(dev_alloc(&dminhi, nprob)); A_(dev_alloc(&dpaths, 4));
+    if (key) { A_(dev_alloc(&dkey, n)); UP_(dkey, key, (size_t) n * 4); }
+    if (wlen_out) { A_(dev_alloc(&dwlen, 2 * (int64_t) nprob)); A_(dev_alloc(&dwoff, 2 * (int64_t) nprob)); }
+    if (!rc) for (int32_t c = 0; c < nprob; c++) hminhi[c] = INT64_MAX;
+    UP_(dminhi, hminhi, (size_t) nprob * 8);
+    HIP_(hipMemsetAsync(dint, 0, (size_t) nint * 4, stream)); HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
+    if (!rc) {
+        SlipTimed timed;
+        A.key = dkey; A.lokey = dlokey; A.minhi = dminhi; A.cand = dcand;
+        A.ncand = dint; A.best = dint + nprob; A.nties = dint + 2 * (int64_t) nprob; A.nelig = dint + 3 * (int64_t) nprob;
+        A.maxdig = dint + 4 * (int64_t) nprob; A.err = A.maxdig + 2;
+        A.nchunk = (int32_t) nchunk; A.cwpos = dcw; A.cwties = dcw + nprob * nchunk;
+        A.wlen = dwlen; A.woff = dwoff; A.paths = dpaths;
+        A_(timed.begin(stream));
+        A.phase = 0; A_(SERVICE_LAUNCH(ratio, wave_blocks(rounds), stream, A));
+        A.phase = 1; A_(SERVICE_LAUNCH(ratio, wave_blocks(rounds), stream, A));
+        /* the widest eligible operands (8 bytes) size the scratch of the memory path */
+        HIP_(hipMemcpyAsync(hmax, A.maxdig, 8, hipMemcpyDeviceToHost, stream)); HIP_(hipStreamSynchronize(stream));
+        const int64_t wcap = (int64_t) hmax[0] + hmax[1];
+        int64_t blocks = wave_blocks(nprob * nchunk);
+        if (!rc && wcap > 256) {
+            if (wcap > (1 << 28)) rc = SLIP_HIP_OUT_OF_MEMORY;
+            blocks = fit_scratch(blocks, 2 * wcap);
+            A_(dev_alloc(&dscr, blocks * SERVICE_WAVES * 2 * wcap));
+            A.scratch = dscr; A.wcap = (int32_t) wcap;
+        }
+        const int64_t fblocks = wave_blocks(nprob) < blocks ? wave_blocks(nprob) : blocks;
+        A.phase = 2; A_(SERVICE_LAUNCH(ratio, blocks, stream, A));
+        A.phase = 3; A_(SERVICE_LAUNCH(ratio, fblocks, stream, A));
+        A_(timed.end(stream, ms_out));
+    }
+    DOWN_(hres, dint, (size_t) nint * 4); DOWN_(hpaths, dpaths, 32);
+    if (!rc && hres[nint - 1]) rc = SLIP_HIP_DEVICE_ERROR;                          /* a product wider than the scratch */
+    int32_t *wl = NULL; uint64_t *wv = NULL; int64_t wn = 0;
+    if (wlen_out) A_(pack_download(2 * (int64_t) nprob, dwlen, dwoff, A.xlimbs, 0, &wl, &wv, &wn, stream));
+    if (!rc) {
+        memcpy(best, hres + nprob, (size_t) nprob * 4); memcpy(nties, hres + 2 * (size_t) nprob, (size_t) nprob * 4);
+        memcpy(neligible, hres + 3 * (size_t) nprob, (size_t) nprob * 4);
+        if (paths_out) for (int t = 0; t < 4; t++) paths_out[t] = (int64_t) hpaths[t];
+        if (wlen_out) { *wlen_out = wl; *wlimbs_out = wv; *wnl_out = wn; wl = NULL; wv = NULL; }
+    }
+    free(hminhi); free(hres); free(wl); free(wv);
+    dev_free(dkey); dev_free(dint); dev_free(dcand); dev_free(dcw); dev_free(dwlen); dev_free(dwoff);
+    dev_free(dlokey); dev_free(dminhi); dev_free(dpaths); dev_free(dscr);
+    return rc;
+}
+
+/* a caller's slab of `count` entries on the device: the host's digit counts and offsets (s), the three device arrays */
+static int ratio_upload(int64_t count, const int32_t *len, const uint64_t *limbs, int64_t cap, SlipSlab *s,
+                        int32_t **dlen, int64_t **doff, uint64_t **dlimbs)
+{
+    int rc = slab_prepare(count, len, limbs, cap, s);
+    A_(dev_alloc(dlen, count)); A_(dev_alloc(doff, count)); A_(dev_alloc(dlimbs, s->total));
+    UP_(*dlen, s->dig, (size_t) count * 4); UP_(*doff, s->off, (size_t) count * 8); UP_(*dlimbs, limbs, (size_t) s->total * 8);
+    return rc;
+}
+
+extern "C" int slip_hip_ratio_test(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                   const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs, int32_t sense, const int32_t *key,
+                                   int32_t *best, int32_t *nties, int32_t *neligible, void *stream_v)
+{
+    if (n <= 0 || nprob < 1 || (sense != 1 && sense != -1) || !xlen || !xlimbs || !alen != !alimbs || !best || !nties || !neligible)
+        return SLIP_HIP_INCORRECT_INPUT;
+    TRY_(need_device());
+    const int64_t ne = (int64_t) n * nprob;
+    SlipSlab xs, as; memset(&xs, 0, sizeof xs); memset(&as, 0, sizeof as);
+    int32_t *dxl = NULL, *dal = NULL; int64_t *dxo = NULL, *dao = NULL; uint64_t *dxv = NULL, *dav = NULL;
+    int rc = ratio_upload(ne, xlen, xlimbs, x_limbs, &xs, &dxl, &dxo, &dxv);
+    if (alen) A_(ratio_upload(ne, alen, alimbs, a_limbs, &as, &dal, &dao, &dav));
+    SlipRatioArgs A; memset(&A, 0, sizeof A);
+    A.n = n; A.nprob = nprob; A.pstride = n; A.xlen = dxl; A.xoff = dxo; A.xlimbs = dxv; A.alen = dal; A.aoff = dao; A.alimbs = dav;
+    A.asense = alen ? sense : 0; A.xflip = !alen && sense < 0;
+    memset(slip_ratio_paths_last, 0, sizeof slip_ratio_paths_last);
+    A_(ratio_core(A, key, best, nties, neligible, NULL, NULL, NULL, (hipStream_t) stream_v, NULL, slip_ratio_paths_last));
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dal); dev_free(dao); dev_free(dav);
+    slab_free(&xs); slab_free(&as);
+    return rc;
+}
+
+extern "C" int slip_hip_ratio_test_paths(int64_t out[4])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_ratio_paths_last, sizeof slip_ratio_paths_last);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_ratio_test(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                                          int32_t sense, const int32_t *key, int32_t *best, int32_t *nties, int32_t *neligible,
+                                          int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    if (!f || nprob < 1 || nprob > (1 << 30) || (sense != 1 && sense != -1) || !blen || !blimbs || !best || !nties || !neligible)
+        return SLIP_HIP_INCORRECT_INPUT;
+    if ((wlen_out || wlimbs_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (!transpose && f->factors_only) return SLIP_HIP_INCORRECT_INPUT;             /* no q behind such a handle */
+    if (wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipSolveOut o;
+    TRY_(solve_device(f, transpose, 2 * nprob, blen, blimbs, stream, &o));
+    const int32_t n = f->n;
+    int32_t *doidx = NULL, *hidx = NULL;
+    int rc = 0;
+    /* the sign of det = rho[n-1] from its pivot record: it decides which sign of anum is eligible */
+    SlipPiv pr; memset(&pr, 0, sizeof pr);
+    DOWN_(&pr, f->P.piv.p_ + (n - 1), sizeof pr);
+    if (!rc && pr.len == 0) rc = SLIP_HIP_DEVICE_ERROR;
+    if (!rc && transpose) {                                /* position p of the transposed solve is row i, pinv[i] = p */
+        hidx = (int32_t *) malloc((size_t) n * 4);
+        if (!hidx) rc = SLIP_HIP_OUT_OF_MEMORY;
+        else for (int32_t i = 0; i < n; i++) hidx[f->tpinv[i]] = i;
+        A_(dev_alloc(&doidx, n)); UP_(doidx, hidx, (size_t) n * 4);
+    }
+    SlipRatioArgs A; memset(&A, 0, sizeof A);
+    A.n = n; A.nprob = nprob; A.pstride = 2 * (int64_t) n; A.oidx = doidx;
+    A.xlen = o.olen; A.xoff = o.ooff; A.xlimbs = o.olimbs; A.alen = o.olen + n; A.aoff = o.ooff + n; A.alimbs = o.olimbs;
+    A.asense = pr.len < 0 ? -sense : sense; A.xflip = pr.len < 0;
+    f->ratio_ms = 0; memset(f->ratio_paths, 0, sizeof f->ratio_paths);
+    A_(ratio_core(A, key, best, nties, neligible, wlen_out, wlimbs_out, wnl_out, stream, &f->ratio_ms, f->ratio_paths));
+    free(hidx); dev_free(doidx);
+    solve_out_free(&o);
+    return rc;
+}
+
+extern "C" double slip_hip_factor_ratio_test_ms(const slip_hip_factor *f) { return f ? f->ratio_ms : 0.0; }
+extern "C" int slip_hip_factor_ratio_test_paths(const slip_hip_factor *f, int64_t out[4])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->ratio_paths, sizeof f->ratio_paths);
+    return SLIP_HIP_OK;
+}
 
 /* ---- subtree farm: multiply the committed factors by per-column scales ---- */
 static void rescale_drop(slip_hip_factor *f)

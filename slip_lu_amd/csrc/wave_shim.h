@@ -311,4 +311,15 @@ SLIP_DEV uint32_t slip_shfl_up_u32(uint32_t v, int d)
     return r;
 }
 
+/* minimum of a signed 64-bit value over the 64 lanes, result in every lane (all lanes active): a butterfly of shuffles,
+ * the same source in both builds */
+SLIP_DEV int64_t slip_wave_min_i64(int64_t v)
+{
+    for (int d = SLIP_WAVE / 2; d > 0; d >>= 1) {
+        const int64_t o = (int64_t) slip_shfl_u64((uint64_t) v, slip_lane() ^ d);
+        if (o < v) v = o;
+    }
+    return v;
+}
+
 #endif /* SLIP_WAVE_SHIM_H */
