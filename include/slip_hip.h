@@ -478,6 +478,54 @@ int slip_hip_factor_ratio_test(slip_hip_factor *f, int32_t transpose, int32_t np
 double slip_hip_factor_ratio_test_ms(const slip_hip_factor *f);
 int slip_hip_factor_ratio_test_paths(const slip_hip_factor *f, int64_t out[4]);
 
+/* Exact pricing on the device: the transposed substitution, the products with a resident matrix and the selection in one
+ * call -- the entering column of a simplex step (Dantzig pricing) or the dual ratio test, with no numerator downloaded.
+ *
+ * Operands.  M is a slip_hip_matrix with m == f->n: its rows are original row ids of A, its ncols columns the candidates.
+ * b holds nside * nprob right-hand sides exactly as slip_hip_factor_solve_transpose takes them (by pivot position, column
+ * q[k] of A); nside is 1 or 2.  y_v is the numerator vector of right-hand side v, by original row id, over det = rho[n-1].
+ * Problem c has the x side v = nside * c and, with nside = 2, the a side v = 2c + 1.  g is optional: glen and glimbs both
+ * non-NULL hold nprob * ncols entries, g_c[j] at c * ncols + j, g_limbs being the capacity of glimbs in limbs.
+ *
+ * Values formed for column j of M:
+ *   X_j = sum_i M(i,j) * y_x[i] - det * g_c[j]     (without g: the sum alone); its true value is X_j / det
+ *   A_j = sum_i M(i,j) * y_a[i]                    (nside = 2; never a g term); its true value is alpha_j = A_j / det
+ * With B y = c_B (b = c_B by position) and g = c_N the reduced cost of column j is d_j = c_j - a_j^T y = -X_j / det: the most
+ * negative reduced cost is sense = -1 (the largest X_j / det).
+ *
+ * Selection.  nside = 1, Dantzig pricing: every column is eligible and best[c] is the j with the smallest sense * X_j / det.
+ * nside = 2, the dual ratio test: slip_hip_factor_ratio_test's definition on (X, A) -- column j is eligible iff sense *
+ * sign(det) * A_j > 0 and its ratio is X_j / (sense * A_j).  Exact ties go to the smallest (key[j], j); key holds ncols entries
+ * or is NULL.  nties[c] counts the eligible columns whose ratio equals the minimum exactly, the winner included; neligible[c]
+ * the eligible columns; best[c] = -1 (nties 0) when nothing is eligible.
+ *
+ * vsign[c] is the sign (-1, 0, +1) of the winner's true x-side value X_best / det, 0 when best[c] = -1: optimality ("no
+ * negative reduced cost") is tested without any numerator.  wlen_out / wlimbs_out / wnl_out (all three or none): the winners'
+ * numerators as one malloc'ed slab (slip_hip_free), entries 2c and 2c + 1 of problem c: X_best and A_best (nside 2), X_best
+ * and an entry of length 0 (nside 1), both of length 0 when best = -1.
+ *
+ * Only the 4 * nprob result integers and, on request, the winners' slab come back from the device: no numerator of y, X or A
+ * is downloaded otherwise.  The products are staged in groups of whole problems under SLIP_HIP_PRODUCT_STAGE_KB (at least one
+ * problem a group; the bound never refuses).
+ *
+ * Needs the complete factorisation; a handle from slip_hip_factor_from_factors is accepted (the transposed solve works
+ * there and nothing of A or q is needed).  SLIP_HIP_INCORRECT_INPUT, with nothing written: a NULL f, M, b or result array,
+ * M->m != f->n, nside not 1 or 2, nprob < 1, sense not +1 or -1, exactly one of glen / glimbs NULL, a g slab longer than
+ * g_limbs, a partial winners' triple, an incomplete factorisation.  A broken handle answers SLIP_HIP_DEVICE_ERROR.  The
+ * handle's solve, solve_transpose, multiply and ratio_test return afterwards what they always did.
+ *
+ * _ms: device ms of the last call by pass: out[0] the record gather and the width pass, out[1] the offset scans, out[2] the
+ * products, out[3] the selection (the substitution: slip_hip_factor_solve_transpose_ms).  _paths: the four counts of
+ * slip_hip_factor_ratio_test_paths for the last price call, summed over its groups. */
+int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int32_t nside, int32_t nprob,
+                          const int32_t *blen, const uint64_t *blimbs,                 /* nside*nprob right-hand sides */
+                          const int32_t *glen, const uint64_t *glimbs, int64_t g_limbs, /* optional: nprob cost vectors of ncols */
+                          int32_t sense, const int32_t *key,
+                          int32_t *best, int32_t *nties, int32_t *neligible, int32_t *vsign,
+                          int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+int slip_hip_factor_price_ms(const slip_hip_factor *f, double out[4]);
+int slip_hip_factor_price_paths(const slip_hip_factor *f, int64_t out[4]);
+
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize
  * creates and destroys one per call): at most SLIP_HIP_POOL_MB megabytes (environment, default 32768; 0 = no pool).  This

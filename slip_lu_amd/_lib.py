@@ -48,7 +48,8 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_multiply", "slip_hip_factor_multiply_ms", "slip_hip_matrix_create", "slip_hip_matrix_multiply",
            "slip_hip_matrix_multiply_ms", "slip_hip_matrix_destroy", "slip_hip_multiply_passes",
            "slip_hip_ratio_test", "slip_hip_ratio_test_paths", "slip_hip_factor_ratio_test", "slip_hip_factor_ratio_test_ms",
-           "slip_hip_factor_ratio_test_paths")
+           "slip_hip_factor_ratio_test_paths",
+           "slip_hip_factor_price", "slip_hip_factor_price_ms", "slip_hip_factor_price_paths")
 
 _libs = {}
 
@@ -172,5 +173,12 @@ def load(path=None):
     lib.slip_hip_factor_ratio_test_ms.restype = C.c_double
     lib.slip_hip_factor_ratio_test_paths.argtypes = [vp, vp]
     lib.slip_hip_factor_ratio_test_paths.restype = C.c_int
+    lib.slip_hip_factor_price.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, i64, C.c_int32, vp, vp, vp, vp, vp,
+                                          C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
+    lib.slip_hip_factor_price.restype = C.c_int
+    lib.slip_hip_factor_price_ms.argtypes = [vp, vp]
+    lib.slip_hip_factor_price_ms.restype = C.c_int
+    lib.slip_hip_factor_price_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_price_paths.restype = C.c_int
     _libs[path] = lib
     return lib

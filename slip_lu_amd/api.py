@@ -690,6 +690,50 @@ class Factorization:
         products, of those the comparisons on the memory path]"""
         return _paths(self.lib.slip_hip_factor_ratio_test_paths, self.h)
 
+    def price(self, M, blen, blimbs, nprob=1, sides=1, cost=None, sense=1, key=None, winners=False, stream=None):
+        """Solve, multiply and select on the device (slip_hip_factor_price): b holds sides * nprob right-hand sides as
+        `solve_transpose` takes them, M is a SparseMatrix with m == n whose columns are the candidates.  With y the
+        numerators of the solve by row id over det, column j of M gives X_j = M(:,j)^T y_x - det * cost_c[j] (cost: None or
+        (signed limb counts, limbs) of nprob * ncols entries) and, with sides=2, A_j = M(:,j)^T y_a.  sides=1: best is the j
+        with the smallest sense * X_j / det (the reduced cost of column j is -X_j / det: sense=-1 is the most negative one);
+        sides=2: the dual ratio test, `ratio_test`'s definition on (X, A).  Exact ties go to the smallest (key[j], j).
+        Returns (best, nties, neligible, vsign), int32[nprob] each, vsign the sign of X_best / det; with winners=True also
+        (wlen, wlimbs): X_best and A_best of problem c as entries 2c and 2c + 1 (sides=1: the second one empty), both empty
+        where best is -1.  No numerator is downloaded otherwise."""
+        nprob, sides = int(nprob), int(sides)
+        ncols = M.ncols
+        blen, blimbs, _ = _rhs(self.n, blen, blimbs, sides * nprob if nprob >= 1 and sides in (1, 2) else 0)
+        if cost is None:
+            g = (None, None, 0)
+        else:
+            glen, glimbs, gcap = _limb_arrays(*cost)
+            if nprob >= 1 and glen.size != nprob * ncols:
+                raise ValueError("price: cost must hold nprob*ncols entries")
+            g = (glen.ctypes.data, glimbs.ctypes.data, gcap)
+        key = _ratio_key(ncols, key)
+        best, nties, nelig, vsign = (np.zeros(max(nprob, 1), np.int32) for _ in range(4))
+        pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+        outs = (C.byref(pl), C.byref(px), C.byref(nl)) if winners else (None, None, None)
+        rc = self.lib.slip_hip_factor_price(self.h, M.h, sides, nprob, blen.ctypes.data, blimbs.ctypes.data, *g,
+                                            int(sense), None if key is None else key.ctypes.data,
+                                            best.ctypes.data, nties.ctypes.data, nelig.ctypes.data, vsign.ctypes.data,
+                                            *outs, C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_price")
+        res = (best[:nprob], nties[:nprob], nelig[:nprob], vsign[:nprob])
+        return res + _take_slab(self.lib, pl, px, nl, 2 * nprob) if winners else res
+
+    def price_ms(self):
+        """device ms of the last price by pass: [the record gather and the widths, the offset scans, the products, the
+        selection] (the substitution: solve_transpose_ms)"""
+        out = np.zeros(4, np.float64)
+        self.lib.slip_hip_factor_price_ms(self.h, out.ctypes.data)
+        return [float(v) for v in out]
+
+    def price_paths(self):
+        """the last price: the four counts of ratio_test_paths over its selections"""
+        return _paths(self.lib.slip_hip_factor_price_paths, self.h)
+
     def solve_transpose_ms(self):
         """(device ms of the last transposed solve's substitution kernels, ms of that call's view build: 0 when it was reused)"""
         view = C.c_double()

@@ -1469,6 +1469,59 @@ static void slip_ratio_body(SlipRatioArgs A)
     }
 }
 
+/* Exact pricing (slip_hip_factor_price): the record work between the transposed substitution, slip_product_kernel
+ * and slip_ratio_kernel.  Every phase takes `count` entries one to a lane, a wave's 64 entries a round (the loops are
+ * wave-uniform); no limb moves.
+ * phase 0, the record gather: the substitution leaves its output by pivot position p, the column view of a matrix indexes x
+ *   by row id i, pinv[i] = p: xlen[v*n + i] = olen[v*n + pinv[i]] and the offsets likewise, count = n * the vectors.
+ * phase 1, the widest item: the maximum of w[0..count) into wmax[0], one atomic per wave (the widths of slip_product_kernel's
+ *   phase 0: the host sizes the memory path's scratch from it).
+ * phase 2, one lane per problem, count = nprob: vsign[c] = the sign of the winner's x-side value over det (dneg: det < 0)
+ *   from its signed digit count, 0 when best[c] = -1; with wlen, the records of the winners' slab of a selection without
+ *   denominators (entry 2c: the winner's x record, 2c + 1: empty). */
+struct SlipPriceArgs {
+    int32_t phase, n, dneg; int64_t count, pstride;
+    const int32_t *pinv, *olen; const int64_t *ooff; int32_t *xlen; int64_t *xoff;        /* phase 0                          */
+    const int32_t *w; int32_t *wmax;                                                       /* phase 1                          */
+    const int32_t *best, *rlen; const int64_t *soff;                                       /* phase 2: x of problem c at c * pstride */
+    int32_t *vsign, *wlen; int64_t *woff;
+};
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_price_kernel(SlipPriceArgs A)
+#else
+static void slip_price_body(SlipPriceArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    const int64_t rounds = (A.count + SLIP_WAVE - 1) / SLIP_WAVE;
+    uint32_t wm = 0;
+    for (int64_t r = wave0; r < rounds; r += nwaves) {
+        const int64_t t = r * SLIP_WAVE + lane;
+        if (A.phase == 0) {
+            if (t < A.count) {
+                const int64_t v = t / A.n, s = v * A.n + A.pinv[t - v * A.n];
+                A.xlen[t] = A.olen[s]; A.xoff[t] = A.ooff[s];
+            }
+        } else if (A.phase == 1) {
+            const uint32_t w = slip_wave_max_u32(t < A.count ? (uint32_t) A.w[t] : 0u);
+            if (w > wm) wm = w;
+        } else if (t < A.count) {
+            const int32_t b = A.best[t];
+            const int64_t e = t * A.pstride + (b < 0 ? 0 : b);
+            const int32_t sx = b < 0 ? 0 : A.rlen[e];
+            A.vsign[t] = sx == 0 ? 0 : (((sx < 0) != (A.dneg != 0)) ? -1 : 1);
+            if (A.wlen) {
+                A.wlen[2 * t] = sx; A.woff[2 * t] = b < 0 ? 0 : A.soff[e];
+                A.wlen[2 * t + 1] = 0; A.woff[2 * t + 1] = 0;
+            }
+        }
+    }
+    if (A.phase == 1 && lane == 0 && wm) slip_atomic_max_i32(A.wmax, (int32_t) wm);
+}
+
 /* The transposed view of complete factors (slip_hip_factor_solve_transpose).  With M = A(row_perm, q) the matrix that was
  * factorised, every entry of a REF factorisation is a minor of M (L(i,k) = det M[{0..k-1,i},{0..k}], U(k,j) =
  * det M[{0..k},{0..k-1,j}], rho_k = det M[0..k,0..k]); transposing swaps the rows and columns of every minor, so the REF
@@ -1842,6 +1895,8 @@ struct slip_hip_factor {
     double tompfr_ms; int64_t tompfr_paths[4];
     /* slip_hip_factor_ratio_test: device time of the last selection's kernels, its path counts */
     double ratio_ms; int64_t ratio_paths[4];
+    /* slip_hip_factor_price: device time of the last call by pass, the path counts of its selections */
+    double price_ms[4]; int64_t price_paths[4];
     /* slip_hip_factor_rewind / _replace_column: the host copy of q; the storage of the resident A -- annz / alimbs are its
      * LIVE entries and limbs, Acap_nz / Acap_nl what dAi, dAlen, dAoff / dAlimbs can hold, Anl_used the limbs of the slab
      * handed out (live ones and the dead ones of replaced columns: new limbs are appended there), A0_nz / A0_nl the initial
@@ -4219,55 +4274,72 @@ static int64_t product_stage_limbs(void)
     return kb > 0 ? (int64_t) kb * 128 : ((int64_t) 256 << 20) / 8;
 }
 
-/* one product on the device: x (and b, with bs != NULL) prepared on the host; d_c as device records into ddlimbs (with b).
- * The result is one compact malloc'ed slab of V.nout * nvec entries, signed limb counts. */
-static int product_core(const SlipProductView &V, int32_t nvec, const SlipSlab &xs, const uint64_t *xlimbs,
-                        const SlipSlab *bs, const uint64_t *blimbs,
-                        const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
-                        int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, hipStream_t stream, double *ms_out)
+/* operand records on the device: signed digit counts, limb offsets, the limbs */
+struct SlipDevRecs { const int32_t *len; const int64_t *off; const uint64_t *limbs; };
+
+/* one product on operands that are on the device already; d_c as device records (with b).  xmaxdig: the digits of the widest
+ * entry of x, or negative when only the device knows the lengths (a substitution's output): the widest item is then reduced
+ * from the widths the width pass wrote (slip_price_kernel) and four bytes are read back.  The result stays on the device:
+ * vectors are staged in groups of whole multiples of `gran` (at least gran: the bound groups, it never refuses) and
+ * sink(c0, nv, rlen, soff, stage, &t) is handed every group -- vectors c0 .. c0 + nv, the signed digit counts and staging
+ * offsets of their nout * nv items, the staging slab; its t is added to ms[3].  ms: device ms by pass (the widths, the offset
+ * scans, the products, the sink's). */
+template <class Sink>
+static int product_device(const SlipProductView &V, int32_t nvec, const SlipDevRecs &x, int32_t xmaxdig,
+                          const SlipDevRecs *b, int32_t bmaxdig, const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
+                          int64_t gran, Sink sink, hipStream_t stream, double ms[4])
 {
-    const int64_t nout = V.nout, ne = nout * nvec, nxe = (int64_t) V.nx * nvec;
+    const int64_t nout = V.nout, ne = nout * nvec;
     /* every width is at most wtop (slip_product_kernel), wcap in whole limbs: the staging of a group and the memory path's scratch
      * are sized from it */
-    const int64_t wtop = (bs && dmaxdig + bs->maxdig > V.amaxdig + xs.maxdig ? dmaxdig + bs->maxdig : V.amaxdig + xs.maxdig) + 1;
-    const int64_t wcap = (wtop + 1) & ~(int64_t) 1;
-    if (wcap > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
-    int64_t group = product_stage_limbs() / (nout * (wcap / 2));                  /* vectors staged together */
-    if (group < 1) group = 1;
-    if (group > nvec) group = nvec;
-    const int64_t blocks = wtop > 256 ? fit_scratch(wave_blocks(ne), wcap) : wave_blocks(ne), sblocks = offscan_blocks(nout * group);
-    int32_t *dxl = NULL, *dbl = NULL, *dw = NULL, *drl = NULL; int64_t *dxo = NULL, *dbo = NULL, *dso = NULL; uint64_t *dxv = NULL, *dbv = NULL;
+    int64_t wtop = (b && dmaxdig + bmaxdig > V.amaxdig + xmaxdig ? dmaxdig + bmaxdig : V.amaxdig + xmaxdig) + 1;
+    if (xmaxdig >= 0 && ((wtop + 1) & ~(int64_t) 1) > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
+    int32_t *dw = NULL, *drl = NULL, *dwmax = NULL; int64_t *dso = NULL;
     dig_t *dscr = NULL; unsigned long long *bsum = NULL;
-    int32_t *rl = (int32_t *) malloc((size_t) ne * 4); uint64_t *rv = NULL; int64_t rn = 0;
-    double ms[4] = {0, 0, 0, 0};
-    int rc = !rl ? SLIP_HIP_OUT_OF_MEMORY : 0;
-    A_(dev_alloc(&dxl, nxe)); A_(dev_alloc(&dxo, nxe)); A_(dev_alloc(&dxv, xs.total));
-    if (bs) { A_(dev_alloc(&dbl, ne)); A_(dev_alloc(&dbo, ne)); A_(dev_alloc(&dbv, bs->total)); }
-    A_(dev_alloc(&dw, ne)); A_(dev_alloc(&dso, ne)); A_(dev_alloc(&drl, ne)); A_(dev_alloc(&bsum, sblocks));
-    if (wtop > 256) A_(dev_alloc(&dscr, blocks * SERVICE_WAVES * wcap));
-    UP_(dxl, xs.dig, (size_t) nxe * 4); UP_(dxo, xs.off, (size_t) nxe * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
-    if (bs) { UP_(dbl, bs->dig, (size_t) ne * 4); UP_(dbo, bs->off, (size_t) ne * 8); UP_(dbv, blimbs, (size_t) bs->total * 8); }
+    int rc = 0;
+    A_(dev_alloc(&dw, ne)); A_(dev_alloc(&dso, ne)); A_(dev_alloc(&drl, ne));
+    if (xmaxdig < 0) A_(dev_alloc(&dwmax, 1));
     SlipProductArgs A; memset(&A, 0, sizeof A);
     A.nout = V.nout; A.nx = V.nx; A.rp = V.rp; A.re = V.re; A.rx = V.rx; A.alen = V.alen; A.aoff = V.aoff; A.alimbs = V.alimbs;
-    A.xlimbs = dxv; A.blimbs = dbv; A.dlimbs = ddlimbs; A.scratch = dscr; A.wcap = (int32_t) wcap;
+    A.xlimbs = x.limbs; A.blimbs = b ? b->limbs : NULL; A.dlimbs = ddlimbs;
     /* the vectors c0 .. c0 + nv of the operands */
     auto slice = [&](int64_t c0, int64_t nv, int phase) {
         A.nvec = (int32_t) nv; A.phase = phase;
-        A.xlen = dxl + c0 * V.nx; A.xoff = dxo + c0 * V.nx;
-        A.blen = bs ? dbl + c0 * nout : NULL; A.boff = bs ? dbo + c0 * nout : NULL;
-        A.dlen = bs ? ddlen + c0 : NULL; A.doff = bs ? ddoff + c0 : NULL;
+        A.xlen = x.len + c0 * V.nx; A.xoff = x.off + c0 * V.nx;
+        A.blen = b ? b->len + c0 * nout : NULL; A.boff = b ? b->off + c0 * nout : NULL;
+        A.dlen = b ? ddlen + c0 : NULL; A.doff = b ? ddoff + c0 : NULL;
         A.wlen = dw + c0 * nout; A.soff = dso + c0 * nout; A.rlen = drl + c0 * nout;
     };
-    if (!rc) {                                             /* pass 1: the widths of all items */
+    if (!rc) {                                             /* pass 1: the widths of all items (and the widest of them) */
         SlipTimed timed;
         slice(0, nvec, 0);
         A_(timed.begin(stream));
         A_(SERVICE_LAUNCH(product, wave_blocks(ne), stream, A));
+        if (xmaxdig < 0) {
+            SlipPriceArgs R; memset(&R, 0, sizeof R);
+            R.phase = 1; R.count = ne; R.w = dw; R.wmax = dwmax;
+            HIP_(hipMemsetAsync(dwmax, 0, 4, stream));
+            A_(SERVICE_LAUNCH(price, service_blocks(ne), stream, R));
+        }
         A_(timed.end(stream, &ms[0]));
     }
+    if (xmaxdig < 0) {
+        int32_t hwmax = 0;
+        DOWN_(&hwmax, dwmax, 4);
+        wtop = hwmax;
+    }
+    const int64_t wcap = (wtop + 1) & ~(int64_t) 1;
+    if (!rc && (wcap > (1 << 28) || wcap < 2)) rc = wcap < 2 ? SLIP_HIP_DEVICE_ERROR : SLIP_HIP_OUT_OF_MEMORY;
+    int64_t group = rc ? gran : product_stage_limbs() / (nout * (wcap / 2)) / gran * gran;      /* vectors staged together */
+    if (group < gran) group = gran;
+    if (group > nvec) group = nvec;
+    const int64_t blocks = wtop > 256 ? fit_scratch(wave_blocks(ne), wcap) : wave_blocks(ne), sblocks = offscan_blocks(nout * group);
+    A_(dev_alloc(&bsum, sblocks));
+    if (wtop > 256) A_(dev_alloc(&dscr, blocks * SERVICE_WAVES * wcap));
+    A.scratch = dscr; A.wcap = (int32_t) wcap;
     for (int64_t c0 = 0; c0 < nvec && !rc; c0 += group) {
         const int64_t nv = c0 + group <= nvec ? group : nvec - c0, cnt = nout * nv;
-        uint64_t *dstage = NULL; int32_t *gl = NULL; uint64_t *gv = NULL; int64_t gn = 0, total = 0;
+        uint64_t *dstage = NULL; int64_t total = 0;
         double t = 0;
         slice(c0, nv, 1);
         {                                                  /* pass 2: the staging offsets from the widths */
@@ -4288,23 +4360,51 @@ static int product_core(const SlipProductView &V, int32_t nvec, const SlipSlab &
             A_(timed.end(stream, &t));
             ms[2] += t;
         }
-        A_(pack_download(cnt, A.rlen, A.soff, dstage, 0, &gl, &gv, &gn, stream, &t));
+        t = 0;
+        A_(sink(c0, nv, (const int32_t *) A.rlen, A.soff, (const uint64_t *) dstage, &t));
+        if (!rc) ms[3] += t;
+        dev_free(dstage);
+    }
+    dev_free(dw); dev_free(dso); dev_free(drl); dev_free(dwmax); dev_free(bsum); dev_free(dscr);
+    return rc;
+}
+
+/* one product on the device: x (and b, with bs != NULL) prepared on the host; d_c as device records into ddlimbs (with b).
+ * The result is one compact malloc'ed slab of V.nout * nvec entries, signed limb counts. */
+static int product_core(const SlipProductView &V, int32_t nvec, const SlipSlab &xs, const uint64_t *xlimbs,
+                        const SlipSlab *bs, const uint64_t *blimbs,
+                        const int32_t *ddlen, const int64_t *ddoff, const uint64_t *ddlimbs, int32_t dmaxdig,
+                        int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, hipStream_t stream, double *ms_out)
+{
+    const int64_t nout = V.nout, ne = nout * nvec, nxe = (int64_t) V.nx * nvec;
+    int32_t *dxl = NULL, *dbl = NULL; int64_t *dxo = NULL, *dbo = NULL; uint64_t *dxv = NULL, *dbv = NULL;
+    int32_t *rl = (int32_t *) malloc((size_t) ne * 4); uint64_t *rv = NULL; int64_t rn = 0;
+    double ms[4] = {0, 0, 0, 0};
+    int rc = !rl ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    A_(dev_alloc(&dxl, nxe)); A_(dev_alloc(&dxo, nxe)); A_(dev_alloc(&dxv, xs.total));
+    if (bs) { A_(dev_alloc(&dbl, ne)); A_(dev_alloc(&dbo, ne)); A_(dev_alloc(&dbv, bs->total)); }
+    UP_(dxl, xs.dig, (size_t) nxe * 4); UP_(dxo, xs.off, (size_t) nxe * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
+    if (bs) { UP_(dbl, bs->dig, (size_t) ne * 4); UP_(dbo, bs->off, (size_t) ne * 8); UP_(dbv, blimbs, (size_t) bs->total * 8); }
+    const SlipDevRecs x = {dxl, dxo, dxv}, b = {dbl, dbo, dbv};
+    /* a group packed and downloaded (pack_download), appended to the result */
+    auto sink = [&](int64_t c0, int64_t nv, const int32_t *drl, const int64_t *dso, const uint64_t *dstage, double *t) {
+        int32_t *gl = NULL; uint64_t *gv = NULL; int64_t gn = 0;
+        int rc = pack_download(nout * nv, drl, dso, dstage, 0, &gl, &gv, &gn, stream, t);
         if (!rc) {
-            ms[3] += t;
             uint64_t *grown = (uint64_t *) realloc(rv, (size_t)(rn + gn > 0 ? rn + gn : 1) * 8);
             if (!grown) rc = SLIP_HIP_OUT_OF_MEMORY;
             else {
                 rv = grown;
-                memcpy(rl + c0 * nout, gl, (size_t) cnt * 4);
+                memcpy(rl + c0 * nout, gl, (size_t)(nout * nv) * 4);
                 if (gn > 0) memcpy(rv + rn, gv, (size_t) gn * 8);
                 rn += gn;
             }
         }
         free(gl); free(gv);
-        dev_free(dstage);
-    }
+        return rc;
+    };
+    A_(product_device(V, nvec, x, xs.maxdig, bs ? &b : NULL, bs ? bs->maxdig : 0, ddlen, ddoff, ddlimbs, dmaxdig, 1, sink, stream, ms));
     dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dbl); dev_free(dbo); dev_free(dbv);
-    dev_free(dw); dev_free(dso); dev_free(drl); dev_free(bsum); dev_free(dscr);
     if (rc) { free(rl); free(rv); return rc; }
     memcpy(slip_product_passes_last, ms, sizeof ms);
     if (ms_out) *ms_out = ms[0] + ms[1] + ms[2] + ms[3];
@@ -4600,6 +4700,145 @@ extern "C" int slip_hip_factor_ratio_test_paths(const slip_hip_factor *f, int64_
 {
     if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
     memcpy(out, f->ratio_paths, sizeof f->ratio_paths);
+    return SLIP_HIP_OK;
+}
+
+/* ---- exact pricing: the entering column (Dantzig) or the dual ratio test chosen on the device, fused from the transposed
+ * substitution (slip_solve_kernel on the view), the products with a resident matrix (slip_product_kernel) and the selection
+ * (slip_ratio_kernel), joined by slip_price_kernel's records; no numerator leaves the device (no counterpart in the reference;
+ * DESIGN 3k) ---- */
+extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int32_t nside, int32_t nprob,
+                                     const int32_t *blen, const uint64_t *blimbs,
+                                     const int32_t *glen, const uint64_t *glimbs, int64_t g_limbs,
+                                     int32_t sense, const int32_t *key,
+                                     int32_t *best, int32_t *nties, int32_t *neligible, int32_t *vsign,
+                                     int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    if (!f || !M || !blen || !blimbs || !best || !nties || !neligible || !vsign || (nside != 1 && nside != 2) || nprob < 1 ||
+        nprob > (1 << 29) || (sense != 1 && sense != -1) || !glen != !glimbs)
+        return SLIP_HIP_INCORRECT_INPUT;
+    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (M->m != f->n) return SLIP_HIP_INCORRECT_INPUT;
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
+    if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
+    const int32_t n = f->n, ncols = M->ncols, nvec = nside * nprob;
+    const int64_t nxe = (int64_t) n * nvec, ne = (int64_t) ncols * nvec;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipSlab gs; memset(&gs, 0, sizeof gs);
+    if (glen) TRY_(slab_prepare((int64_t) nprob * ncols, glen, glimbs, g_limbs, &gs));
+    if (wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
+    SlipSolveOut o;
+    int rc = solve_device(f, 1, nvec, blen, blimbs, stream, &o);
+    if (rc) { slab_free(&gs); return rc; }
+    int32_t *dxl = NULL, *dgl = NULL, *ddlen = NULL, *dsel = NULL, *dwl = NULL; int64_t *dxo = NULL, *dgo = NULL, *ddoff = NULL, *dwo = NULL;
+    uint64_t *dgv = NULL;
+    int32_t dmaxdig = 0;
+    /* the result on the host until all of it stands: best, nties, neligible, vsign, nprob each */
+    int32_t *hres = (int32_t *) malloc((size_t) nprob * 16), *wl = wlen_out ? (int32_t *) malloc((size_t) nprob * 8) : NULL;
+    uint64_t *wv = NULL; int64_t wn = 0;
+    double gather_ms = 0, ms[4] = {0, 0, 0, 0};
+    int64_t paths[4] = {0, 0, 0, 0};
+    if (!hres || (wlen_out && !wl)) rc = SLIP_HIP_OUT_OF_MEMORY;
+    /* the sign of det = rho[n-1] from its pivot record: it decides the eligible sign of A, the direction of X and vsign */
+    SlipPiv pr; memset(&pr, 0, sizeof pr);
+    DOWN_(&pr, f->P.piv.p_ + (n - 1), sizeof pr);
+    if (!rc && pr.len == 0) rc = SLIP_HIP_DEVICE_ERROR;
+    const int dneg = pr.len < 0;
+    /* y by row id: the records of the substitution's output gathered through pinv, its limbs where they are */
+    A_(dev_alloc(&dxl, nxe)); A_(dev_alloc(&dxo, nxe));
+    if (!rc) {
+        SlipTimed timed;
+        SlipPriceArgs G; memset(&G, 0, sizeof G);
+        G.phase = 0; G.n = n; G.count = nxe; G.pinv = f->P.pinv.p_; G.olen = o.olen; G.ooff = o.ooff; G.xlen = dxl; G.xoff = dxo;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(price, service_blocks(nxe), stream, G));
+        A_(timed.end(stream, &gather_ms));
+    }
+    /* det * g: the cost vector's records on the x side of every problem, empty records on its a side */
+    if (glen) {
+        int32_t *hl = (int32_t *) calloc((size_t) ne, 4); int64_t *ho = (int64_t *) calloc((size_t) ne, 8);
+        if (!hl || !ho) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
+        else for (int32_t c = 0; c < nprob; c++) {
+            memcpy(hl + (int64_t) nside * c * ncols, gs.dig + (int64_t) c * ncols, (size_t) ncols * 4);
+            memcpy(ho + (int64_t) nside * c * ncols, gs.off + (int64_t) c * ncols, (size_t) ncols * 8);
+        }
+        A_(dev_alloc(&dgl, ne)); A_(dev_alloc(&dgo, ne)); A_(dev_alloc(&dgv, gs.total));
+        UP_(dgl, hl, (size_t) ne * 4); UP_(dgo, ho, (size_t) ne * 8); UP_(dgv, glimbs, (size_t) gs.total * 8);
+        free(hl); free(ho);
+        A_(det_records(f, nvec, &ddlen, &ddoff, &dmaxdig));
+    }
+    /* per group: best (up), vsign (down), and without denominators the winners' records */
+    A_(dev_alloc(&dsel, 2 * (int64_t) nprob));
+    if (wlen_out && nside == 1) { A_(dev_alloc(&dwl, 2 * (int64_t) nprob)); A_(dev_alloc(&dwo, 2 * (int64_t) nprob)); }
+    SlipProductView V;
+    V.nout = ncols; V.nx = n; V.alen = M->dAlen; V.aoff = M->dAoff; V.alimbs = M->dAlimbs; V.amaxdig = M->amaxdig;
+    V.rp = M->col_rp; V.re = M->col_re; V.rx = M->col_rx;
+    const SlipDevRecs x = {dxl, dxo, o.olimbs}, g = {dgl, dgo, dgv};
+    /* the selection on a group of whole problems, on the staged records: X of problem c at c * pstride, A (nside 2) ncols on */
+    auto select = [&](int64_t c0, int64_t nv, const int32_t *rlen, const int64_t *soff, const uint64_t *stage, double *t) {
+        const int64_t p0 = c0 / nside;
+        const int32_t np = (int32_t)(nv / nside);
+        const int pair = wlen_out && nside == 2, single = wlen_out && nside == 1;
+        int32_t *gwl = NULL; uint64_t *gwv = NULL; int64_t gwn = 0, gp[4] = {0, 0, 0, 0};
+        SlipRatioArgs R; memset(&R, 0, sizeof R);
+        R.n = ncols; R.nprob = np; R.pstride = (int64_t) nside * ncols;
+        R.xlen = rlen; R.xoff = soff; R.xlimbs = stage;
+        if (nside == 2) { R.alen = rlen + ncols; R.aoff = soff + ncols; R.alimbs = stage; R.asense = dneg ? -sense : sense; R.xflip = dneg; }
+        else R.xflip = (sense < 0) != (dneg != 0);
+        int rc = ratio_core(R, key, hres + p0, hres + nprob + p0, hres + 2 * (int64_t) nprob + p0,
+                            pair ? &gwl : NULL, pair ? &gwv : NULL, pair ? &gwn : NULL, stream, t, gp);
+        int32_t *dbest = dsel, *dvs = dsel + nprob;
+        UP_(dbest, hres + p0, (size_t) np * 4);
+        if (!rc) {
+            SlipPriceArgs Q; memset(&Q, 0, sizeof Q);
+            Q.phase = 2; Q.count = np; Q.pstride = R.pstride; Q.dneg = dneg; Q.best = dbest; Q.rlen = rlen; Q.soff = soff; Q.vsign = dvs;
+            if (single) { Q.wlen = dwl; Q.woff = dwo; }
+            A_(SERVICE_LAUNCH(price, service_blocks(np), stream, Q));
+            HIP_(hipStreamSynchronize(stream));
+        }
+        DOWN_(hres + 3 * (int64_t) nprob + p0, dvs, (size_t) np * 4);
+        if (single) A_(pack_download(2 * (int64_t) np, dwl, dwo, stage, 0, &gwl, &gwv, &gwn, stream));
+        if (!rc && wlen_out) {
+            uint64_t *grown = (uint64_t *) realloc(wv, (size_t)(wn + gwn > 0 ? wn + gwn : 1) * 8);
+            if (!grown) rc = SLIP_HIP_OUT_OF_MEMORY;
+            else {
+                wv = grown;
+                memcpy(wl + 2 * p0, gwl, (size_t) np * 8);
+                if (gwn > 0) memcpy(wv + wn, gwv, (size_t) gwn * 8);
+                wn += gwn;
+            }
+        }
+        if (!rc) for (int k = 0; k < 4; k++) paths[k] += gp[k];
+        free(gwl); free(gwv);
+        return rc;
+    };
+    A_(product_device(V, nvec, x, -1, glen ? &g : NULL, gs.maxdig, ddlen, ddoff, f->P.Llimbs, dmaxdig, nside, select, stream, ms));
+    dev_free(dxl); dev_free(dxo); dev_free(dgl); dev_free(dgo); dev_free(dgv); dev_free(ddlen); dev_free(ddoff);
+    dev_free(dsel); dev_free(dwl); dev_free(dwo);
+    slab_free(&gs);
+    solve_out_free(&o);
+    if (!rc) {
+        memcpy(best, hres, (size_t) nprob * 4); memcpy(nties, hres + nprob, (size_t) nprob * 4);
+        memcpy(neligible, hres + 2 * (size_t) nprob, (size_t) nprob * 4); memcpy(vsign, hres + 3 * (size_t) nprob, (size_t) nprob * 4);
+        if (wlen_out) { *wlen_out = wl; *wlimbs_out = wv; *wnl_out = wn; wl = NULL; wv = NULL; }
+        ms[0] += gather_ms;
+        memcpy(f->price_ms, ms, sizeof ms); memcpy(f->price_paths, paths, sizeof paths);
+    }
+    free(hres); free(wl); free(wv);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_price_ms(const slip_hip_factor *f, double out[4])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->price_ms, sizeof f->price_ms);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_price_paths(const slip_hip_factor *f, int64_t out[4])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->price_paths, sizeof f->price_paths);
     return SLIP_HIP_OK;
 }
 
