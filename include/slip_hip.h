@@ -29,6 +29,8 @@
  *   slip_hip_matrix_*                         the exact sparse products of a simplex code's pricing and of a residual
  *   slip_hip_ratio_test,                 <->  no counterpart: the exact ratio test of a simplex step (the leaving row, the
  *   slip_hip_factor_ratio_test                most negative reduced cost, the dual ratio test); only the choice comes back
+ *   slip_hip_*ratio_test_bounded,        <->  no counterpart: the ratio test of a basis with boxed variables l <= x <= u, and
+ *   slip_hip_*bound_test                      the most violated bound (primal feasibility, the dual simplex's leaving row)
  *   status codes                         <->  SLIP_info, SLIP_LU.h:160-168
  *
  * The GMP-typed drop-in  SLIP_LU_factorize(L,U,A,S,rhos,pinv,option)  built on
@@ -525,6 +527,83 @@ int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int32_t nside,
                           int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
 int slip_hip_factor_price_ms(const slip_hip_factor *f, double out[4]);
 int slip_hip_factor_price_paths(const slip_hip_factor *f, int64_t out[4]);
+
+/* Bounds in the exact selections: the ratio test of a basis whose variables are boxed, l_i <= x_i <= u_i with either side
+ * possibly infinite, and the exact feasibility test (the most violated bound: the dual simplex's leaving row).
+ *
+ * A set of bounds: kind[i] bit 0 = a finite lower bound, bit 1 = a finite upper bound (any other bit is refused); integer
+ * numerators lonum_i, hinum_i as two limb slabs of n entries (the entry of a side kind switches off is ignored and may have
+ * length 0; a side no entry switches on may be NULL, NULL, 0); one common denominator bd > 0 as a signed limb count and limbs,
+ * NULL limbs meaning 1.  l_i = lonum_i / bd, u_i = hinum_i / bd; nothing requires l_i <= u_i.  One set is shared by all
+ * problems of a call, as key is; entry i, key[i] and every reported index are in the index of the matching solve's output
+ * (pivot position for transpose 0, original row id for transpose 1). */
+typedef struct slip_hip_bounds {
+    const int32_t *kind;                                   /* n entries: bit 0 lower, bit 1 upper */
+    const int32_t *lolen; const uint64_t *lolimbs; int64_t lo_limbs;   /* n entries; NULL,NULL,0 iff no entry has bit 0 */
+    const int32_t *hilen; const uint64_t *hilimbs; int64_t hi_limbs;   /* likewise for bit 1 */
+    int32_t bdlen; const uint64_t *bdlimbs;                /* common denominator > 0; NULL limbs = 1 */
+} slip_hip_bounds;
+
+/* Bounded ratio test.  Problem c: numerators xnum, anum over one nonzero signed d (on a handle d = det = rho[n-1]).  With
+ * s = sign(d) and t_i = sense * s * anum_i:
+ *   t_i > 0: eligible iff bit 0 of kind[i];  N_i = bd * xnum_i - d * lonum_i,  a'_i =  anum_i,  side -1
+ *   t_i < 0: eligible iff bit 1 of kind[i];  N_i = d * hinum_i - bd * xnum_i,  a'_i = -anum_i,  side +1
+ *   t_i = 0: never eligible.
+ * The ratio of an eligible entry is r_i = N_i / (sense * a'_i) (the true step to the bound is r_i / bd); best[c] is the
+ * eligible i with the smallest r_i compared exactly, among exact ties the smallest (key[i], i), -1 when nothing is eligible;
+ * nties[c] the eligible entries whose ratio equals the minimum, the winner included; neligible[c] the eligible entries;
+ * side[c] the winner's side, 0 with best = -1.  A numerator of any sign is allowed (an x_i outside its bounds gives a
+ * negative ratio).  The winners' slab (all three pointers or none; malloc'ed, slip_hip_free): entries 2c and 2c + 1 are
+ * N_best and a'_best, theta = N_best / (bd * sense * a'_best); both empty with best = -1.  With kind = 1, lonum = 0, bd = 1
+ * this is slip_hip_factor_ratio_test's definition with side -1.
+ *
+ * Bound test.  Problem c: one numerator vector xnum over d.  Vlo_i = s * (d * lonum_i - bd * xnum_i) with bit 0 of kind[i],
+ * else 0; Vhi_i = s * (bd * xnum_i - d * hinum_i) with bit 1, else 0 -- the violations over the common positive denominator
+ * |d| * bd.  v_i = max(Vlo_i, Vhi_i), of side -1 when Vlo_i >= Vhi_i, else +1; entry i is violated iff v_i > 0 (an entry
+ * exactly on its bound is not).  nviolated[c] counts the violated entries; worst[c] is the violated i with the largest v_i,
+ * ties to the smallest (key[i], i), -1 when the vector is feasible; nties[c] the violated entries that share that maximum (0
+ * when feasible); side[c] the side of worst[c] (0 when feasible).  The winners' slab holds nprob entries, v_worst of problem
+ * c as entry c, empty when feasible.
+ *
+ * slip_hip_factor_ratio_test_bounded: right-hand sides, conventions, statuses and refusals are those of
+ * slip_hip_factor_ratio_test (column 2c the x side, 2c + 1 the a side).  slip_hip_factor_bound_test: nprob right-hand sides
+ * as the matching solve takes them.  slip_hip_ratio_test_bounded, slip_hip_bound_test: the handle-less forms on caller slabs
+ * of nprob * n entries, with one nonzero signed d_c per problem as slip_hip_check_solution takes its denominators.  High zero
+ * limbs are allowed in every operand.  The numerators are staged in groups of whole problems under
+ * SLIP_HIP_PRODUCT_STAGE_KB (at least one problem a group; the bound never refuses).
+ *
+ * SLIP_HIP_INCORRECT_INPUT, with nothing written and before any array is read past its end: a NULL bounds, kind or result
+ * array; a kind outside 0..3; a side some kind switches on whose slab is NULL; a slab whose sum |len| exceeds its capacity;
+ * bd <= 0; a zero d_c; a partial winners' triple; everything the unbounded counterpart refuses.  No device:
+ * SLIP_HIP_DEVICE_ERROR.  The handle's solve, solve_transpose, multiply, ratio_test and price return afterwards what they
+ * always did.
+ *
+ * slip_hip_factor_bound_ms: device ms of the handle's last bounded call, out[0] the classify, offset and form passes, out[1]
+ * the selection.  _paths (of the handle's last call; of this thread's last handle-less call): out[0..3] the entries the form
+ * pass settled [0] without a product, [1] in a lane, [2] by a wavefront in registers, [3] by a wavefront through memory;
+ * out[4..7] the four counts of slip_hip_factor_ratio_test_paths for the selection. */
+int slip_hip_factor_ratio_test_bounded(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                                       const slip_hip_bounds *bounds, int32_t sense, const int32_t *key,
+                                       int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side,
+                                       int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+int slip_hip_factor_bound_test(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                               const slip_hip_bounds *bounds, const int32_t *key,
+                               int32_t *worst, int32_t *nties, int32_t *nviolated, int32_t *side,
+                               int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+int slip_hip_ratio_test_bounded(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                                const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                const slip_hip_bounds *bounds, int32_t sense, const int32_t *key,
+                                int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side,
+                                int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+int slip_hip_bound_test(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                        const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                        const slip_hip_bounds *bounds, const int32_t *key,
+                        int32_t *worst, int32_t *nties, int32_t *nviolated, int32_t *side,
+                        int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+int slip_hip_factor_bound_ms(const slip_hip_factor *f, double out[2]);
+int slip_hip_factor_bound_paths(const slip_hip_factor *f, int64_t out[8]);
+int slip_hip_bound_paths(int64_t out[8]);
 
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize

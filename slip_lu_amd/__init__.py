@@ -5,6 +5,7 @@ and the GMP-typed drop-in shim (csrc/libslip_lu_hip.so); this package is the thi
 ctypes layer the tests and bench.py use.
 """
 from . import api  # noqa: F401
-from .api import (Factorization, SlipError, SparseMatrix, check_solution, factorize, ints_to_slab, matgen,  # noqa: F401
-                  multiply_passes, ratio_test, ratio_test_paths, read_triplet, solution_to_double, solution_to_mpfr,
-                  solution_to_mpfr_paths, solution_to_rational, solution_to_rational_paths, write_triplet)
+from .api import (Bounds, Factorization, SlipError, SparseMatrix, bound_paths, bound_test, check_solution, factorize,  # noqa: F401
+                  ints_to_slab, matgen, multiply_passes, ratio_test, ratio_test_bounded, ratio_test_paths, read_triplet,
+                  solution_to_double, solution_to_mpfr, solution_to_mpfr_paths, solution_to_rational,
+                  solution_to_rational_paths, write_triplet)

@@ -18,6 +18,13 @@ class Options(C.Structure):
                 ("workers", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BoundsRec(C.Structure):
+    """slip_hip_bounds"""
+    _fields_ = [("kind", C.c_void_p), ("lolen", C.c_void_p), ("lolimbs", C.c_void_p), ("lo_limbs", C.c_int64),
+                ("hilen", C.c_void_p), ("hilimbs", C.c_void_p), ("hi_limbs", C.c_int64),
+                ("bdlen", C.c_int32), ("bdlimbs", C.c_void_p)]
+
+
 class Info(C.Structure):
     _fields_ = [("n", C.c_int32), ("K", C.c_int32), ("status", C.c_int32), ("window_end", C.c_int32),
                 ("lnz", C.c_int64), ("unz", C.c_int64), ("l_limbs", C.c_int64), ("u_limbs", C.c_int64),
@@ -49,7 +56,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_matrix_multiply_ms", "slip_hip_matrix_destroy", "slip_hip_multiply_passes",
            "slip_hip_ratio_test", "slip_hip_ratio_test_paths", "slip_hip_factor_ratio_test", "slip_hip_factor_ratio_test_ms",
            "slip_hip_factor_ratio_test_paths",
-           "slip_hip_factor_price", "slip_hip_factor_price_ms", "slip_hip_factor_price_paths")
+           "slip_hip_factor_price", "slip_hip_factor_price_ms", "slip_hip_factor_price_paths",
+           "slip_hip_factor_ratio_test_bounded", "slip_hip_factor_bound_test", "slip_hip_ratio_test_bounded", "slip_hip_bound_test",
+           "slip_hip_factor_bound_ms", "slip_hip_factor_bound_paths", "slip_hip_bound_paths")
 
 _libs = {}
 
@@ -180,5 +189,21 @@ def load(path=None):
     lib.slip_hip_factor_price_ms.restype = C.c_int
     lib.slip_hip_factor_price_paths.argtypes = [vp, vp]
     lib.slip_hip_factor_price_paths.restype = C.c_int
+    res4, win = [vp] * 4, [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+    bp = C.POINTER(BoundsRec)
+    lib.slip_hip_factor_ratio_test_bounded.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, bp, C.c_int32, vp] + res4 + win + [vp]
+    lib.slip_hip_factor_ratio_test_bounded.restype = C.c_int
+    lib.slip_hip_factor_bound_test.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, bp, vp] + res4 + win + [vp]
+    lib.slip_hip_factor_bound_test.restype = C.c_int
+    lib.slip_hip_ratio_test_bounded.argtypes = [C.c_int32, C.c_int32] + [vp, vp, i64] * 3 + [bp, C.c_int32, vp] + res4 + win + [vp]
+    lib.slip_hip_ratio_test_bounded.restype = C.c_int
+    lib.slip_hip_bound_test.argtypes = [C.c_int32, C.c_int32] + [vp, vp, i64] * 2 + [bp, vp] + res4 + win + [vp]
+    lib.slip_hip_bound_test.restype = C.c_int
+    lib.slip_hip_factor_bound_ms.argtypes = [vp, vp]
+    lib.slip_hip_factor_bound_ms.restype = C.c_int
+    lib.slip_hip_factor_bound_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_bound_paths.restype = C.c_int
+    lib.slip_hip_bound_paths.argtypes = [vp]
+    lib.slip_hip_bound_paths.restype = C.c_int
     _libs[path] = lib
     return lib

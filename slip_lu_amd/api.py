@@ -274,6 +274,92 @@ def ratio_test_paths(lib_path=None):
     return _paths(_lib.load(lib_path).slip_hip_ratio_test_paths)
 
 
+class Bounds:
+    """A set of bounds l_i = lo_i / den <= x_i <= hi_i / den for the bounded selections (slip_hip_bounds): kind[i] bit 0 = a
+    finite lower bound, bit 1 = a finite upper bound; lo and hi are (signed limb counts, limbs) slabs of n entries (the entry of
+    a side kind switches off is ignored; a side nothing switches on may be None); den a positive Python int."""
+
+    def __init__(self, n, kind, lo=None, hi=None, den=1):
+        self.n = int(n)
+        self.kind = np.ascontiguousarray(kind, dtype=np.int32)
+        if self.kind.size != self.n:
+            raise ValueError("Bounds: kind must hold n entries")
+        self.lo = None if lo is None else _limb_arrays(*lo)
+        self.hi = None if hi is None else _limb_arrays(*hi)
+        for s in (self.lo, self.hi):
+            if s is not None and s[0].size != self.n:
+                raise ValueError("Bounds: lo and hi must hold n entries")
+        self.bdlen, self.bd = _int_limbs(den)
+        self.rec = _lib.BoundsRec()
+        self.rec.kind = self.kind.ctypes.data
+        if self.lo is not None:
+            self.rec.lolen, self.rec.lolimbs, self.rec.lo_limbs = self.lo[0].ctypes.data, self.lo[1].ctypes.data, self.lo[2]
+        if self.hi is not None:
+            self.rec.hilen, self.rec.hilimbs, self.rec.hi_limbs = self.hi[0].ctypes.data, self.hi[1].ctypes.data, self.hi[2]
+        if den != 1:
+            self.rec.bdlen, self.rec.bdlimbs = self.bdlen, self.bd.ctypes.data
+
+    def ref(self, n):
+        if self.n != n:
+            raise ValueError("Bounds: made for another n")
+        return C.byref(self.rec)
+
+
+def _bounded_results(lib, rc, where, res, nprob, winners, per, pl, px, nl):
+    if rc:
+        raise SlipError(rc, where)
+    res = tuple(r[:nprob] for r in res)
+    return res + _take_slab(lib, pl, px, nl, per * nprob) if winners else res
+
+
+def _bounded_slabs(mode, n, nprob, slabs, bounds, sense, key, winners, lib_path):
+    lib = _lib.load(lib_path)
+    n, nprob = int(n), int(nprob)
+    args, keep = [], []
+    for t, (lens, limbs) in enumerate(slabs):
+        lens, limbs, cap = _limb_arrays(lens, limbs)
+        if n >= 1 and nprob >= 1 and lens.size != (nprob if t == len(slabs) - 1 else n * nprob):
+            raise ValueError("bounded selection: x and a must hold n*nprob entries, d nprob")
+        keep.append((lens, limbs))
+        args += [lens.ctypes.data, limbs.ctypes.data, cap]
+    key = _ratio_key(n, key) if n >= 1 else None
+    res = [np.zeros(max(nprob, 1), np.int32) for _ in range(4)]
+    pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+    outs = (C.byref(pl), C.byref(px), C.byref(nl)) if winners else (None, None, None)
+    tail = [None if key is None else key.ctypes.data] + [r.ctypes.data for r in res] + list(outs) + [None]
+    if mode == 0:
+        rc = lib.slip_hip_ratio_test_bounded(n, nprob, *args, bounds.ref(n), int(sense), *tail)
+    else:
+        rc = lib.slip_hip_bound_test(n, nprob, *args, bounds.ref(n), *tail)
+    return _bounded_results(lib, rc, "slip_hip_bound_test" if mode else "slip_hip_ratio_test_bounded", res, nprob, winners,
+                            1 if mode else 2, pl, px, nl)
+
+
+def ratio_test_bounded(n, xlen, xlimbs, alen, alimbs, dlen, dlimbs, bounds, nprob=1, sense=1, key=None, winners=False, lib_path=None):
+    """The bounded ratio test on caller slabs (slip_hip_ratio_test_bounded): x and a hold nprob * n numerators over one nonzero
+    signed d per problem.  With t_i = sense * sign(d) * a_i an entry heads for its lower bound (t_i > 0, bit 0 of kind, N_i =
+    den * x_i - d * lo_i, a'_i = a_i, side -1) or its upper bound (t_i < 0, bit 1, N_i = d * hi_i - den * x_i, a'_i = -a_i, side
+    +1); the smallest N_i / (sense * a'_i) wins, exact ties to the smallest (key[i], i).  Returns (best, nties, neligible,
+    side), int32[nprob] each, with winners=True also (wlen, wlimbs): N_best and a'_best as entries 2c and 2c + 1."""
+    return _bounded_slabs(0, n, nprob, ((xlen, xlimbs), (alen, alimbs), (dlen, dlimbs)), bounds, sense, key, winners, lib_path)
+
+
+def bound_test(n, xlen, xlimbs, dlen, dlimbs, bounds, nprob=1, key=None, winners=False, lib_path=None):
+    """The exact feasibility test on caller slabs (slip_hip_bound_test): per problem the entry that violates a bound the most
+    (v_i = max(s * (d * lo_i - den * x_i), s * (den * x_i - d * hi_i)) > 0, s = sign(d)), ties to the smallest (key[i], i).
+    Returns (worst, nties, nviolated, side), worst -1 when the vector is feasible; with winners=True also (wlen, wlimbs), entry
+    c the violation v_worst of problem c."""
+    return _bounded_slabs(1, n, nprob, ((xlen, xlimbs), (dlen, dlimbs)), bounds, 1, key, winners, lib_path)
+
+
+def bound_paths(lib_path=None):
+    """this thread's last handle-less bounded call: entries formed [without a product, in a lane, by a wavefront in registers,
+    by a wavefront through memory], then the four counts of ratio_test_paths for its selection"""
+    out = np.zeros(8, np.int64)
+    _lib.load(lib_path).slip_hip_bound_paths(out.ctypes.data)
+    return [int(v) for v in out]
+
+
 class SparseMatrix:
     """An m x ncols integer matrix resident on one GPU without a factorisation (handle of slip_hip_matrix_*): the CSC as
     Factorization() takes it, a repeated row keeping its LAST value."""
@@ -689,6 +775,46 @@ class Factorization:
         """the last ratio_test: [eligible entries, entries the bound pass left to the exact pass, exact comparisons that formed
         products, of those the comparisons on the memory path]"""
         return _paths(self.lib.slip_hip_factor_ratio_test_paths, self.h)
+
+    def _bounded(self, mode, blen, blimbs, bounds, nprob, transpose, sense, key, winners, stream):
+        nprob, per = int(nprob), 1 if mode else 2
+        blen, blimbs, _ = _rhs(self.n, blen, blimbs, per * nprob if nprob >= 1 else nprob)
+        key = _ratio_key(self.n, key)
+        res = [np.zeros(max(nprob, 1), np.int32) for _ in range(4)]
+        pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+        outs = (C.byref(pl), C.byref(px), C.byref(nl)) if winners else (None, None, None)
+        tail = [None if key is None else key.ctypes.data] + [r.ctypes.data for r in res] + list(outs) + [C.c_void_p(stream or 0)]
+        head = (self.h, int(bool(transpose)), nprob, blen.ctypes.data, blimbs.ctypes.data, bounds.ref(self.n))
+        if mode == 0:
+            rc = self.lib.slip_hip_factor_ratio_test_bounded(*head, int(sense), *tail)
+        else:
+            rc = self.lib.slip_hip_factor_bound_test(*head, *tail)
+        return _bounded_results(self.lib, rc, "slip_hip_factor_bound_test" if mode else "slip_hip_factor_ratio_test_bounded",
+                                res, nprob, winners, per, pl, px, nl)
+
+    def ratio_test_bounded(self, blen, blimbs, bounds, nprob=1, transpose=False, sense=1, key=None, winners=False, stream=None):
+        """Solve and select on the device with bounds on the basic variables (slip_hip_factor_ratio_test_bounded): the
+        right-hand sides and index conventions of `ratio_test`, the definition of the module's `ratio_test_bounded` with d =
+        det.  Returns (best, nties, neligible, side[, wlen, wlimbs])."""
+        return self._bounded(0, blen, blimbs, bounds, nprob, transpose, sense, key, winners, stream)
+
+    def bound_test(self, blen, blimbs, bounds, nprob=1, transpose=False, key=None, winners=False, stream=None):
+        """Solve and test feasibility on the device (slip_hip_factor_bound_test): nprob right-hand sides as the matching solve
+        takes them, the definition of the module's `bound_test` with d = det.  Returns (worst, nties, nviolated, side[, wlen,
+        wlimbs])."""
+        return self._bounded(1, blen, blimbs, bounds, nprob, transpose, 1, key, winners, stream)
+
+    def bound_ms(self):
+        """device ms of the last bounded call: [the classify, offset and form passes, the selection]"""
+        out = np.zeros(2, np.float64)
+        self.lib.slip_hip_factor_bound_ms(self.h, out.ctypes.data)
+        return [float(v) for v in out]
+
+    def bound_paths(self):
+        """the last bounded call, as the module's `bound_paths`"""
+        out = np.zeros(8, np.int64)
+        self.lib.slip_hip_factor_bound_paths(self.h, out.ctypes.data)
+        return [int(v) for v in out]
 
     def price(self, M, blen, blimbs, nprob=1, sides=1, cost=None, sense=1, key=None, winners=False, stream=None):
         """Solve, multiply and select on the device (slip_hip_factor_price): b holds sides * nprob right-hand sides as

@@ -1522,6 +1522,331 @@ static void slip_price_body(SlipPriceArgs A)
     if (A.phase == 1 && lane == 0 && wm) slip_atomic_max_i32(A.wmax, (int32_t) wm);
 }
 
+/* Bounds in the exact selections (slip_hip_factor_ratio_test_bounded, slip_hip_factor_bound_test and their handle-less
+ * forms): the numerators slip_ratio_kernel selects on, formed from a solve's output and a set of bounds
+ * l_i = lonum_i / bd, u_i = hinum_i / bd.  With s = sign(d_c) and
+ *     G(b) = s * bd * x_i - |d_c| * b
+ * mode 0 (ratio test) stages s * N_i: G(lonum_i) for an entry heading for its lower bound (sense * s * a_i > 0, bit 0 of
+ * kind), -G(hinum_i) for one heading for its upper bound (sense * s * a_i < 0, bit 1), and the a record sense * |a_i| on
+ * a_i's own limbs, so that the selection runs with asense = sense and no flip whatever the sign of d_c (one d per problem
+ * in the handle-less form); mode 1 (bound test) stages v_i = max(Vlo_i, Vhi_i), Vlo_i = -G(lonum_i), Vhi_i = G(hinum_i)
+ * (the lower side on equality), over the denominator record 1 when v_i > 0 and 0 otherwise.  Entry i of problem c is
+ * entry c * xstride + i of x (c * astride + i of a) and entry c * n + i of every array written here; its bounds and kind are
+ * those of idx = oidx[i].
+ *
+ * phase 0, classify and size, one lane per entry (a wave's 64 entries are of one problem): cls = the sides to form (bit 0
+ *   lower, bit 1 upper; 0: not eligible) | the path << 2, w = the digits the entry owns in the staging slab (W =
+ *   max(dig(bd) + dig(x), dig(d) + dig(bound)) + 1 with an absent factor's term 0; dig(x) on path 0), the a record in mode
+ *   0; the widest w and the widest w of the wave paths go to wmax[0], wmax[1], one atomic each per wave.
+ * phase 1, the lane pass, one lane per entry: path 1, both products of at most four digits, finished in 128-bit pieces.
+ * phase 2, the wave pass, one wave per entry, wave-uniform: path 0 (bd = 1 and every bound that counts is zero) copies |x|;
+ *   path 2, both products of at most 256 digits by their operands' bit lengths (the class D = 1 .. 4 is kept in cls >> 4),
+ *   forms them in registers (slip_check_mac_reg) and G in sign and magnitude: a comparison and a subtraction, or a sum
+ *   whose carry is digit 64 D; path 3 forms G modulo B^Wp, Wp = (W + 1) & ~1, in the entry's own staging region with
+ *   the products in this wave's scratch (2 * wcap digits: a product, and the second side of a bound test), the top bit
+ *   being the sign as in slip_product_kernel.
+ *   Every path leaves the magnitude in whole limbs and the trimmed signed digit count in rlen.
+ * phase 3, one lane per problem: side[c] from cls at the winner (pos: the entry of a reported index), and the records of the
+ *   winners' numerators with the sign of d_c taken out again.
+ * paths: entries by the path that formed them. */
+struct SlipBoundArgs {
+    int32_t n, nprob, phase, mode, sense, bdunit;
+    int64_t xstride, astride;
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* x: signed digit counts, limb offsets   */
+    const int32_t *alen; const int64_t *aoff; const uint64_t *alimbs;              /* a likewise (mode 0)                    */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* d_c: entry c                           */
+    const int32_t *oidx, *pos;                                                     /* reported index of entry i; its inverse */
+    const int32_t *kind;                                                           /* by reported index, as lo and hi        */
+    const int32_t *lolen; const int64_t *looff; const uint64_t *lolimbs;
+    const int32_t *hilen; const int64_t *hioff; const uint64_t *hilimbs;
+    int32_t bddig; const uint64_t *bdlimbs;                                        /* bd > 0, trimmed                        */
+    int32_t *cls, *w, *wmax;
+    int32_t *alen2; int64_t *aoff2;                                                /* the a records of the selection         */
+    const int64_t *soff; uint64_t *stage; int32_t *rlen;                           /* staging slab, signed digit counts      */
+    dig_t *scratch; int32_t wcap;                                                  /* path 3: 2 * wcap digits per wave       */
+    const int32_t *best; int32_t *side;                                            /* phase 3, per problem                   */
+    int32_t *wnlen, *walen; int64_t *wnoff, *waoff;                                /* the winners' records, or NULL          */
+    unsigned long long *paths;
+};
+
+/* an operand: its trimmed digits and its sign */
+struct SlipBoundOp { const dig_t *p; int l, s; };
+SLIP_DEV SlipBoundOp slip_bound_op(const int32_t *len, const int64_t *off, const uint64_t *limbs, int64_t e)
+{
+    SlipBoundOp o;
+    const int32_t sl = len[e];
+    o.p = (const dig_t *)(limbs + off[e]);
+    o.l = slip_trim_digits(o.p, slip_abs(sl));
+    o.s = o.l == 0 ? 0 : (sl < 0 ? -1 : 1);
+    return o;
+}
+
+/* the operands of entry i of problem c whose sides are `sides` */
+struct SlipBoundEnt { SlipBoundOp X, BD, Dn, LO, HI; int sides, mode; };
+SLIP_DEV SlipBoundEnt slip_bound_ent(const SlipBoundArgs &A, int c, int i, int sides)
+{
+    SlipBoundEnt E;
+    const int idx = A.oidx ? A.oidx[i] : i;
+    E.sides = sides; E.mode = A.mode;
+    E.X = slip_bound_op(A.xlen, A.xoff, A.xlimbs, (int64_t) c * A.xstride + i);
+    E.Dn = slip_bound_op(A.dlen, A.doff, A.dlimbs, c);
+    E.BD.p = (const dig_t *) A.bdlimbs; E.BD.l = A.bddig; E.BD.s = 1;
+    E.LO.p = (const dig_t *) 0; E.LO.l = 0; E.LO.s = 0; E.HI = E.LO;
+    if (sides & 1) E.LO = slip_bound_op(A.lolen, A.looff, A.lolimbs, idx);
+    if (sides & 2) E.HI = slip_bound_op(A.hilen, A.hioff, A.hilimbs, idx);
+    return E;
+}
+
+/* side q (1 lower, 2 upper) of an entry: the value staged is s1 * bd * |x| + s2 * |d| * |b|, b = *B */
+SLIP_DEV void slip_bound_terms(const SlipBoundEnt &E, int q, const SlipBoundOp **B, int *s1, int *s2)
+{
+    const int f = ((q == 1) == (E.mode == 1)) ? -1 : 1;
+    *B = q == 1 ? &E.LO : &E.HI;
+    *s1 = f * E.Dn.s * E.X.s; *s2 = -f * (*B)->s;
+}
+
+/* is the signed number (sg2, |.| = m2) greater than (sg1, m1); cm = the comparison of the magnitudes m2 against m1 */
+SLIP_DEV int slip_bound_greater(int sg2, int sg1, int cm) { return sg2 != sg1 ? sg2 > sg1 : (sg1 > 0 ? cm > 0 : sg1 < 0 ? cm < 0 : 0); }
+
+/* lane pass: an operand of at most four digits as one 128-bit number */
+SLIP_DEV slip_u128 slip_bound_load128(const SlipBoundOp &o)
+{
+    slip_u128 v = 0;
+    for (int k = o.l - 1; k >= 0; k--) v = (v << 32) | o.p[k];
+    return v;
+}
+
+/* lane pass: side q as sign, 128-bit magnitude and the carry above it */
+SLIP_DEV void slip_bound_eval_lane(const SlipBoundEnt &E, int q, int *sg, slip_u128 *mag, uint32_t *top)
+{
+    const SlipBoundOp *Bv; int s1, s2;
+    slip_bound_terms(E, q, &Bv, &s1, &s2);
+    const slip_u128 P = s1 ? slip_bound_load128(E.X) * slip_bound_load128(E.BD) : 0, Q = s2 ? slip_bound_load128(E.Dn) * slip_bound_load128(*Bv) : 0;
+    *top = 0;
+    if (s1 == s2 || !s1 || !s2) { *mag = P + Q; *top = *mag < P ? 1u : 0u; *sg = s1 ? s1 : s2; }
+    else if (P >= Q) { *mag = P - Q; *sg = P == Q ? 0 : s1; }
+    else { *mag = Q - P; *sg = s2; }
+}
+
+/* sign(P - Q) of two register numbers' magnitudes */
+template <int D> SLIP_DEV int slip_bound_cmp_reg(const WR<D> &P, const WR<D> &Q)
+{
+#pragma unroll
+    for (int q = D - 1; q >= 0; q--) {
+        const uint64_t df = slip_ballot(P.d[q] != Q.d[q]);
+        if (df) {
+            const int t = 63 - slip_clz64(df);
+            return slip_readlane(P.d[q], t) > slip_readlane(Q.d[q], t) ? 1 : -1;
+        }
+    }
+    return 0;
+}
+
+/* the product of two operands that fits 64*D digits, the shorter one walked */
+template <int D> SLIP_DEV WR<D> slip_bound_mul_reg(const SlipBoundOp &a, const SlipBoundOp &b)
+{
+    return a.l <= b.l ? slip_check_mac_reg<D>(wr_zero<D>(), a.p, a.l, b.p, b.l, 0) : slip_check_mac_reg<D>(wr_zero<D>(), b.p, b.l, a.p, a.l, 0);
+}
+
+/* wave pass, registers: side q, both products below B^(64*D) (the class is chosen from their bit lengths), in sign and
+ * magnitude: *sg the sign, *top the digit 64*D of the magnitude (the carry of a sum: 0 or 1), the digits below it returned */
+template <int D> SLIP_DEV WR<D> slip_bound_eval_reg(const SlipBoundEnt &E, int q, int *sg, uint32_t *top)
+{
+    const SlipBoundOp *Bv; int s1, s2;
+    slip_bound_terms(E, q, &Bv, &s1, &s2);
+    const WR<D> P = s1 ? slip_bound_mul_reg<D>(E.X, E.BD) : wr_zero<D>(), Q = s2 ? slip_bound_mul_reg<D>(E.Dn, *Bv) : wr_zero<D>();
+    *top = 0;
+    if (!s1 || !s2 || s1 == s2) {
+        const WR<D> R = wr_addsub<D>(P, Q, 0);
+        *top = slip_bound_cmp_reg<D>(R, P) < 0 ? 1u : 0u;          /* the sum wrapped */
+        *sg = s1 ? s1 : s2;
+        return R;
+    }
+    const int cm = slip_bound_cmp_reg<D>(P, Q);
+    *sg = cm > 0 ? s1 : cm < 0 ? s2 : 0;
+    return cm >= 0 ? wr_addsub<D>(P, Q, 1) : wr_addsub<D>(Q, P, 1);
+}
+
+/* wave pass, registers: the entry's value into out in whole limbs; its signed digit count, *side the side it is of */
+template <int D> SLIP_DEV int slip_bound_entry_reg(const SlipBoundEnt &E, dig_t *out, int *side)
+{
+    int sg, q = (E.sides & 1) ? 1 : 2;
+    uint32_t top;
+    WR<D> V = slip_bound_eval_reg<D>(E, q, &sg, &top);
+    if (E.sides == 3) {
+        int sg2; uint32_t top2;
+        const WR<D> V2 = slip_bound_eval_reg<D>(E, 2, &sg2, &top2);
+        const int cm = top2 != top ? (top2 > top ? 1 : -1) : slip_bound_cmp_reg<D>(V2, V);
+        if (slip_bound_greater(sg2, sg, cm)) { V = V2; sg = sg2; top = top2; q = 2; }
+    }
+    /* (a carry means a product of 64*D digits: the entry owns at least 64*D + 2 digits of the staging slab) */
+    const int len = top ? 64 * D + 1 : wr_len<D>(V);
+    wr_store<D>(out, V, top ? 64 * D : (len + 1) & ~1);
+    if (top && slip_lane() < 2) out[64 * D + slip_lane()] = slip_lane() == 0 ? 1u : 0u;
+    *side = q;
+    return sg < 0 ? -len : len;
+}
+
+/* wave pass, memory: side q modulo B^Wp into dst (prod: Wp digits of scratch); its signed digit count */
+SLIP_DEV int slip_bound_eval_wide(const SlipBoundEnt &E, int q, int Wp, dig_t *dst, dig_t *prod)
+{
+    const SlipBoundOp *Bv; int s1, s2;
+    slip_bound_terms(E, q, &Bv, &s1, &s2);
+    for (int k = slip_lane(); k < Wp; k += SLIP_WAVE) dst[k] = 0u;
+    slip_wave_sync();
+    if (s1) { wb_mul_lo(prod, E.X.p, E.X.l, E.BD.p, E.BD.l, Wp); wb_addsub(dst, dst, Wp, prod, Wp, Wp, s1 < 0); }
+    if (s2) { wb_mul_lo(prod, E.Dn.p, E.Dn.l, Bv->p, Bv->l, Wp); wb_addsub(dst, dst, Wp, prod, Wp, Wp, s2 < 0); }
+    const int neg = (int)(dst[Wp - 1] >> 31);
+    if (neg) wb_addsub(dst, (const dig_t *) 0, 1, dst, Wp, Wp, 1, 0u);
+    const int len = wb_len(dst, Wp);
+    return neg ? -len : len;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_bound_kernel(SlipBoundArgs A)
+#else
+static void slip_bound_body(SlipBoundArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    if (A.phase <= 1) {
+        const int64_t rpp = ((int64_t) A.n + SLIP_WAVE - 1) / SLIP_WAVE, rounds = rpp * A.nprob;
+        uint32_t wall = 0, wwave = 0;
+        unsigned long long total = 0;
+        for (int64_t r = wave0; r < rounds; r += nwaves) {
+            const int c = (int)(r / rpp);
+            const int64_t i = (r - (int64_t) c * rpp) * SLIP_WAVE + lane, e = (int64_t) c * A.n + i;
+            if (A.phase == 1) {
+                const int code = i < A.n ? A.cls[e] : 0, take = (code & 3) != 0 && ((code >> 2) & 3) == 1;
+                if (take) {
+                    const SlipBoundEnt E = slip_bound_ent(A, c, (int) i, code & 3);
+                    int sg, q = (code & 1) ? 1 : 2;
+                    slip_u128 mag; uint32_t top;
+                    slip_bound_eval_lane(E, q, &sg, &mag, &top);
+                    if ((code & 3) == 3) {
+                        int sg2; slip_u128 mag2; uint32_t top2;
+                        slip_bound_eval_lane(E, 2, &sg2, &mag2, &top2);
+                        const int cm = top2 != top ? (top2 > top ? 1 : -1) : mag2 != mag ? (mag2 > mag ? 1 : -1) : 0;
+                        if (slip_bound_greater(sg2, sg, cm)) { sg = sg2; mag = mag2; top = top2; q = 2; }
+                    }
+                    const uint64_t l0 = (uint64_t) mag, l1 = (uint64_t)(mag >> 64);
+                    const int len = top ? 9 : l1 ? (l1 >> 32 ? 8 : 7) : l0 ? (l0 >> 32 ? 6 : 5) : 4;      /* digits + 4 */
+                    uint64_t *out = A.stage + A.soff[e];
+                    if (len > 4) out[0] = l0;
+                    if (len > 6) out[1] = l1;
+                    if (len > 8) out[2] = top;
+                    A.rlen[e] = sg < 0 ? -(len - 4) : len - 4;
+                    if (A.mode) { A.alen2[e] = sg > 0 ? 1 : 0; A.aoff2[e] = 0; A.cls[e] = q | (1 << 2); }
+                }
+                total += (unsigned long long) slip_popc64(slip_ballot(take));
+                continue;
+            }
+            uint32_t W = 0, Ww = 0;
+            if (i < A.n) {
+                const int idx = A.oidx ? A.oidx[i] : (int) i, k = A.kind[idx];
+                const int32_t sd = A.dlen[c];
+                int sides = k & 3;
+                if (!A.mode) {
+                    const int64_t ea = (int64_t) c * A.astride + i;
+                    const SlipBoundOp Av = slip_bound_op(A.alen, A.aoff, A.alimbs, ea);
+                    const int t = A.sense * (sd < 0 ? -1 : 1) * Av.s;
+                    sides = t > 0 ? (k & 1) : t < 0 ? (k & 2) : 0;
+                    A.alen2[e] = sides ? A.sense * Av.l : 0; A.aoff2[e] = A.aoff[ea];
+                } else { A.alen2[e] = 0; A.aoff2[e] = 0; }
+                int code = 0;
+                if (sides) {
+                    const SlipBoundEnt E = slip_bound_ent(A, c, (int) i, sides);
+                    const int lb = E.LO.l > E.HI.l ? E.LO.l : E.HI.l;
+                    int path = 0;
+                    if (A.bdunit && lb == 0) W = (uint32_t) E.X.l;
+                    else {
+                        /* pd: the digits neither product exceeds, from the operands' bit lengths */
+                        const int blo = wb_bits(E.LO.p, E.LO.l), bhi = wb_bits(E.HI.p, E.HI.l);
+                        const int w1 = E.X.l ? E.BD.l + E.X.l : 0, w2 = lb ? E.Dn.l + lb : 0;
+                        const int p1 = E.X.l ? (wb_bits(E.BD.p, E.BD.l) + wb_bits(E.X.p, E.X.l) + 31) >> 5 : 0;
+                        const int p2 = lb ? (wb_bits(E.Dn.p, E.Dn.l) + (blo > bhi ? blo : bhi) + 31) >> 5 : 0, pd = p1 > p2 ? p1 : p2;
+                        W = (uint32_t)((w1 > w2 ? w1 : w2) + 1);
+                        path = w1 <= 4 && w2 <= 4 ? 1 : pd <= 256 ? 2 : 3;
+                        if (path == 2) code = ((pd + 63) >> 6) << 4;
+                    }
+                    if (path == 3) Ww = W;
+                    code |= sides | (path << 2);
+                }
+                A.cls[e] = code; A.w[e] = (int32_t) W; A.rlen[e] = 0;
+            }
+            W = slip_wave_max_u32(W); Ww = slip_wave_max_u32(Ww);
+            if (W > wall) wall = W;
+            if (Ww > wwave) wwave = Ww;
+        }
+        if (A.phase == 0 && lane == 0) {
+            if (wall) slip_atomic_max_i32(A.wmax + 0, (int32_t) wall);
+            if (wwave) slip_atomic_max_i32(A.wmax + 1, (int32_t) wwave);
+        }
+        if (A.phase == 1 && lane == 0 && total) slip_atomic_add_u64(A.paths + 1, total);
+        return;
+    }
+    if (A.phase == 2) {
+        dig_t *prod = A.scratch ? A.scratch + wave0 * 2 * (int64_t) A.wcap : (dig_t *) 0, *alt = prod ? prod + A.wcap : (dig_t *) 0;
+        const int64_t items = (int64_t) A.n * A.nprob;
+        unsigned long long cnt[4] = {0, 0, 0, 0};
+        for (int64_t e = wave0; e < items; e += nwaves) {
+            const int code = A.cls[e], sides = code & 3, path = (code >> 2) & 3, cls = code >> 4;
+            if (!sides || path == 1) continue;
+            const int c = (int)(e / A.n), i = (int)(e - (int64_t) c * A.n);
+            const SlipBoundEnt E = slip_bound_ent(A, c, i, sides);
+            const int W = A.w[e];
+            dig_t *out = (dig_t *)(A.stage + A.soff[e]);
+            int len, q = (sides & 1) ? 1 : 2;
+            if (path == 0) {
+                /* every bound that counts is zero and bd = 1: the value is s1 * |x| */
+                const SlipBoundOp *Bv; int sg, s2;
+                slip_bound_terms(E, q, &Bv, &sg, &s2);
+                if (sides == 3 && -sg > sg) { sg = -sg; q = 2; }
+                wb_copy_pad(out, E.X.p, E.X.l);
+                len = sg < 0 ? -E.X.l : E.X.l;
+            } else if (path == 2 && cls == 1) len = slip_bound_entry_reg<1>(E, out, &q);
+            else if (path == 2 && cls == 2) len = slip_bound_entry_reg<2>(E, out, &q);
+            else if (path == 2 && cls == 3) len = slip_bound_entry_reg<3>(E, out, &q);
+            else if (path == 2) len = slip_bound_entry_reg<4>(E, out, &q);
+            else {
+                const int Wp = (W + 1) & ~1;                       /* at most wcap: the host sized it from wmax */
+                len = slip_bound_eval_wide(E, q, Wp, out, prod);
+                if (sides == 3) {
+                    const int len2 = slip_bound_eval_wide(E, 2, Wp, alt, prod);
+                    const int sg = len > 0 ? 1 : len < 0 ? -1 : 0, sg2 = len2 > 0 ? 1 : len2 < 0 ? -1 : 0;
+                    if (slip_bound_greater(sg2, sg, wb_cmp(alt, slip_abs(len2), out, slip_abs(len)))) {
+                        for (int k = lane; k < Wp; k += SLIP_WAVE) out[k] = alt[k];
+                        slip_wave_sync();
+                        len = len2; q = 2;
+                    }
+                }
+            }
+            if (lane == 0) {
+                A.rlen[e] = len;
+                if (A.mode) { A.alen2[e] = len > 0 ? 1 : 0; A.aoff2[e] = 0; A.cls[e] = q | (path << 2); }
+            }
+            cnt[path]++;
+        }
+        if (lane == 0) for (int k = 0; k < 4; k++) if (cnt[k]) slip_atomic_add_u64(A.paths + k, cnt[k]);
+        return;
+    }
+    const int64_t rounds = ((int64_t) A.nprob + SLIP_WAVE - 1) / SLIP_WAVE;
+    for (int64_t r = wave0; r < rounds; r += nwaves) {
+        const int64_t c = r * SLIP_WAVE + lane;
+        if (c >= A.nprob) continue;
+        const int32_t b = A.best[c];
+        const int64_t e = c * A.n + (b < 0 ? 0 : (A.pos ? A.pos[b] : b));
+        const int s = A.mode || A.dlen[c] > 0 ? 1 : -1;
+        A.side[c] = b < 0 ? 0 : ((A.cls[e] & 3) == 1 ? -1 : 1);
+        if (A.wnlen) {
+            A.wnlen[c] = b < 0 ? 0 : s * A.rlen[e]; A.wnoff[c] = b < 0 ? 0 : A.soff[e];
+            if (A.walen) { A.walen[c] = b < 0 ? 0 : s * A.alen2[e]; A.waoff[c] = b < 0 ? 0 : A.aoff2[e]; }
+        }
+    }
+}
+
 /* The transposed view of complete factors (slip_hip_factor_solve_transpose).  With M = A(row_perm, q) the matrix that was
  * factorised, every entry of a REF factorisation is a minor of M (L(i,k) = det M[{0..k-1,i},{0..k}], U(k,j) =
  * det M[{0..k},{0..k-1,j}], rho_k = det M[0..k,0..k]); transposing swaps the rows and columns of every minor, so the REF
@@ -1897,6 +2222,9 @@ struct slip_hip_factor {
     double ratio_ms; int64_t ratio_paths[4];
     /* slip_hip_factor_price: device time of the last call by pass, the path counts of its selections */
     double price_ms[4]; int64_t price_paths[4];
+    /* slip_hip_factor_ratio_test_bounded / _bound_test: device time of the last call (the form passes, the selection), the
+     * entries by the path that formed them and the path counts of the selection */
+    double bound_ms[2]; int64_t bound_paths[8];
     /* slip_hip_factor_rewind / _replace_column: the host copy of q; the storage of the resident A -- annz / alimbs are its
      * LIVE entries and limbs, Acap_nz / Acap_nl what dAi, dAlen, dAoff / dAlimbs can hold, Anl_used the limbs of the slab
      * handed out (live ones and the dead ones of replaced columns: new limbs are appended there), A0_nz / A0_nl the initial
@@ -4700,6 +5028,348 @@ extern "C" int slip_hip_factor_ratio_test_paths(const slip_hip_factor *f, int64_
 {
     if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
     memcpy(out, f->ratio_paths, sizeof f->ratio_paths);
+    return SLIP_HIP_OK;
+}
+
+/* ---- bounds in the exact selections: the ratio test of a basis with boxed variables and the most violated bound, the
+ * numerators formed on the device from a solve's output and a set of bounds, the selection slip_ratio_kernel's as it stands
+ * (no counterpart in the reference; kernel: slip_bound_kernel) ---- */
+
+/* the counts of this thread's last handle-less bounded call */
+static thread_local int64_t slip_bound_paths_last[8];
+
+/* a set of bounds checked and laid out on the host (bdl: the limbs of bd, `one` when the caller gave none) */
+struct SlipHostBounds { SlipSlab lo, hi; int has_lo, has_hi; int32_t bddig; uint64_t one; };
+static void host_bounds_free(SlipHostBounds *h) { slab_free(&h->lo); slab_free(&h->hi); }
+static int host_bounds(int32_t n, const slip_hip_bounds *B, SlipHostBounds *h)
+{
+    memset(h, 0, sizeof *h);
+    h->one = 1;
+    if (!B || !B->kind) return SLIP_HIP_INCORRECT_INPUT;
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t k = B->kind[i];
+        if (k < 0 || k > 3) return SLIP_HIP_INCORRECT_INPUT;
+        h->has_lo |= k & 1; h->has_hi |= k & 2;
+    }
+    if ((h->has_lo && (!B->lolen || !B->lolimbs)) || (h->has_hi && (!B->hilen || !B->hilimbs))) return SLIP_HIP_INCORRECT_INPUT;
+    if (B->bdlimbs) {
+        if (B->bdlen <= 0) return SLIP_HIP_INCORRECT_INPUT;
+        h->bddig = limb_digits(B->bdlimbs, B->bdlen);
+        if (h->bddig == 0) return SLIP_HIP_INCORRECT_INPUT;
+    } else h->bddig = 1;
+    int rc = h->has_lo ? slab_prepare(n, B->lolen, B->lolimbs, B->lo_limbs, &h->lo) : 0;
+    if (!rc && h->has_hi) rc = slab_prepare(n, B->hilen, B->hilimbs, B->hi_limbs, &h->hi);
+    if (rc) host_bounds_free(h);
+    return rc;
+}
+
+/* the device operands of a bounded selection: x (and a, mode 0) of problem c from entry c * stride on, d_c, the map from an
+ * entry to the index reported and its inverse (both NULL: the identity) */
+struct SlipBoundIn {
+    int32_t n, nprob, mode, sense;
+    SlipDevRecs x, a, d; int64_t xstride, astride;
+    const int32_t *oidx, *pos;
+};
+
+/* one bounded selection on the device.  res: 4 * nprob host integers (best, nties, the count, side); with wlen_out the
+ * winners' slab (mode 0: N and a' of every problem, a' read from I.a.limbs; mode 1: v).  ms: the form passes, the selection. */
+static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const SlipHostBounds &hb, const int32_t *key, int32_t *res,
+                      int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, hipStream_t stream, double ms[2], int64_t paths[8])
+{
+    const int32_t n = I.n, nprob = I.nprob;
+    const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE, per = I.mode ? 1 : 2;
+    int32_t *dkind = NULL, *dlol = NULL, *dhil = NULL, *dcls = NULL, *dw = NULL, *drl = NULL, *dal2 = NULL, *dwmax = NULL, *dsel = NULL, *dwn = NULL;
+    int64_t *dloo = NULL, *dhio = NULL, *dso = NULL, *dao2 = NULL, *dwo = NULL;
+    uint64_t *dlov = NULL, *dhiv = NULL, *dbd = NULL;
+    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, *bsum = NULL, hpaths[4] = {0, 0, 0, 0};
+    int32_t *hres = (int32_t *) malloc((size_t) nprob * 16), hwmax[2] = {0, 0};
+    std::vector<int32_t> wl; std::vector<uint64_t> wv;
+    int rc = !hres ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    ms[0] = ms[1] = 0; memset(paths, 0, 8 * sizeof(int64_t));
+    /* the bounds; dbd: the limbs of bd, then one limb holding 1 (the denominator record of a violated entry) */
+    const int64_t bdn = ((int64_t) hb.bddig + 1) >> 1;
+    A_(dev_alloc(&dkind, n)); UP_(dkind, B->kind, (size_t) n * 4);
+    A_(dev_alloc(&dbd, bdn + 1)); UP_(dbd, B->bdlimbs ? B->bdlimbs : &hb.one, (size_t) bdn * 8); UP_(dbd + bdn, &hb.one, 8);
+    if (hb.has_lo) {
+        A_(dev_alloc(&dlol, n)); A_(dev_alloc(&dloo, n)); A_(dev_alloc(&dlov, hb.lo.total));
+        UP_(dlol, hb.lo.dig, (size_t) n * 4); UP_(dloo, hb.lo.off, (size_t) n * 8); UP_(dlov, B->lolimbs, (size_t) hb.lo.total * 8);
+    }
+    if (hb.has_hi) {
+        A_(dev_alloc(&dhil, n)); A_(dev_alloc(&dhio, n)); A_(dev_alloc(&dhiv, hb.hi.total));
+        UP_(dhil, hb.hi.dig, (size_t) n * 4); UP_(dhio, hb.hi.off, (size_t) n * 8); UP_(dhiv, B->hilimbs, (size_t) hb.hi.total * 8);
+    }
+    A_(dev_alloc(&dcls, ne)); A_(dev_alloc(&dw, ne)); A_(dev_alloc(&drl, ne)); A_(dev_alloc(&dso, ne));
+    A_(dev_alloc(&dal2, ne)); A_(dev_alloc(&dao2, ne)); A_(dev_alloc(&dwmax, 2)); A_(dev_alloc(&dpaths, 4));
+    A_(dev_alloc(&dsel, 2 * (int64_t) nprob));
+    if (wlen_out) { A_(dev_alloc(&dwn, 2 * (int64_t) nprob)); A_(dev_alloc(&dwo, 2 * (int64_t) nprob)); }
+    HIP_(hipMemsetAsync(dwmax, 0, 8, stream)); HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
+    SlipBoundArgs A; memset(&A, 0, sizeof A);
+    A.n = n; A.mode = I.mode; A.sense = I.sense; A.xstride = I.xstride; A.astride = I.astride;
+    A.xlimbs = I.x.limbs; A.alimbs = I.a.limbs; A.dlimbs = I.d.limbs; A.oidx = I.oidx; A.pos = I.pos;
+    A.kind = dkind; A.lolen = dlol; A.looff = dloo; A.lolimbs = dlov; A.hilen = dhil; A.hioff = dhio; A.hilimbs = dhiv;
+    A.bddig = hb.bddig; A.bdlimbs = dbd; A.bdunit = hb.bddig == 1 && (B->bdlimbs ? B->bdlimbs[0] : 1) == 1;
+    A.wmax = dwmax; A.paths = dpaths;
+    /* the problems c0 .. c0 + nv of every per-problem and per-entry array */
+    auto slice = [&](int64_t c0, int64_t nv, int phase) {
+        A.nprob = (int32_t) nv; A.phase = phase;
+        A.xlen = I.x.len + c0 * I.xstride; A.xoff = I.x.off + c0 * I.xstride;
+        A.alen = I.a.len ? I.a.len + c0 * I.astride : NULL; A.aoff = I.a.off ? I.a.off + c0 * I.astride : NULL;
+        A.dlen = I.d.len + c0; A.doff = I.d.off + c0;
+        A.cls = dcls + c0 * n; A.w = dw + c0 * n; A.rlen = drl + c0 * n; A.soff = dso + c0 * n;
+        A.alen2 = dal2 + c0 * n; A.aoff2 = dao2 + c0 * n;
+    };
+    if (!rc) {                                             /* the classes and widths of all entries, the widest of them */
+        SlipTimed timed;
+        slice(0, nprob, 0);
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(bound, wave_blocks(rpp * nprob), stream, A));
+        A_(timed.end(stream, &ms[0]));
+    }
+    DOWN_(hwmax, dwmax, 8);
+    const int64_t wcap = hwmax[0] > 1 ? ((int64_t) hwmax[0] + 1) & ~(int64_t) 1 : 2, scap = ((int64_t) hwmax[1] + 1) & ~(int64_t) 1;
+    if (!rc && wcap > (1 << 28)) rc = SLIP_HIP_OUT_OF_MEMORY;
+    int64_t group = rc ? 1 : product_stage_limbs() / ((int64_t) n * (wcap / 2));       /* problems staged together */
+    if (group < 1) group = 1;
+    if (group > nprob) group = nprob;
+    const int64_t wblocks = hwmax[1] > 256 ? fit_scratch(wave_blocks(ne), 2 * scap) : wave_blocks(ne), sblocks = offscan_blocks((int64_t) n * group);
+    A_(dev_alloc(&bsum, sblocks));
+    if (hwmax[1] > 256) { A_(dev_alloc(&dscr, wblocks * SERVICE_WAVES * 2 * scap)); A.scratch = dscr; A.wcap = (int32_t) scap; }
+    for (int64_t c0 = 0; c0 < nprob && !rc; c0 += group) {
+        const int64_t nv = c0 + group <= nprob ? group : nprob - c0, cnt = (int64_t) n * nv;
+        uint64_t *dstage = NULL; int64_t total = 0;
+        double t = 0;
+        {                                                  /* the staging offsets from the widths */
+            SlipTimed timed;
+            A_(timed.begin(stream));
+            A_(offscan_run(cnt, dw + c0 * n, dso + c0 * n, bsum, sblocks, stream));
+            A_(timed.end(stream, &t));
+            ms[0] += t;
+        }
+        A_(offscan_total(bsum, sblocks, &total, stream));
+        if (!rc && total > cnt * (wcap / 2)) rc = SLIP_HIP_DEVICE_ERROR;           /* (the widths' bound: the host's own figure) */
+        A_(dev_alloc(&dstage, total));
+        if (!rc) {                                         /* the numerators into the staging slab: the lane pass, the wave pass */
+            SlipTimed timed;
+            A.stage = dstage;
+            A_(timed.begin(stream));
+            slice(c0, nv, 1); A_(SERVICE_LAUNCH(bound, wave_blocks(rpp * nv), stream, A));
+            slice(c0, nv, 2); A_(SERVICE_LAUNCH(bound, wave_blocks(cnt) < wblocks ? wave_blocks(cnt) : wblocks, stream, A));
+            A_(timed.end(stream, &t));
+            ms[0] += t;
+        }
+        /* the selection on the group's (N, a') records */
+        int64_t gp[4] = {0, 0, 0, 0};
+        SlipRatioArgs R; memset(&R, 0, sizeof R);
+        R.n = n; R.nprob = (int32_t) nv; R.pstride = n; R.oidx = I.oidx;
+        R.xlen = drl + c0 * n; R.xoff = dso + c0 * n; R.xlimbs = dstage;
+        R.alen = dal2 + c0 * n; R.aoff = dao2 + c0 * n; R.alimbs = I.mode ? dbd + bdn : I.a.limbs;
+        R.asense = I.mode ? 1 : I.sense; R.xflip = I.mode;
+        t = 0;
+        A_(ratio_core(R, key, hres + c0, hres + nprob + c0, hres + 2 * (int64_t) nprob + c0, NULL, NULL, NULL, stream, &t, gp));
+        if (!rc) { ms[1] += t; for (int k = 0; k < 4; k++) paths[4 + k] += gp[k]; }
+        /* the winners' sides and, on request, their records */
+        UP_(dsel, hres + c0, (size_t) nv * 4);
+        if (!rc) {
+            slice(c0, nv, 3);
+            A.best = dsel; A.side = dsel + nprob;
+            if (wlen_out) { A.wnlen = dwn; A.wnoff = dwo; A.walen = I.mode ? NULL : dwn + nprob; A.waoff = I.mode ? NULL : dwo + nprob; }
+            A_(SERVICE_LAUNCH(bound, service_blocks(nv), stream, A));
+            HIP_(hipStreamSynchronize(stream));
+        }
+        DOWN_(hres + 3 * (int64_t) nprob + c0, dsel + nprob, (size_t) nv * 4);
+        if (wlen_out) {
+            int32_t *nl = NULL, *al = NULL; uint64_t *nvl = NULL, *avl = NULL; int64_t nn = 0, an = 0;
+            A_(pack_download(nv, dwn, dwo, dstage, 0, &nl, &nvl, &nn, stream));
+            if (!I.mode) A_(pack_download(nv, dwn + nprob, dwo + nprob, I.a.limbs, 0, &al, &avl, &an, stream));
+            if (!rc) {
+                int64_t on = 0, oa = 0;
+                for (int64_t c = 0; c < nv; c++) {
+                    const int64_t ln = nl[c] < 0 ? -nl[c] : nl[c];
+                    wl.push_back(nl[c]); wv.insert(wv.end(), nvl + on, nvl + on + ln); on += ln;
+                    if (!I.mode) {
+                        const int64_t la = al[c] < 0 ? -al[c] : al[c];
+                        wl.push_back(al[c]); wv.insert(wv.end(), avl + oa, avl + oa + la); oa += la;
+                    }
+                }
+            }
+            free(nl); free(al); free(nvl); free(avl);
+        }
+        dev_free(dstage);
+    }
+    DOWN_(hpaths, dpaths, 32);
+    int32_t *ol = NULL; uint64_t *ov = NULL;
+    if (!rc && wlen_out) {
+        ol = (int32_t *) malloc((size_t)(per * nprob) * 4); ov = (uint64_t *) malloc((wv.size() > 0 ? wv.size() : 1) * 8);
+        if (!ol || !ov) { free(ol); free(ov); rc = SLIP_HIP_OUT_OF_MEMORY; }
+        else {
+            memcpy(ol, wl.data(), (size_t)(per * nprob) * 4);
+            if (!wv.empty()) memcpy(ov, wv.data(), wv.size() * 8);
+        }
+    }
+    if (!rc) {
+        memcpy(res, hres, (size_t) nprob * 16);
+        for (int k = 0; k < 4; k++) paths[k] = (int64_t) hpaths[k];
+        if (wlen_out) { *wlen_out = ol; *wlimbs_out = ov; *wnl_out = (int64_t) wv.size(); }
+    }
+    free(hres);
+    dev_free(dkind); dev_free(dlol); dev_free(dhil); dev_free(dloo); dev_free(dhio); dev_free(dlov); dev_free(dhiv); dev_free(dbd);
+    dev_free(dcls); dev_free(dw); dev_free(drl); dev_free(dso); dev_free(dal2); dev_free(dao2); dev_free(dwmax); dev_free(dpaths);
+    dev_free(dsel); dev_free(dwn); dev_free(dwo); dev_free(bsum); dev_free(dscr);
+    return rc;
+}
+
+/* the 4 * nprob results of bound_core into the caller's four arrays */
+static void bound_results(const int32_t *res, int32_t nprob, int32_t *r0, int32_t *r1, int32_t *r2, int32_t *r3)
+{
+    memcpy(r0, res, (size_t) nprob * 4); memcpy(r1, res + nprob, (size_t) nprob * 4);
+    memcpy(r2, res + 2 * (size_t) nprob, (size_t) nprob * 4); memcpy(r3, res + 3 * (size_t) nprob, (size_t) nprob * 4);
+}
+
+/* both fused forms: mode 0 the bounded ratio test on 2 * nprob right-hand sides, mode 1 the bound test on nprob */
+static int bound_on_handle(slip_hip_factor *f, int mode, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                           const slip_hip_bounds *bounds, int32_t sense, const int32_t *key,
+                           int32_t *r0, int32_t *r1, int32_t *r2, int32_t *r3,
+                           int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    if (!f || nprob < 1 || nprob > (1 << 29) || (sense != 1 && sense != -1) || !blen || !blimbs || !r0 || !r1 || !r2 || !r3 ||
+        !bounds || !bounds->kind)
+        return SLIP_HIP_INCORRECT_INPUT;
+    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (!transpose && f->factors_only) return SLIP_HIP_INCORRECT_INPUT;             /* no q behind such a handle */
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
+    if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
+    const int32_t n = f->n, per = mode ? 1 : 2;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipHostBounds hb;
+    TRY_(host_bounds(n, bounds, &hb));
+    SlipSolveOut o;
+    int rc = solve_device(f, transpose, per * nprob, blen, blimbs, stream, &o);
+    if (rc) { host_bounds_free(&hb); return rc; }
+    if (wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
+    int32_t *ddlen = NULL, *doidx = NULL, *dpos = NULL, *hidx = NULL, *res = (int32_t *) malloc((size_t) nprob * 16); int64_t *ddoff = NULL;
+    int32_t dmaxdig = 0;
+    if (!res) rc = SLIP_HIP_OUT_OF_MEMORY;
+    A_(det_records(f, nprob, &ddlen, &ddoff, &dmaxdig));
+    if (!rc && transpose) {                                /* position p of the transposed solve is row i, pinv[i] = p */
+        hidx = (int32_t *) malloc((size_t) n * 4);
+        if (!hidx) rc = SLIP_HIP_OUT_OF_MEMORY;
+        else for (int32_t i = 0; i < n; i++) hidx[f->tpinv[i]] = i;
+        A_(dev_alloc(&doidx, n)); UP_(doidx, hidx, (size_t) n * 4);
+        A_(dev_alloc(&dpos, n)); UP_(dpos, f->tpinv, (size_t) n * 4);
+    }
+    SlipBoundIn I; memset(&I, 0, sizeof I);
+    I.n = n; I.nprob = nprob; I.mode = mode; I.sense = sense; I.oidx = doidx; I.pos = dpos;
+    I.x.len = o.olen; I.x.off = o.ooff; I.x.limbs = o.olimbs; I.xstride = (int64_t) per * n;
+    if (!mode) { I.a.len = o.olen + n; I.a.off = o.ooff + n; I.a.limbs = o.olimbs; I.astride = 2 * (int64_t) n; }
+    I.d.len = ddlen; I.d.off = ddoff; I.d.limbs = f->P.Llimbs;
+    double ms[2]; int64_t paths[8];
+    A_(bound_core(I, bounds, hb, key, res, wlen_out, wlimbs_out, wnl_out, stream, ms, paths));
+    if (!rc) {
+        bound_results(res, nprob, r0, r1, r2, r3);
+        memcpy(f->bound_ms, ms, sizeof ms); memcpy(f->bound_paths, paths, sizeof paths);
+    }
+    free(hidx); free(res); dev_free(doidx); dev_free(dpos); dev_free(ddlen); dev_free(ddoff);
+    solve_out_free(&o);
+    host_bounds_free(&hb);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_ratio_test_bounded(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                                                  const slip_hip_bounds *bounds, int32_t sense, const int32_t *key,
+                                                  int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side,
+                                                  int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    return bound_on_handle(f, 0, transpose, nprob, blen, blimbs, bounds, sense, key, best, nties, neligible, side, wlen_out, wlimbs_out, wnl_out, stream_v);
+}
+
+extern "C" int slip_hip_factor_bound_test(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                                          const slip_hip_bounds *bounds, const int32_t *key,
+                                          int32_t *worst, int32_t *nties, int32_t *nviolated, int32_t *side,
+                                          int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    return bound_on_handle(f, 1, transpose, nprob, blen, blimbs, bounds, 1, key, worst, nties, nviolated, side, wlen_out, wlimbs_out, wnl_out, stream_v);
+}
+
+/* both handle-less forms (mode 1: no a) */
+static int bound_on_slabs(int mode, int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                          const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                          const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                          const slip_hip_bounds *bounds, int32_t sense, const int32_t *key,
+                          int32_t *r0, int32_t *r1, int32_t *r2, int32_t *r3,
+                          int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    if (n <= 0 || nprob < 1 || nprob > (1 << 29) || (sense != 1 && sense != -1) || !xlen || !xlimbs || (!mode && (!alen || !alimbs)) ||
+        !dlen || !dlimbs || !r0 || !r1 || !r2 || !r3 || !bounds || !bounds->kind)
+        return SLIP_HIP_INCORRECT_INPUT;
+    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    TRY_(need_device());
+    const int64_t ne = (int64_t) n * nprob;
+    SlipHostBounds hb;
+    TRY_(host_bounds(n, bounds, &hb));
+    SlipSlab xs, as, ds; memset(&xs, 0, sizeof xs); memset(&as, 0, sizeof as); memset(&ds, 0, sizeof ds);
+    int32_t *dxl = NULL, *dal = NULL, *ddl = NULL, *res = NULL; int64_t *dxo = NULL, *dao = NULL, *ddo = NULL; uint64_t *dxv = NULL, *dav = NULL, *ddv = NULL;
+    /* (every slab is checked against its capacity before a limb of it is read) */
+    int rc = ratio_upload(nprob, dlen, dlimbs, d_limbs, &ds, &ddl, &ddo, &ddv);
+    for (int32_t c = 0; c < nprob && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    A_(ratio_upload(ne, xlen, xlimbs, x_limbs, &xs, &dxl, &dxo, &dxv));
+    if (!mode) A_(ratio_upload(ne, alen, alimbs, a_limbs, &as, &dal, &dao, &dav));
+    if (!rc && !(res = (int32_t *) malloc((size_t) nprob * 16))) rc = SLIP_HIP_OUT_OF_MEMORY;
+    if (!rc && wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
+    SlipBoundIn I; memset(&I, 0, sizeof I);
+    I.n = n; I.nprob = nprob; I.mode = mode; I.sense = sense; I.xstride = n; I.astride = n;
+    I.x.len = dxl; I.x.off = dxo; I.x.limbs = dxv; I.a.len = dal; I.a.off = dao; I.a.limbs = dav; I.d.len = ddl; I.d.off = ddo; I.d.limbs = ddv;
+    double ms[2]; int64_t paths[8];
+    A_(bound_core(I, bounds, hb, key, res, wlen_out, wlimbs_out, wnl_out, (hipStream_t) stream_v, ms, paths));
+    if (!rc) {
+        bound_results(res, nprob, r0, r1, r2, r3);
+        memcpy(slip_bound_paths_last, paths, sizeof paths);
+    }
+    free(res);
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dal); dev_free(dao); dev_free(dav); dev_free(ddl); dev_free(ddo); dev_free(ddv);
+    slab_free(&xs); slab_free(&as); slab_free(&ds);
+    host_bounds_free(&hb);
+    return rc;
+}
+
+extern "C" int slip_hip_ratio_test_bounded(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                           const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                                           const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                           const slip_hip_bounds *bounds, int32_t sense, const int32_t *key,
+                                           int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side,
+                                           int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    return bound_on_slabs(0, n, nprob, xlen, xlimbs, x_limbs, alen, alimbs, a_limbs, dlen, dlimbs, d_limbs, bounds, sense, key,
+                          best, nties, neligible, side, wlen_out, wlimbs_out, wnl_out, stream_v);
+}
+
+extern "C" int slip_hip_bound_test(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                   const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                   const slip_hip_bounds *bounds, const int32_t *key,
+                                   int32_t *worst, int32_t *nties, int32_t *nviolated, int32_t *side,
+                                   int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    return bound_on_slabs(1, n, nprob, xlen, xlimbs, x_limbs, NULL, NULL, 0, dlen, dlimbs, d_limbs, bounds, 1, key,
+                          worst, nties, nviolated, side, wlen_out, wlimbs_out, wnl_out, stream_v);
+}
+
+extern "C" int slip_hip_factor_bound_ms(const slip_hip_factor *f, double out[2])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->bound_ms, sizeof f->bound_ms);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_bound_paths(const slip_hip_factor *f, int64_t out[8])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->bound_paths, sizeof f->bound_paths);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_bound_paths(int64_t out[8])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_bound_paths_last, sizeof slip_bound_paths_last);
     return SLIP_HIP_OK;
 }
 
