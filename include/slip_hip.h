@@ -605,6 +605,63 @@ int slip_hip_factor_bound_ms(const slip_hip_factor *f, double out[2]);
 int slip_hip_factor_bound_paths(const slip_hip_factor *f, int64_t out[8]);
 int slip_hip_bound_paths(int64_t out[8]);
 
+/* Nonbasic states and reference weights in exact pricing: the entering side of a simplex step on a boxed LP, the
+ * counterpart of the bounded ratio test above.  Operands as slip_hip_factor_price takes them (M with m == n, nside * nprob
+ * right-hand sides, optional g, sense, optional key[ncols]); X_j and A_j are formed exactly as there.  With s = sign(det),
+ * v_j = X_j / det and alpha_j = A_j / det, and two more operands shared by all problems of a call, as key is:
+ *   state[ncols]: 0 never eligible, 1 at its lower bound, 2 at its upper bound, 3 free (any other value is refused);
+ *   weights: an optional limb slab of ncols integers w_j > 0 (reference weights: Devex, steepest edge), nside 1 only.
+ *
+ * nside 1, primal pricing: column j is eligible iff sense * v_j < 0 (state 1), sense * v_j > 0 (state 2), v_j != 0 (state
+ * 3).  Its score is |v_j| without weights and v_j^2 / w_j with them; best[c] is the eligible j with the largest score
+ * compared exactly, among exact ties the smallest (key[j], j), -1 when nothing is eligible (optimality).  With sense = -1
+ * and the reduced cost d_j = -v_j, state 1 is "d_j < 0" (slip_hip_factor_price's correspondence).
+ * nside 2, dual ratio test: with t_j = sense * s * A_j column j is eligible iff t_j > 0 (state 1), t_j < 0 (state 2),
+ * t_j != 0 (state 3); best[c] is the eligible j with the smallest r_j = X_j / (sense * A_j), an exact rational of any sign,
+ * ties by (key[j], j).  With state = 1 everywhere this is slip_hip_factor_price's nside = 2 definition.
+ * nties[c] counts the eligible columns whose score (ratio) equals the winner's, the winner included; neligible[c] the
+ * eligible columns; vsign[c] is the sign of v_best, 0 with best = -1 (a free column needs it: which way to move).  The
+ * winners' slab (all three pointers or none; malloc'ed, slip_hip_free): entries 2c and 2c + 1 are X_best and A_best with
+ * their own signs, the second empty with nside 1, both empty with best = -1.  Squares never leave the device.
+ *
+ * slip_hip_factor_price_states is fused as slip_hip_factor_price is: nothing of y, X, A or X^2 is downloaded.
+ * slip_hip_price_select is the handle-less form on caller slabs of nprob * ncols entries over one nonzero signed d_c per
+ * problem (as slip_hip_ratio_test_bounded takes its d; d_c stands for det); a is required iff nside = 2.  High zero limbs
+ * are allowed in every operand.  The squares are staged in groups of whole problems under SLIP_HIP_PRODUCT_STAGE_KB (at
+ * least one problem a group; the bound never refuses).
+ *
+ * SLIP_HIP_INCORRECT_INPUT, with nothing written and before any array is read past its end: a NULL state; a state outside
+ * 0..3; exactly one of wlen / wlimbs NULL; a weights slab whose sum |len| exceeds w_limbs; any w_j <= 0 (all-zero limbs
+ * included, also for a column of state 0); weights with nside = 2; a zero d_c; a missing with nside = 2 or given with nside
+ * = 1 (handle-less form); a partial winners' triple; everything slip_hip_factor_price refuses.  A broken handle, or no
+ * device: SLIP_HIP_DEVICE_ERROR.  The handle's solve, solve_transpose, multiply, ratio_test, price and bounded calls return
+ * afterwards what they always did.
+ *
+ * slip_hip_factor_price_states_ms: device ms of the handle's last call, out[0] the classify, offset and square passes,
+ * out[1] the selection.  _paths (of the handle's last call; of this thread's last slip_hip_price_select): out[0..3] the
+ * eligible entries [0] settled without a product (no weights, or nside 2), [1] squared in a lane, [2] squared by a
+ * wavefront in registers, [3] squared by a wavefront through memory; out[4..7] the four counts of
+ * slip_hip_factor_ratio_test_paths for the selection. */
+int slip_hip_factor_price_states(slip_hip_factor *f, slip_hip_matrix *M, int32_t nside, int32_t nprob,
+                                 const int32_t *blen, const uint64_t *blimbs,                 /* nside*nprob right-hand sides */
+                                 const int32_t *glen, const uint64_t *glimbs, int64_t g_limbs, /* optional: nprob cost vectors of ncols */
+                                 const int32_t *state,                                        /* ncols entries, 0..3 */
+                                 const int32_t *wlen, const uint64_t *wlimbs, int64_t w_limbs, /* optional: ncols weights > 0 */
+                                 int32_t sense, const int32_t *key,
+                                 int32_t *best, int32_t *nties, int32_t *neligible, int32_t *vsign,
+                                 int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+int slip_hip_price_select(int32_t ncols, int32_t nprob, int32_t nside,
+                          const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                          const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                          const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                          const int32_t *state, const int32_t *wlen, const uint64_t *wlimbs, int64_t w_limbs,
+                          int32_t sense, const int32_t *key,
+                          int32_t *best, int32_t *nties, int32_t *neligible, int32_t *vsign,
+                          int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream);
+int slip_hip_factor_price_states_ms(const slip_hip_factor *f, double out[2]);
+int slip_hip_factor_price_states_paths(const slip_hip_factor *f, int64_t out[8]);
+int slip_hip_price_select_paths(int64_t out[8]);
+
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize
  * creates and destroys one per call): at most SLIP_HIP_POOL_MB megabytes (environment, default 32768; 0 = no pool).  This

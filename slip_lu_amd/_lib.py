@@ -58,7 +58,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_ratio_test_paths",
            "slip_hip_factor_price", "slip_hip_factor_price_ms", "slip_hip_factor_price_paths",
            "slip_hip_factor_ratio_test_bounded", "slip_hip_factor_bound_test", "slip_hip_ratio_test_bounded", "slip_hip_bound_test",
-           "slip_hip_factor_bound_ms", "slip_hip_factor_bound_paths", "slip_hip_bound_paths")
+           "slip_hip_factor_bound_ms", "slip_hip_factor_bound_paths", "slip_hip_bound_paths",
+           "slip_hip_factor_price_states", "slip_hip_price_select", "slip_hip_factor_price_states_ms",
+           "slip_hip_factor_price_states_paths", "slip_hip_price_select_paths")
 
 _libs = {}
 
@@ -205,5 +207,16 @@ def load(path=None):
     lib.slip_hip_factor_bound_paths.restype = C.c_int
     lib.slip_hip_bound_paths.argtypes = [vp]
     lib.slip_hip_bound_paths.restype = C.c_int
+    states = [vp, vp, vp, i64, C.c_int32, vp] + res4 + win + [vp]        # state, the weights, sense, key, the results, stream
+    lib.slip_hip_factor_price_states.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, i64] + states
+    lib.slip_hip_factor_price_states.restype = C.c_int
+    lib.slip_hip_price_select.argtypes = [C.c_int32] * 3 + [vp, vp, i64] * 3 + states
+    lib.slip_hip_price_select.restype = C.c_int
+    lib.slip_hip_factor_price_states_ms.argtypes = [vp, vp]
+    lib.slip_hip_factor_price_states_ms.restype = C.c_int
+    lib.slip_hip_factor_price_states_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_price_states_paths.restype = C.c_int
+    lib.slip_hip_price_select_paths.argtypes = [vp]
+    lib.slip_hip_price_select_paths.restype = C.c_int
     _libs[path] = lib
     return lib

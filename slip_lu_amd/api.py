@@ -360,6 +360,62 @@ def bound_paths(lib_path=None):
     return [int(v) for v in out]
 
 
+def _states_args(ncols, state, weights, where):
+    """the states and optional weights of a pricing with states as the arguments of the C ABI (and the arrays behind them)"""
+    state = np.ascontiguousarray(state, dtype=np.int32)
+    if state.size != ncols:
+        raise ValueError(f"{where}: state must hold ncols entries")
+    if weights is None:
+        return (state,), [state.ctypes.data, None, None, 0]
+    wlen, wlimbs, wcap = _limb_arrays(*weights)
+    if wlen.size != ncols:
+        raise ValueError(f"{where}: weights must hold ncols entries")
+    return (state, wlen, wlimbs), [state.ctypes.data, wlen.ctypes.data, wlimbs.ctypes.data, wcap]
+
+
+def price_select(ncols, xlen, xlimbs, dlen, dlimbs, state, alen=None, alimbs=None, weights=None, nprob=1, sides=1, sense=1,
+                 key=None, winners=False, lib_path=None):
+    """Pricing with nonbasic states on caller slabs (slip_hip_price_select): x (and a, iff sides=2) hold nprob * ncols
+    numerators X_j (A_j) over one nonzero signed d per problem; state[j] is 0 (never eligible), 1 (at lower), 2 (at upper) or
+    3 (free); weights is None or a (signed limb counts, limbs) slab of ncols positive integers (sides=1 only).  With v_j =
+    X_j / d: sides=1 picks the eligible j (sense * v_j < 0 at lower, > 0 at upper, v_j != 0 free) with the largest |v_j|, or
+    v_j^2 / w_j with weights; sides=2 the eligible j (t_j = sense * sign(d) * A_j > 0 at lower, < 0 at upper, != 0 free) with
+    the smallest X_j / (sense * A_j).  Exact ties go to the smallest (key[j], j).  Returns (best, nties, neligible, vsign),
+    int32[nprob] each, vsign the sign of v_best; with winners=True also (wlen, wlimbs): X_best and A_best of problem c as
+    entries 2c and 2c + 1 (sides=1: the second one empty), both empty where best is -1."""
+    lib = _lib.load(lib_path)
+    ncols, nprob, sides = int(ncols), int(nprob), int(sides)
+    xlen, xlimbs, xcap = _limb_arrays(xlen, xlimbs)
+    dlen, dlimbs, dcap = _limb_arrays(dlen, dlimbs)
+    if ncols >= 1 and nprob >= 1 and (xlen.size != ncols * nprob or dlen.size != nprob):
+        raise ValueError("price_select: x must hold ncols*nprob entries, d nprob")
+    args = [xlen.ctypes.data, xlimbs.ctypes.data, xcap]
+    if alen is None and alimbs is None:
+        args += [None, None, 0]
+    else:
+        alen, alimbs, acap = _limb_arrays(alen, alimbs)
+        if ncols >= 1 and nprob >= 1 and alen.size != ncols * nprob:
+            raise ValueError("price_select: a must hold ncols*nprob entries")
+        args += [alen.ctypes.data, alimbs.ctypes.data, acap]
+    args += [dlen.ctypes.data, dlimbs.ctypes.data, dcap]
+    keep, sargs = _states_args(max(ncols, 0), state, weights, "price_select")
+    key = _ratio_key(ncols, key) if ncols >= 1 else None
+    res = [np.zeros(max(nprob, 1), np.int32) for _ in range(4)]
+    pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+    outs = (C.byref(pl), C.byref(px), C.byref(nl)) if winners else (None, None, None)
+    rc = lib.slip_hip_price_select(ncols, nprob, sides, *args, *sargs, int(sense), None if key is None else key.ctypes.data,
+                                   *[r.ctypes.data for r in res], *outs, None)
+    return _bounded_results(lib, rc, "slip_hip_price_select", res, nprob, winners, 2, pl, px, nl)
+
+
+def price_select_paths(lib_path=None):
+    """this thread's last price_select: eligible entries [settled without a product, squared in a lane, squared by a
+    wavefront in registers, squared by a wavefront through memory], then the four counts of ratio_test_paths for its selection"""
+    out = np.zeros(8, np.int64)
+    _lib.load(lib_path).slip_hip_price_select_paths(out.ctypes.data)
+    return [int(v) for v in out]
+
+
 class SparseMatrix:
     """An m x ncols integer matrix resident on one GPU without a factorisation (handle of slip_hip_matrix_*): the CSC as
     Factorization() takes it, a repeated row keeping its LAST value."""
@@ -859,6 +915,44 @@ class Factorization:
     def price_paths(self):
         """the last price: the four counts of ratio_test_paths over its selections"""
         return _paths(self.lib.slip_hip_factor_price_paths, self.h)
+
+    def price_states(self, M, blen, blimbs, state, weights=None, nprob=1, sides=1, cost=None, sense=1, key=None, winners=False,
+                     stream=None):
+        """Solve, multiply and select on the device with a state per column of M (slip_hip_factor_price_states): the
+        operands, X_j and A_j of `price`, the states, weights and definition of the module's `price_select` with d = det.
+        Returns (best, nties, neligible, vsign[, wlen, wlimbs]); nothing of y, X, A or the squares is downloaded otherwise."""
+        nprob, sides = int(nprob), int(sides)
+        ncols = M.ncols
+        blen, blimbs, _ = _rhs(self.n, blen, blimbs, sides * nprob if nprob >= 1 and sides in (1, 2) else 0)
+        if cost is None:
+            g = (None, None, 0)
+        else:
+            glen, glimbs, gcap = _limb_arrays(*cost)
+            if nprob >= 1 and glen.size != nprob * ncols:
+                raise ValueError("price_states: cost must hold nprob*ncols entries")
+            g = (glen.ctypes.data, glimbs.ctypes.data, gcap)
+        keep, sargs = _states_args(ncols, state, weights, "price_states")
+        key = _ratio_key(ncols, key)
+        res = [np.zeros(max(nprob, 1), np.int32) for _ in range(4)]
+        pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+        outs = (C.byref(pl), C.byref(px), C.byref(nl)) if winners else (None, None, None)
+        rc = self.lib.slip_hip_factor_price_states(self.h, M.h, sides, nprob, blen.ctypes.data, blimbs.ctypes.data, *g, *sargs,
+                                                   int(sense), None if key is None else key.ctypes.data,
+                                                   *[r.ctypes.data for r in res], *outs, C.c_void_p(stream or 0))
+        return _bounded_results(self.lib, rc, "slip_hip_factor_price_states", res, nprob, winners, 2, pl, px, nl)
+
+    def price_states_ms(self):
+        """device ms of the last price_states: [the classify, offset and square passes, the selection] (the substitution:
+        solve_transpose_ms)"""
+        out = np.zeros(2, np.float64)
+        self.lib.slip_hip_factor_price_states_ms(self.h, out.ctypes.data)
+        return [float(v) for v in out]
+
+    def price_states_paths(self):
+        """the last price_states, as the module's `price_select_paths`"""
+        out = np.zeros(8, np.int64)
+        self.lib.slip_hip_factor_price_states_paths(self.h, out.ctypes.data)
+        return [int(v) for v in out]
 
     def solve_transpose_ms(self):
         """(device ms of the last transposed solve's substitution kernels, ms of that call's view build: 0 when it was reused)"""

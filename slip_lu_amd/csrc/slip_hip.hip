@@ -1847,6 +1847,164 @@ static void slip_bound_body(SlipBoundArgs A)
     }
 }
 
+/* Nonbasic states and reference weights in exact pricing (slip_hip_factor_price_states, slip_hip_price_select):
+ * the records slip_ratio_kernel selects on, formed from the numerators X_j (and A_j, nside 2) of nprob problems over one
+ * nonzero signed d_c each, the state of every column (0 never eligible, 1 at its lower bound, 2 at its upper bound, 3 free)
+ * and, with nside 1, optional weights w_j > 0.  With s = sign(d_c):
+ *   nside 1: t_j = sense * s * X_j; eligible iff t_j < 0 (state 1), t_j > 0 (state 2), t_j != 0 (state 3).  Without weights
+ *     the x record is |X_j| on X_j's own limbs over the one-limb constant 1 (length 0 when not eligible); with weights it is
+ *     X_j^2 in a staging slab of its own over w_j's record.  Either way the selection takes the largest ratio (xflip = 1,
+ *     asense = 1).
+ *   nside 2: t_j = sense * s * A_j; eligible iff t_j > 0 (state 1), t_j < 0 (state 2), t_j != 0 (state 3).  The a record is
+ *     sense * |A_j| on A_j's limbs (length 0 when not eligible), the x record X_j with the sign of X_j / (sense * A_j): the
+ *     selection runs with asense = sense and no flip whatever the signs of d_c and A_j.
+ * Entry j of problem c is entry c * xstride + j of x (c * astride + j of a) and entry c * n + j of every array written here.
+ *
+ * phase 0, classify and size, one lane per entry (a wave's 64 entries are of one problem): the selection's records; with
+ *   weights cls = the path of an eligible entry (1 the lane pass; 1 + D, D = 1 .. 4, a square of at most 64 D digits by the
+ *   BIT length of X_j, a p-bit number's square having at most 2 p bits; 6 through memory; 0 not eligible) and w = 2 dig(X_j),
+ *   the digits it owns in the squares' slab, the widest of them to wmax[0], one atomic per wave.  Without weights no limb
+ *   moves and this phase is the whole job.
+ * phase 1, the lane pass, one lane per entry: |X_j| of at most two digits, squared in the lane as one 128-bit product.
+ * phase 2, the wave pass, one wavefront per entry, wave-uniform: the operand times itself in registers (slip_check_mac_reg)
+ *   when the square fits 256 digits, through memory (wb_mul_lo straight into the entry's own region of the slab: no scratch)
+ *   above.  Every path leaves whole limbs and the trimmed digit count in xlen2.
+ * phase 3, one lane per problem: vsign[c] from the ORIGINAL record of X_best and the sign of d_c, and the records of the
+ *   winners' X and A as they came in.
+ * paths: eligible entries [0] settled without a product, [1] squared in a lane, [2] in registers, [3] through memory. */
+struct SlipStatesArgs {
+    int32_t n, nprob, phase, nside, sense, weighted;
+    int64_t xstride, astride;
+    const int32_t *xlen; const int64_t *xoff; const uint64_t *xlimbs;              /* X: signed digit counts, limb offsets   */
+    const int32_t *alen; const int64_t *aoff; const uint64_t *alimbs;              /* A likewise (nside 2)                   */
+    const int32_t *dlen;                                                           /* d_c: entry c (its sign is all it takes) */
+    const int32_t *state;                                                          /* by column                              */
+    const int32_t *wtlen; const int64_t *wtoff;                                    /* the weights' records, by column        */
+    int32_t *cls, *w, *wmax;                                                       /* (with weights)                         */
+    int32_t *xlen2, *alen2; int64_t *xoff2, *aoff2;                                /* the records of the selection           */
+    const int64_t *soff; uint64_t *stage;                                          /* the squares' slab                      */
+    const int32_t *best; int32_t *vsign;                                           /* phase 3, per problem                   */
+    int32_t *wxlen, *walen; int64_t *wxoff, *waoff;                                /* the winners' records, or NULL          */
+    unsigned long long *paths;
+};
+
+/* wave pass, registers: the square of X, at most 64*D digits, into out in whole limbs; its digit count */
+template <int D> SLIP_DEV int slip_states_square_reg(const SlipBoundOp &X, dig_t *out)
+{
+    const WR<D> V = slip_check_mac_reg<D>(wr_zero<D>(), X.p, X.l, X.p, X.l, 0);
+    const int len = wr_len<D>(V);
+    wr_store<D>(out, V, (len + 1) & ~1);
+    return len;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_states_kernel(SlipStatesArgs A)
+#else
+static void slip_states_body(SlipStatesArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    if (A.phase <= 1) {
+        const int64_t rpp = ((int64_t) A.n + SLIP_WAVE - 1) / SLIP_WAVE, rounds = rpp * A.nprob;
+        uint32_t wall = 0;
+        unsigned long long total = 0;
+        for (int64_t r = wave0; r < rounds; r += nwaves) {
+            const int c = (int)(r / rpp);
+            const int64_t i = (r - (int64_t) c * rpp) * SLIP_WAVE + lane, e = (int64_t) c * A.n + i, ex = (int64_t) c * A.xstride + i;
+            if (A.phase == 1) {
+                const int take = i < A.n && A.cls[e] == 1;
+                if (take) {
+                    const SlipBoundOp X = slip_bound_op(A.xlen, A.xoff, A.xlimbs, ex);
+                    const uint64_t v = X.l > 1 ? ((uint64_t) X.p[1] << 32) | X.p[0] : X.p[0];
+                    const slip_u128 sq = (slip_u128) v * v;
+                    const uint64_t l0 = (uint64_t) sq, l1 = (uint64_t)(sq >> 64);
+                    uint64_t *out = A.stage + A.soff[e];
+                    out[0] = l0;
+                    if (X.l > 1) out[1] = l1;
+                    A.xlen2[e] = l1 ? (l1 >> 32 ? 4 : 3) : (l0 >> 32 ? 2 : 1);
+                }
+                total += (unsigned long long) slip_popc64(slip_ballot(take));
+                continue;
+            }
+            uint32_t W = 0;
+            int el = 0;
+            if (i < A.n) {
+                const int st = A.state[i], sd = A.dlen[c] < 0 ? -1 : 1;
+                const SlipBoundOp X = slip_bound_op(A.xlen, A.xoff, A.xlimbs, ex);
+                if (A.nside == 1) {
+                    const int t = A.sense * sd * X.s;
+                    el = st == 1 ? t < 0 : st == 2 ? t > 0 : st == 3 ? t != 0 : 0;
+                    if (!A.weighted) {
+                        A.xlen2[e] = X.l; A.xoff2[e] = A.xoff[ex];
+                        A.alen2[e] = el; A.aoff2[e] = 0;
+                    } else {
+                        int code = 0;
+                        if (el) {
+                            const int sq = (2 * wb_bits(X.p, X.l) + 31) >> 5;      /* the digits the square cannot exceed */
+                            code = X.l <= 2 ? 1 : sq <= 256 ? 1 + ((sq + 63) >> 6) : 6;
+                            W = 2u * (uint32_t) X.l;
+                        }
+                        A.cls[e] = code; A.w[e] = (int32_t) W;
+                        A.xlen2[e] = 0;
+                        A.alen2[e] = el ? A.wtlen[i] : 0; A.aoff2[e] = A.wtoff[i];
+                    }
+                } else {
+                    const int64_t ea = (int64_t) c * A.astride + i;
+                    const SlipBoundOp Av = slip_bound_op(A.alen, A.aoff, A.alimbs, ea);
+                    const int t = A.sense * sd * Av.s;
+                    el = st == 1 ? t > 0 : st == 2 ? t < 0 : st == 3 ? t != 0 : 0;
+                    A.xlen2[e] = X.s * A.sense * Av.s * X.l; A.xoff2[e] = A.xoff[ex];
+                    A.alen2[e] = el ? A.sense * Av.l : 0; A.aoff2[e] = A.aoff[ea];
+                }
+            }
+            if (A.weighted) { W = slip_wave_max_u32(W); if (W > wall) wall = W; }
+            else total += (unsigned long long) slip_popc64(slip_ballot(el));
+        }
+        if (lane == 0 && wall) slip_atomic_max_i32(A.wmax, (int32_t) wall);
+        if (lane == 0 && total) slip_atomic_add_u64(A.paths + A.phase, total);
+        return;
+    }
+    if (A.phase == 2) {
+        const int64_t items = (int64_t) A.n * A.nprob;
+        unsigned long long cnt[2] = {0, 0};
+        for (int64_t e = wave0; e < items; e += nwaves) {
+            const int code = A.cls[e];
+            if (code < 2) continue;
+            const int c = (int)(e / A.n), i = (int)(e - (int64_t) c * A.n);
+            const SlipBoundOp X = slip_bound_op(A.xlen, A.xoff, A.xlimbs, (int64_t) c * A.xstride + i);
+            dig_t *out = (dig_t *)(A.stage + A.soff[e]);
+            int len;
+            if (code == 2) len = slip_states_square_reg<1>(X, out);
+            else if (code == 3) len = slip_states_square_reg<2>(X, out);
+            else if (code == 4) len = slip_states_square_reg<3>(X, out);
+            else if (code == 5) len = slip_states_square_reg<4>(X, out);
+            else {
+                wb_mul_lo(out, X.p, X.l, X.p, X.l, 2 * X.l);       /* (the entry owns 2 dig(X) digits: whole limbs) */
+                len = wb_len(out, 2 * X.l);
+            }
+            if (lane == 0) A.xlen2[e] = len;
+            cnt[code == 6]++;
+        }
+        if (lane == 0) for (int k = 0; k < 2; k++) if (cnt[k]) slip_atomic_add_u64(A.paths + 2 + k, cnt[k]);
+        return;
+    }
+    const int64_t rounds = ((int64_t) A.nprob + SLIP_WAVE - 1) / SLIP_WAVE;
+    for (int64_t r = wave0; r < rounds; r += nwaves) {
+        const int64_t c = r * SLIP_WAVE + lane;
+        if (c >= A.nprob) continue;
+        const int32_t b = A.best[c];
+        const int64_t ex = c * A.xstride + (b < 0 ? 0 : b), ea = c * A.astride + (b < 0 ? 0 : b);
+        const int32_t sx = b < 0 ? 0 : A.xlen[ex];
+        A.vsign[c] = sx == 0 ? 0 : (((sx < 0) != (A.dlen[c] < 0)) ? -1 : 1);
+        if (A.wxlen) {
+            A.wxlen[c] = sx; A.wxoff[c] = b < 0 ? 0 : A.xoff[ex];
+            A.walen[c] = b < 0 || A.nside == 1 ? 0 : A.alen[ea]; A.waoff[c] = b < 0 || A.nside == 1 ? 0 : A.aoff[ea];
+        }
+    }
+}
+
 /* The transposed view of complete factors (slip_hip_factor_solve_transpose).  With M = A(row_perm, q) the matrix that was
  * factorised, every entry of a REF factorisation is a minor of M (L(i,k) = det M[{0..k-1,i},{0..k}], U(k,j) =
  * det M[{0..k},{0..k-1,j}], rho_k = det M[0..k,0..k]); transposing swaps the rows and columns of every minor, so the REF
@@ -2225,6 +2383,9 @@ struct slip_hip_factor {
     /* slip_hip_factor_ratio_test_bounded / _bound_test: device time of the last call (the form passes, the selection), the
      * entries by the path that formed them and the path counts of the selection */
     double bound_ms[2]; int64_t bound_paths[8];
+    /* slip_hip_factor_price_states: device time of the last call (the classify, offset and square passes, the selection), the
+     * eligible entries by the path that settled them and the path counts of the selection */
+    double states_ms[2]; int64_t states_paths[8];
     /* slip_hip_factor_rewind / _replace_column: the host copy of q; the storage of the resident A -- annz / alimbs are its
      * LIVE entries and limbs, Acap_nz / Acap_nl what dAi, dAlen, dAoff / dAlimbs can hold, Anl_used the limbs of the slab
      * handed out (live ones and the dead ones of replaced columns: new limbs are appended there), A0_nz / A0_nl the initial
@@ -5509,6 +5670,349 @@ extern "C" int slip_hip_factor_price_paths(const slip_hip_factor *f, int64_t out
 {
     if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
     memcpy(out, f->price_paths, sizeof f->price_paths);
+    return SLIP_HIP_OK;
+}
+
+/* ---- nonbasic states and reference weights in exact pricing: the entering column of a boxed LP (at lower, at upper, free,
+ * never) under Dantzig's rule or reference weights (the largest X_j^2 / w_j), and the dual ratio test with the mirror rule
+ * on the sign of A_j; the records formed on the device, the selection slip_ratio_kernel's as it stands (no counterpart in
+ * the reference; kernel: slip_states_kernel) ---- */
+
+/* the counts of this thread's last slip_hip_price_select */
+static thread_local int64_t slip_states_paths_last[8];
+
+/* the states and weights of a call checked on the host: ws receives the weights' layout (untouched without weights) */
+static int states_check(int32_t ncols, int32_t nside, const int32_t *state, const int32_t *wlen, const uint64_t *wlimbs, int64_t w_limbs,
+                        SlipSlab *ws)
+{
+    memset(ws, 0, sizeof *ws);
+    if (!state || !wlen != !wlimbs || (wlen && nside != 1)) return SLIP_HIP_INCORRECT_INPUT;
+    for (int32_t j = 0; j < ncols; j++) if (state[j] < 0 || state[j] > 3) return SLIP_HIP_INCORRECT_INPUT;
+    if (!wlen) return SLIP_HIP_OK;
+    TRY_(slab_prepare(ncols, wlen, wlimbs, w_limbs, ws));
+    for (int32_t j = 0; j < ncols; j++) if (ws->dig[j] <= 0) { slab_free(ws); return SLIP_HIP_INCORRECT_INPUT; }
+    return SLIP_HIP_OK;
+}
+
+/* the same on the device: the states, the weights' records and limbs (NULL without weights), one limb holding 1 */
+struct SlipStatesOps { int32_t *state, *wtlen; int64_t *wtoff; uint64_t *wtlimbs, *one; };
+static void states_ops_free(SlipStatesOps *o)
+{
+    dev_free(o->state); dev_free(o->wtlen); dev_free(o->wtoff); dev_free(o->wtlimbs); dev_free(o->one);
+    memset(o, 0, sizeof *o);
+}
+static int states_upload(int32_t ncols, const int32_t *state, const SlipSlab *ws, const uint64_t *wlimbs, SlipStatesOps *o)
+{
+    const uint64_t one = 1;
+    int rc = 0;
+    memset(o, 0, sizeof *o);
+    A_(dev_alloc(&o->state, ncols)); UP_(o->state, state, (size_t) ncols * 4);
+    A_(dev_alloc(&o->one, 1)); UP_(o->one, &one, 8);
+    if (ws->dig) {
+        A_(dev_alloc(&o->wtlen, ncols)); A_(dev_alloc(&o->wtoff, ncols)); A_(dev_alloc(&o->wtlimbs, ws->total));
+        UP_(o->wtlen, ws->dig, (size_t) ncols * 4); UP_(o->wtoff, ws->off, (size_t) ncols * 8); UP_(o->wtlimbs, wlimbs, (size_t) ws->total * 8);
+    }
+    if (rc) states_ops_free(o);
+    return rc;
+}
+
+/* the device operands of one selection with states: X (and A, nside 2) of problem c from entry c * stride on, the record of
+ * d_c as entry c of d (its sign is all that is read) */
+struct SlipStatesIn {
+    int32_t n, nprob, nside, sense;
+    SlipDevRecs x, a; int64_t xstride, astride;
+    const int32_t *dlen;
+};
+
+/* one selection with states on the device.  r0 .. r3 (host) receive best, nties, neligible and vsign of the nprob problems;
+ * with wl the winners' records are appended to wl / wv, X_best and A_best of every problem (signed limb counts).  ms (the
+ * classify, offset and square passes; the selection) and paths are added to. */
+static int states_core(const SlipStatesIn &I, const SlipStatesOps &O, const int32_t *key, int32_t *r0, int32_t *r1, int32_t *r2, int32_t *r3,
+                       std::vector<int32_t> *wl, std::vector<uint64_t> *wv, hipStream_t stream, double ms[2], int64_t paths[8])
+{
+    const int32_t n = I.n, nprob = I.nprob;
+    const int weighted = O.wtlen != NULL;
+    const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE;
+    int32_t *dxl2 = NULL, *dal2 = NULL, *dcls = NULL, *dw = NULL, *dwmax = NULL, *dsel = NULL, *dwn = NULL;
+    int64_t *dxo2 = NULL, *dao2 = NULL, *dso = NULL, *dwo = NULL;
+    unsigned long long *dpaths = NULL, *bsum = NULL, hpaths[4] = {0, 0, 0, 0};
+    int32_t hwmax = 0;
+    int rc = 0;
+    A_(dev_alloc(&dxl2, ne)); A_(dev_alloc(&dxo2, ne)); A_(dev_alloc(&dal2, ne)); A_(dev_alloc(&dao2, ne));
+    A_(dev_alloc(&dpaths, 4)); A_(dev_alloc(&dsel, 2 * (int64_t) nprob));
+    if (weighted) { A_(dev_alloc(&dcls, ne)); A_(dev_alloc(&dw, ne)); A_(dev_alloc(&dso, ne)); A_(dev_alloc(&dwmax, 1)); }
+    if (wl) { A_(dev_alloc(&dwn, 2 * (int64_t) nprob)); A_(dev_alloc(&dwo, 2 * (int64_t) nprob)); }
+    HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
+    if (weighted) HIP_(hipMemsetAsync(dwmax, 0, 4, stream));
+    SlipStatesArgs A; memset(&A, 0, sizeof A);
+    A.n = n; A.nside = I.nside; A.sense = I.sense; A.weighted = weighted; A.xstride = I.xstride; A.astride = I.astride;
+    A.xlimbs = I.x.limbs; A.alimbs = I.a.limbs; A.state = O.state; A.wtlen = O.wtlen; A.wtoff = O.wtoff;
+    A.wmax = dwmax; A.paths = dpaths;
+    /* the problems c0 .. c0 + nv of every per-problem and per-entry array */
+    auto slice = [&](int64_t c0, int64_t nv, int phase) {
+        A.nprob = (int32_t) nv; A.phase = phase;
+        A.xlen = I.x.len + c0 * I.xstride; A.xoff = I.x.off + c0 * I.xstride;
+        A.alen = I.a.len ? I.a.len + c0 * I.astride : NULL; A.aoff = I.a.off ? I.a.off + c0 * I.astride : NULL;
+        A.dlen = I.dlen + c0;
+        A.xlen2 = dxl2 + c0 * n; A.xoff2 = dxo2 + c0 * n; A.alen2 = dal2 + c0 * n; A.aoff2 = dao2 + c0 * n;
+        A.cls = weighted ? dcls + c0 * n : NULL; A.w = weighted ? dw + c0 * n : NULL; A.soff = weighted ? dso + c0 * n : NULL;
+    };
+    if (!rc) {                                             /* the records of all entries (with weights: their classes and widths) */
+        SlipTimed timed;
+        double t = 0;
+        slice(0, nprob, 0);
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(states, wave_blocks(rpp * nprob), stream, A));
+        A_(timed.end(stream, &t));
+        ms[0] += t;
+    }
+    /* the squares are staged in groups of whole problems (at least one: the bound never refuses) */
+    int64_t group = nprob, sblocks = 0;
+    if (weighted) {
+        DOWN_(&hwmax, dwmax, 4);
+        const int64_t wcap = hwmax > 2 ? hwmax : 2;        /* (even: twice an operand's digits) */
+        if (!rc && wcap > (1 << 28)) rc = SLIP_HIP_OUT_OF_MEMORY;
+        group = rc ? 1 : product_stage_limbs() / ((int64_t) n * (wcap / 2));
+        if (group < 1) group = 1;
+        if (group > nprob) group = nprob;
+        sblocks = offscan_blocks((int64_t) n * group);
+        A_(dev_alloc(&bsum, sblocks));
+    }
+    for (int64_t c0 = 0; c0 < nprob && !rc; c0 += group) {
+        const int64_t nv = c0 + group <= nprob ? group : nprob - c0, cnt = (int64_t) n * nv;
+        uint64_t *dstage = NULL; int64_t total = 0;
+        double t = 0;
+        if (weighted) {
+            {                                              /* the staging offsets from the widths */
+                SlipTimed timed;
+                A_(timed.begin(stream));
+                A_(offscan_run(cnt, dw + c0 * n, dso + c0 * n, bsum, sblocks, stream));
+                A_(timed.end(stream, &t));
+                ms[0] += t;
+            }
+            A_(offscan_total(bsum, sblocks, &total, stream));
+            if (!rc && total > cnt * (int64_t)(hwmax / 2)) rc = SLIP_HIP_DEVICE_ERROR;   /* (the widths' bound: the host's own figure) */
+            A_(dev_alloc(&dstage, total));
+            if (!rc) {                                     /* the squares into the slab: the lane pass, the wave pass */
+                SlipTimed timed;
+                A.stage = dstage;
+                A_(timed.begin(stream));
+                slice(c0, nv, 1); A_(SERVICE_LAUNCH(states, wave_blocks(rpp * nv), stream, A));
+                if (hwmax > 4) { slice(c0, nv, 2); A_(SERVICE_LAUNCH(states, wave_blocks(cnt), stream, A)); }
+                A_(timed.end(stream, &t));
+                ms[0] += t;
+            }
+        }
+        /* the selection on the group's records: the largest |X_j| or X_j^2 / w_j, or the smallest X_j / (sense * A_j) */
+        int64_t gp[4] = {0, 0, 0, 0};
+        SlipRatioArgs R; memset(&R, 0, sizeof R);
+        R.n = n; R.nprob = (int32_t) nv; R.pstride = n;
+        R.xlen = dxl2 + c0 * n; R.xoff = weighted ? dso + c0 * n : dxo2 + c0 * n; R.xlimbs = weighted ? dstage : I.x.limbs;
+        R.alen = dal2 + c0 * n; R.aoff = dao2 + c0 * n; R.alimbs = I.nside == 2 ? I.a.limbs : weighted ? O.wtlimbs : O.one;
+        R.asense = I.nside == 2 ? I.sense : 1; R.xflip = I.nside == 1;
+        t = 0;
+        A_(ratio_core(R, key, r0 + c0, r1 + c0, r2 + c0, NULL, NULL, NULL, stream, &t, gp));
+        if (!rc) { ms[1] += t; for (int k = 0; k < 4; k++) paths[4 + k] += gp[k]; }
+        /* the winners' direction and, on request, their records as they came in */
+        UP_(dsel, r0 + c0, (size_t) nv * 4);
+        if (!rc) {
+            slice(c0, nv, 3);
+            A.best = dsel; A.vsign = dsel + nprob;
+            if (wl) { A.wxlen = dwn; A.wxoff = dwo; A.walen = dwn + nprob; A.waoff = dwo + nprob; }
+            A_(SERVICE_LAUNCH(states, service_blocks(nv), stream, A));
+            HIP_(hipStreamSynchronize(stream));
+        }
+        DOWN_(r3 + c0, dsel + nprob, (size_t) nv * 4);
+        if (wl) {
+            int32_t *xl = NULL, *al = NULL; uint64_t *xv = NULL, *av = NULL; int64_t xn = 0, an = 0;
+            A_(pack_download(nv, dwn, dwo, I.x.limbs, 0, &xl, &xv, &xn, stream));
+            A_(pack_download(nv, dwn + nprob, dwo + nprob, I.nside == 2 ? I.a.limbs : I.x.limbs, 0, &al, &av, &an, stream));
+            if (!rc) {
+                int64_t ox = 0, oa = 0;
+                for (int64_t c = 0; c < nv; c++) {
+                    const int64_t lx = xl[c] < 0 ? -xl[c] : xl[c], la = al[c] < 0 ? -al[c] : al[c];
+                    wl->push_back(xl[c]); wv->insert(wv->end(), xv + ox, xv + ox + lx); ox += lx;
+                    wl->push_back(al[c]); wv->insert(wv->end(), av + oa, av + oa + la); oa += la;
+                }
+            }
+            free(xl); free(al); free(xv); free(av);
+        }
+        dev_free(dstage);
+    }
+    DOWN_(hpaths, dpaths, 32);
+    if (!rc) for (int k = 0; k < 4; k++) paths[k] += (int64_t) hpaths[k];
+    dev_free(dxl2); dev_free(dxo2); dev_free(dal2); dev_free(dao2); dev_free(dcls); dev_free(dw); dev_free(dso); dev_free(dwmax);
+    dev_free(dpaths); dev_free(dsel); dev_free(dwn); dev_free(dwo); dev_free(bsum);
+    return rc;
+}
+
+/* the winners' records collected by states_core as the caller's malloc'ed slab */
+static int states_winners(const std::vector<int32_t> &wl, const std::vector<uint64_t> &wv, int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out)
+{
+    int32_t *ol = (int32_t *) malloc((wl.size() > 0 ? wl.size() : 1) * 4); uint64_t *ov = (uint64_t *) malloc((wv.size() > 0 ? wv.size() : 1) * 8);
+    if (!ol || !ov) { free(ol); free(ov); return SLIP_HIP_OUT_OF_MEMORY; }
+    if (!wl.empty()) memcpy(ol, wl.data(), wl.size() * 4);
+    if (!wv.empty()) memcpy(ov, wv.data(), wv.size() * 8);
+    *wlen_out = ol; *wlimbs_out = ov; *wnl_out = (int64_t) wv.size();
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_price_states(slip_hip_factor *f, slip_hip_matrix *M, int32_t nside, int32_t nprob,
+                                            const int32_t *blen, const uint64_t *blimbs,
+                                            const int32_t *glen, const uint64_t *glimbs, int64_t g_limbs,
+                                            const int32_t *state, const int32_t *wlen, const uint64_t *wlimbs, int64_t w_limbs,
+                                            int32_t sense, const int32_t *key,
+                                            int32_t *best, int32_t *nties, int32_t *neligible, int32_t *vsign,
+                                            int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    if (!f || !M || !blen || !blimbs || !best || !nties || !neligible || !vsign || (nside != 1 && nside != 2) || nprob < 1 ||
+        nprob > (1 << 29) || (sense != 1 && sense != -1) || !glen != !glimbs)
+        return SLIP_HIP_INCORRECT_INPUT;
+    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (M->m != f->n) return SLIP_HIP_INCORRECT_INPUT;
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
+    if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
+    const int32_t n = f->n, ncols = M->ncols, nvec = nside * nprob;
+    const int64_t nxe = (int64_t) n * nvec, ne = (int64_t) ncols * nvec;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipSlab gs, ws; memset(&gs, 0, sizeof gs);
+    TRY_(states_check(ncols, nside, state, wlen, wlimbs, w_limbs, &ws));
+    if (glen) { const int e_ = slab_prepare((int64_t) nprob * ncols, glen, glimbs, g_limbs, &gs); if (e_) { slab_free(&ws); return e_; } }
+    SlipSolveOut o;
+    int rc = solve_device(f, 1, nvec, blen, blimbs, stream, &o);
+    if (rc) { slab_free(&gs); slab_free(&ws); return rc; }
+    if (wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
+    int32_t *dxl = NULL, *dgl = NULL, *ddlen = NULL; int64_t *dxo = NULL, *dgo = NULL, *ddoff = NULL; uint64_t *dgv = NULL;
+    int32_t dmaxdig = 0;
+    /* the result on the host until all of it stands: best, nties, neligible, vsign, nprob each */
+    int32_t *hres = (int32_t *) malloc((size_t) nprob * 16);
+    std::vector<int32_t> wl; std::vector<uint64_t> wv;
+    double pms[4] = {0, 0, 0, 0}, ms[2] = {0, 0};
+    int64_t paths[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    SlipStatesOps O; memset(&O, 0, sizeof O);
+    if (!hres) rc = SLIP_HIP_OUT_OF_MEMORY;
+    A_(states_upload(ncols, state, &ws, wlimbs, &O));
+    /* y by row id: the records of the substitution's output gathered through pinv, its limbs where they are */
+    A_(dev_alloc(&dxl, nxe)); A_(dev_alloc(&dxo, nxe));
+    if (!rc) {
+        SlipPriceArgs G; memset(&G, 0, sizeof G);
+        G.phase = 0; G.n = n; G.count = nxe; G.pinv = f->P.pinv.p_; G.olen = o.olen; G.ooff = o.ooff; G.xlen = dxl; G.xoff = dxo;
+        A_(SERVICE_LAUNCH(price, service_blocks(nxe), stream, G));
+    }
+    /* det * g: the cost vector's records on the x side of every problem, empty records on its a side */
+    if (glen) {
+        int32_t *hl = (int32_t *) calloc((size_t) ne, 4); int64_t *ho = (int64_t *) calloc((size_t) ne, 8);
+        if (!hl || !ho) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
+        else for (int32_t c = 0; c < nprob; c++) {
+            memcpy(hl + (int64_t) nside * c * ncols, gs.dig + (int64_t) c * ncols, (size_t) ncols * 4);
+            memcpy(ho + (int64_t) nside * c * ncols, gs.off + (int64_t) c * ncols, (size_t) ncols * 8);
+        }
+        A_(dev_alloc(&dgl, ne)); A_(dev_alloc(&dgo, ne)); A_(dev_alloc(&dgv, gs.total));
+        UP_(dgl, hl, (size_t) ne * 4); UP_(dgo, ho, (size_t) ne * 8); UP_(dgv, glimbs, (size_t) gs.total * 8);
+        free(hl); free(ho);
+    }
+    /* det's record once per vector: the products' d and, its sign alone, the d_c of every problem */
+    A_(det_records(f, nvec, &ddlen, &ddoff, &dmaxdig));
+    SlipProductView V;
+    V.nout = ncols; V.nx = n; V.alen = M->dAlen; V.aoff = M->dAoff; V.alimbs = M->dAlimbs; V.amaxdig = M->amaxdig;
+    V.rp = M->col_rp; V.re = M->col_re; V.rx = M->col_rx;
+    const SlipDevRecs x = {dxl, dxo, o.olimbs}, g = {dgl, dgo, dgv};
+    /* the selection on a group of whole problems, on the staged records: X of problem c at c * nside * ncols, A ncols on */
+    auto select = [&](int64_t c0, int64_t nv, const int32_t *rlen, const int64_t *soff, const uint64_t *stage, double *t) {
+        const int64_t p0 = c0 / nside;
+        SlipStatesIn I; memset(&I, 0, sizeof I);
+        I.n = ncols; I.nprob = (int32_t)(nv / nside); I.nside = nside; I.sense = sense;
+        I.x.len = rlen; I.x.off = soff; I.x.limbs = stage; I.xstride = (int64_t) nside * ncols;
+        if (nside == 2) { I.a.len = rlen + ncols; I.a.off = soff + ncols; I.a.limbs = stage; I.astride = I.xstride; }
+        I.dlen = ddlen + p0;
+        const double before = ms[0] + ms[1];
+        const int rc = states_core(I, O, key, hres + p0, hres + nprob + p0, hres + 2 * (int64_t) nprob + p0, hres + 3 * (int64_t) nprob + p0,
+                                   wlen_out ? &wl : NULL, wlen_out ? &wv : NULL, stream, ms, paths);
+        *t = ms[0] + ms[1] - before;
+        return rc;
+    };
+    A_(product_device(V, nvec, x, -1, glen ? &g : NULL, gs.maxdig, ddlen, ddoff, f->P.Llimbs, dmaxdig, nside, select, stream, pms));
+    dev_free(dxl); dev_free(dxo); dev_free(dgl); dev_free(dgo); dev_free(dgv); dev_free(ddlen); dev_free(ddoff);
+    states_ops_free(&O);
+    slab_free(&gs); slab_free(&ws);
+    solve_out_free(&o);
+    if (!rc && wlen_out) rc = states_winners(wl, wv, wlen_out, wlimbs_out, wnl_out);
+    if (!rc) {
+        memcpy(best, hres, (size_t) nprob * 4); memcpy(nties, hres + nprob, (size_t) nprob * 4);
+        memcpy(neligible, hres + 2 * (size_t) nprob, (size_t) nprob * 4); memcpy(vsign, hres + 3 * (size_t) nprob, (size_t) nprob * 4);
+        memcpy(f->states_ms, ms, sizeof ms); memcpy(f->states_paths, paths, sizeof paths);
+    }
+    free(hres);
+    return rc;
+}
+
+extern "C" int slip_hip_price_select(int32_t ncols, int32_t nprob, int32_t nside,
+                                     const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                     const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                                     const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                     const int32_t *state, const int32_t *wlen, const uint64_t *wlimbs, int64_t w_limbs,
+                                     int32_t sense, const int32_t *key,
+                                     int32_t *best, int32_t *nties, int32_t *neligible, int32_t *vsign,
+                                     int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, void *stream_v)
+{
+    if (ncols <= 0 || nprob < 1 || nprob > (1 << 29) || (nside != 1 && nside != 2) || (sense != 1 && sense != -1) || !xlen || !xlimbs ||
+        !dlen || !dlimbs || !best || !nties || !neligible || !vsign)
+        return SLIP_HIP_INCORRECT_INPUT;
+    if (nside == 2 ? (!alen || !alimbs) : (alen || alimbs)) return SLIP_HIP_INCORRECT_INPUT;
+    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    TRY_(need_device());
+    const int64_t ne = (int64_t) ncols * nprob;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipSlab xs, as, ds, ws; memset(&xs, 0, sizeof xs); memset(&as, 0, sizeof as); memset(&ds, 0, sizeof ds);
+    TRY_(states_check(ncols, nside, state, wlen, wlimbs, w_limbs, &ws));
+    int32_t *dxl = NULL, *dal = NULL, *ddl = NULL, *res = NULL; int64_t *dxo = NULL, *dao = NULL, *ddo = NULL; uint64_t *dxv = NULL, *dav = NULL, *ddv = NULL;
+    std::vector<int32_t> wl; std::vector<uint64_t> wv;
+    double ms[2] = {0, 0};
+    int64_t paths[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    SlipStatesOps O; memset(&O, 0, sizeof O);
+    /* (every slab is checked against its capacity before a limb of it is read) */
+    int rc = ratio_upload(nprob, dlen, dlimbs, d_limbs, &ds, &ddl, &ddo, &ddv);
+    for (int32_t c = 0; c < nprob && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    A_(ratio_upload(ne, xlen, xlimbs, x_limbs, &xs, &dxl, &dxo, &dxv));
+    if (nside == 2) A_(ratio_upload(ne, alen, alimbs, a_limbs, &as, &dal, &dao, &dav));
+    A_(states_upload(ncols, state, &ws, wlimbs, &O));
+    if (!rc && !(res = (int32_t *) malloc((size_t) nprob * 16))) rc = SLIP_HIP_OUT_OF_MEMORY;
+    if (!rc && wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
+    SlipStatesIn I; memset(&I, 0, sizeof I);
+    I.n = ncols; I.nprob = nprob; I.nside = nside; I.sense = sense; I.xstride = ncols; I.astride = ncols;
+    I.x.len = dxl; I.x.off = dxo; I.x.limbs = dxv; I.a.len = dal; I.a.off = dao; I.a.limbs = dav; I.dlen = ddl;
+    A_(states_core(I, O, key, res, res + nprob, res + 2 * (int64_t) nprob, res + 3 * (int64_t) nprob,
+                   wlen_out ? &wl : NULL, wlen_out ? &wv : NULL, stream, ms, paths));
+    if (!rc && wlen_out) rc = states_winners(wl, wv, wlen_out, wlimbs_out, wnl_out);
+    if (!rc) {
+        bound_results(res, nprob, best, nties, neligible, vsign);
+        memcpy(slip_states_paths_last, paths, sizeof paths);
+    }
+    free(res);
+    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dal); dev_free(dao); dev_free(dav); dev_free(ddl); dev_free(ddo); dev_free(ddv);
+    states_ops_free(&O);
+    slab_free(&xs); slab_free(&as); slab_free(&ds); slab_free(&ws);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_price_states_ms(const slip_hip_factor *f, double out[2])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->states_ms, sizeof f->states_ms);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_price_states_paths(const slip_hip_factor *f, int64_t out[8])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->states_paths, sizeof f->states_paths);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_price_select_paths(int64_t out[8])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_states_paths_last, sizeof slip_states_paths_last);
     return SLIP_HIP_OK;
 }
 
