@@ -662,6 +662,62 @@ int slip_hip_factor_price_states_ms(const slip_hip_factor *f, double out[2]);
 int slip_hip_factor_price_states_paths(const slip_hip_factor *f, int64_t out[8]);
 int slip_hip_price_select_paths(int64_t out[8]);
 
+/* Exact pivot update: the numerators of the next iterate from those the ratio test already holds, without a second
+ * substitution (no counterpart in the reference).  With x = X / d the basic solution, alpha = A / d = B^-1 a_q
+ * the entering column and r the leaving position, the basis B' (a_q at position r) has det B' = +-A_r and
+ *     X'_i = (A_r X_i - X_r A_i) / d  (i != r),   X'_r = X_r           over the denominator A_r;
+ * the division is exact (Cramer's rule on B' x' = b).  The duals update alike: Y' = (A_r Y + D_q R) / d over A_r with R = d
+ * B^-T e_r and D_q = d c_q - a_q^T Y.  The kernel computes, per problem c and entry i,
+ *     R_i = (P_c V_i - T_c A_i) / D_c
+ * in signed big integers, and tests every division: an entry D_c does not divide comes back with length 0 and is counted in
+ * ninexact[c].  Slabs, status and stream as slip_hip_ratio_test_bounded; high zero limbs are allowed in every operand; the
+ * result is a normalised slab (the top limb of an entry is nonzero, a zero has count 0), malloc'ed, release with slip_hip_free.
+ *
+ * slip_hip_pivot_update, on caller slabs: v, a of nprob * n entries; p, t one scalar per problem; d optional (dlen == dlimbs
+ *   == NULL: no division), else one nonzero D_c per problem; place optional, nprob indices in [-1, n): entry place[c] of
+ *   problem c (when >= 0) is T_c itself.  r: nprob * n entries.
+ * slip_hip_factor_solve_update, fused: b holds 2 * nprob right-hand sides as slip_hip_factor_ratio_test takes them (2c the V
+ *   side, 2c + 1 the A side); the substitution runs, D = det = rho[n-1], P and T from the caller; the numerators of V and A
+ *   never leave the device.  Indices (place, the order of r) are those of the matching solve's output: pivot position for
+ *   transpose 0, original row id for transpose 1.
+ * slip_hip_factor_step, the step: slip_hip_factor_ratio_test's selection (sense, key, best, nties, neligible as there), then
+ *   P = anum_best, T = xnum_best, D = det, place = best.  r: nprob * n entries, the new numerators over dnew[c] = anum_best
+ *   (nprob entries); best[c] = -1 leaves the n entries of problem c and dnew[c] with length 0.  The ratio counts of a step
+ *   stay readable through slip_hip_factor_ratio_test_paths.
+ * The fused forms need a complete factorisation; transpose 0 is refused on a handle from slip_hip_factor_from_factors.
+ * SLIP_HIP_INCORRECT_INPUT, with nothing written and before any array is read past its end: a NULL required argument (every
+ * pointer but d, place, key and stream), n <= 0 or nprob < 1, exactly one of dlen / dlimbs NULL, a zero D_c, a slab whose sum
+ * of |len| exceeds its capacity, a place[c] outside [-1, n), everything slip_hip_factor_ratio_test refuses.  A broken handle
+ * or no device: SLIP_HIP_DEVICE_ERROR.
+ *
+ * slip_hip_factor_update_ms: device ms of the handle's last fused call, out[0] the classify, offset and form passes, out[1]
+ * the selection of a step (the substitution: slip_hip_factor_solve_ms).  _paths: out[0 .. 3] the entries [0] that needed no
+ * arithmetic (both terms zero, placed, or of a problem without a winner), formed [1] in a lane, [2] by a wavefront in
+ * registers, [3] by a wavefront through memory; out[4] the inexact entries; out[5 .. 7] are reserved and hold 0.
+ * slip_hip_pivot_update_paths: the same of this thread's last slip_hip_pivot_update. */
+int slip_hip_pivot_update(int32_t n, int32_t nprob,
+                          const int32_t *vlen, const uint64_t *vlimbs, int64_t v_limbs,
+                          const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                          const int32_t *plen, const uint64_t *plimbs, int64_t p_limbs,
+                          const int32_t *tlen, const uint64_t *tlimbs, int64_t t_limbs,
+                          const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                          const int32_t *place, int32_t *ninexact,
+                          int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream);
+int slip_hip_factor_solve_update(slip_hip_factor *f, int32_t transpose, int32_t nprob,
+                                 const int32_t *blen, const uint64_t *blimbs,
+                                 const int32_t *plen, const uint64_t *plimbs, int64_t p_limbs,
+                                 const int32_t *tlen, const uint64_t *tlimbs, int64_t t_limbs,
+                                 const int32_t *place, int32_t *ninexact,
+                                 int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream);
+int slip_hip_factor_step(slip_hip_factor *f, int32_t transpose, int32_t nprob,
+                         const int32_t *blen, const uint64_t *blimbs, int32_t sense, const int32_t *key,
+                         int32_t *best, int32_t *nties, int32_t *neligible, int32_t *ninexact,
+                         int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                         int32_t **dlen_out, uint64_t **dlimbs_out, int64_t *dnl_out, void *stream);
+int slip_hip_factor_update_ms(const slip_hip_factor *f, double out[2]);
+int slip_hip_factor_update_paths(const slip_hip_factor *f, int64_t out[8]);
+int slip_hip_pivot_update_paths(int64_t out[8]);
+
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize
  * creates and destroys one per call): at most SLIP_HIP_POOL_MB megabytes (environment, default 32768; 0 = no pool).  This

@@ -6,6 +6,6 @@ ctypes layer the tests and bench.py use.
 """
 from . import api  # noqa: F401
 from .api import (Bounds, Factorization, SlipError, SparseMatrix, bound_paths, bound_test, check_solution, factorize,  # noqa: F401
-                  ints_to_slab, matgen, multiply_passes, price_select, price_select_paths, ratio_test, ratio_test_bounded,
-                  ratio_test_paths, read_triplet, solution_to_double, solution_to_mpfr, solution_to_mpfr_paths,
+                  ints_to_slab, matgen, multiply_passes, pivot_update, pivot_update_paths, price_select, price_select_paths,
+                  ratio_test, ratio_test_bounded, ratio_test_paths, read_triplet, solution_to_double, solution_to_mpfr, solution_to_mpfr_paths,
                   solution_to_rational, solution_to_rational_paths, write_triplet)

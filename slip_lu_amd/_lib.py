@@ -60,7 +60,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_ratio_test_bounded", "slip_hip_factor_bound_test", "slip_hip_ratio_test_bounded", "slip_hip_bound_test",
            "slip_hip_factor_bound_ms", "slip_hip_factor_bound_paths", "slip_hip_bound_paths",
            "slip_hip_factor_price_states", "slip_hip_price_select", "slip_hip_factor_price_states_ms",
-           "slip_hip_factor_price_states_paths", "slip_hip_price_select_paths")
+           "slip_hip_factor_price_states_paths", "slip_hip_price_select_paths",
+           "slip_hip_pivot_update", "slip_hip_factor_solve_update", "slip_hip_factor_step", "slip_hip_factor_update_ms",
+           "slip_hip_factor_update_paths", "slip_hip_pivot_update_paths")
 
 _libs = {}
 
@@ -218,5 +220,17 @@ def load(path=None):
     lib.slip_hip_factor_price_states_paths.restype = C.c_int
     lib.slip_hip_price_select_paths.argtypes = [vp]
     lib.slip_hip_price_select_paths.restype = C.c_int
+    lib.slip_hip_pivot_update.argtypes = [C.c_int32, C.c_int32] + [vp, vp, i64] * 5 + [vp, vp] + win + [vp]
+    lib.slip_hip_pivot_update.restype = C.c_int
+    lib.slip_hip_factor_solve_update.argtypes = [vp, C.c_int32, C.c_int32, vp, vp] + [vp, vp, i64] * 2 + [vp, vp] + win + [vp]
+    lib.slip_hip_factor_solve_update.restype = C.c_int
+    lib.slip_hip_factor_step.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp] + res4 + win + win + [vp]
+    lib.slip_hip_factor_step.restype = C.c_int
+    lib.slip_hip_factor_update_ms.argtypes = [vp, vp]
+    lib.slip_hip_factor_update_ms.restype = C.c_int
+    lib.slip_hip_factor_update_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_update_paths.restype = C.c_int
+    lib.slip_hip_pivot_update_paths.argtypes = [vp]
+    lib.slip_hip_pivot_update_paths.restype = C.c_int
     _libs[path] = lib
     return lib

@@ -360,6 +360,80 @@ def bound_paths(lib_path=None):
     return [int(v) for v in out]
 
 
+def _scalar_slab(v, nprob, what):
+    """one scalar per problem -- a (signed limb counts, limbs) slab (any pair of two arrays), a Python int or a sequence of nprob Python ints (small
+    ones go through ints_to_slab, wider ones limb by limb) -- as contiguous arrays and the capacity they really have"""
+    if isinstance(v, (tuple, list)) and len(v) == 2 and hasattr(v[0], "__len__") and hasattr(v[1], "__len__"):
+        lens, limbs = v
+    else:
+        vals = [int(v)] * max(nprob, 1) if not hasattr(v, "__len__") else [int(t) for t in v]
+        if all(abs(t) < 2 ** 63 for t in vals):
+            lens, limbs = ints_to_slab(vals)
+        else:
+            parts = [_int_limbs(t) for t in vals]
+            lens = np.array([l for l, _ in parts], np.int32)
+            limbs = np.concatenate([x[:abs(l)] for l, x in parts]) if parts else np.zeros(0, np.uint64)
+    lens, limbs, cap = _limb_arrays(lens, limbs)
+    if nprob >= 1 and lens.size != nprob:
+        raise ValueError(f"pivot update: {what} must hold one entry per problem")
+    return lens, limbs, cap
+
+
+def _place_array(place, nprob):
+    if place is None:
+        return None
+    place = np.ascontiguousarray(place, dtype=np.int32)
+    if nprob >= 1 and place.size != nprob:
+        raise ValueError("pivot update: place must hold one index per problem")
+    return place
+
+
+def pivot_update(n, vlen, vlimbs, alen, alimbs, p, t, d=None, place=None, nprob=1, lib_path=None):
+    """The exact pivot update on caller slabs (slip_hip_pivot_update): R_i = (P_c * V_i - T_c * A_i) / D_c for the nprob * n
+    numerators v and a, one P, T and (optionally) one nonzero D per problem (Python ints or slabs); without d nothing is
+    divided.  place: per problem an index in [-1, n) whose entry of the result is T_c itself.  Returns (rlen, rlimbs,
+    ninexact): the result as a normalised slab; an entry its D does not divide has length 0 and counts in ninexact[c]."""
+    lib = _lib.load(lib_path)
+    n, nprob = int(n), int(nprob)
+    vlen, vlimbs, vcap = _limb_arrays(vlen, vlimbs)
+    alen, alimbs, acap = _limb_arrays(alen, alimbs)
+    if n >= 1 and nprob >= 1 and (vlen.size != n * nprob or alen.size != n * nprob):
+        raise ValueError("pivot_update: vlen and alen must hold n*nprob entries")
+    pl_, pv, pcap = _scalar_slab(p, nprob, "p")
+    tl_, tv, tcap = _scalar_slab(t, nprob, "t")
+    args = [vlen.ctypes.data, vlimbs.ctypes.data, vcap, alen.ctypes.data, alimbs.ctypes.data, acap,
+            pl_.ctypes.data, pv.ctypes.data, pcap, tl_.ctypes.data, tv.ctypes.data, tcap]
+    if d is None:
+        args += [None, None, 0]
+    else:
+        dl_, dv, dcap = _scalar_slab(d, nprob, "d")
+        args += [dl_.ctypes.data, dv.ctypes.data, dcap]
+    place = _place_array(place, nprob)
+    nin = np.zeros(max(nprob, 1), np.int32)
+    pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+    rc = lib.slip_hip_pivot_update(n, nprob, *args, None if place is None else place.ctypes.data, nin.ctypes.data,
+                                   C.byref(pl), C.byref(px), C.byref(nl), None)
+    if rc:
+        raise SlipError(rc, "slip_hip_pivot_update")
+    return _take_slab(lib, pl, px, nl, n * nprob) + (nin[:nprob],)
+
+
+def pivot_update_paths(lib_path=None):
+    """this thread's last pivot_update: entries [that needed no arithmetic, formed in a lane, by a wavefront in registers, by a
+    wavefront through memory], the inexact entries, three reserved zeros"""
+    out = np.zeros(8, np.int64)
+    _lib.load(lib_path).slip_hip_pivot_update_paths(out.ctypes.data)
+    return [int(v) for v in out]
+
+
+class StepResult:
+    """What Factorization.step returns: best, nties, neligible, ninexact (int32[nprob] each), x = (rlen, rlimbs) the new
+    numerators (nprob * n entries) and d = (dlen, dlimbs) the new denominators (nprob entries)."""
+
+    def __init__(self, best, nties, neligible, ninexact, x, d):
+        self.best, self.nties, self.neligible, self.ninexact, self.x, self.d = best, nties, neligible, ninexact, x, d
+
+
 def _states_args(ncols, state, weights, where):
     """the states and optional weights of a pricing with states as the arguments of the C ABI (and the arrays behind them)"""
     state = np.ascontiguousarray(state, dtype=np.int32)
@@ -870,6 +944,59 @@ class Factorization:
         """the last bounded call, as the module's `bound_paths`"""
         out = np.zeros(8, np.int64)
         self.lib.slip_hip_factor_bound_paths(self.h, out.ctypes.data)
+        return [int(v) for v in out]
+
+    def solve_update(self, blen, blimbs, p, t, nprob=1, transpose=False, place=None, stream=None):
+        """Solve and update on the device (slip_hip_factor_solve_update): b holds 2 * nprob right-hand sides as `ratio_test`
+        takes them (2c the V side, 2c + 1 the A side); the module's `pivot_update` on the solve's numerators with D = det, P
+        and T (Python ints or slabs) from the caller, indices those of the matching solve's output.  Returns (rlen, rlimbs,
+        ninexact)."""
+        nprob = int(nprob)
+        blen, blimbs, _ = _rhs(self.n, blen, blimbs, 2 * nprob if nprob >= 1 else nprob)
+        pl_, pv, pcap = _scalar_slab(p, nprob, "p")
+        tl_, tv, tcap = _scalar_slab(t, nprob, "t")
+        place = _place_array(place, nprob)
+        nin = np.zeros(max(nprob, 1), np.int32)
+        pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+        rc = self.lib.slip_hip_factor_solve_update(self.h, int(bool(transpose)), nprob, blen.ctypes.data, blimbs.ctypes.data,
+                                                   pl_.ctypes.data, pv.ctypes.data, pcap, tl_.ctypes.data, tv.ctypes.data, tcap,
+                                                   None if place is None else place.ctypes.data, nin.ctypes.data,
+                                                   C.byref(pl), C.byref(px), C.byref(nl), C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_solve_update")
+        return _take_slab(self.lib, pl, px, nl, self.n * nprob) + (nin[:nprob],)
+
+    def step(self, blen, blimbs, nprob=1, transpose=False, sense=1, key=None, stream=None):
+        """One exact simplex step on the device (slip_hip_factor_step): the selection of `ratio_test` on the same right-hand
+        sides, then the new numerators x_i = (anum_best * xnum_i - xnum_best * anum_i) / det (entry best: xnum_best) over the
+        new denominator d = anum_best, with no second solve.  Returns a StepResult; where best is -1 the problem's entries of
+        x and its d are empty."""
+        nprob = int(nprob)
+        blen, blimbs, _ = _rhs(self.n, blen, blimbs, 2 * nprob if nprob >= 1 else nprob)
+        key = _ratio_key(self.n, key)
+        res = [np.zeros(max(nprob, 1), np.int32) for _ in range(4)]
+        pl, px, nl = C.c_void_p(), C.c_void_p(), C.c_int64()
+        ql, qx, qn = C.c_void_p(), C.c_void_p(), C.c_int64()
+        rc = self.lib.slip_hip_factor_step(self.h, int(bool(transpose)), nprob, blen.ctypes.data, blimbs.ctypes.data, int(sense),
+                                           None if key is None else key.ctypes.data, *[r.ctypes.data for r in res],
+                                           C.byref(pl), C.byref(px), C.byref(nl), C.byref(ql), C.byref(qx), C.byref(qn),
+                                           C.c_void_p(stream or 0))
+        if rc:
+            raise SlipError(rc, "slip_hip_factor_step")
+        x = _take_slab(self.lib, pl, px, nl, self.n * nprob)
+        d = _take_slab(self.lib, ql, qx, qn, nprob)
+        return StepResult(*(r[:nprob] for r in res), x, d)
+
+    def update_ms(self):
+        """device ms of the last solve_update or step: [the classify, offset and form passes, the selection of a step]"""
+        out = np.zeros(2, np.float64)
+        self.lib.slip_hip_factor_update_ms(self.h, out.ctypes.data)
+        return [float(v) for v in out]
+
+    def update_paths(self):
+        """the last solve_update or step, as the module's `pivot_update_paths`"""
+        out = np.zeros(8, np.int64)
+        self.lib.slip_hip_factor_update_paths(self.h, out.ctypes.data)
         return [int(v) for v in out]
 
     def price(self, M, blen, blimbs, nprob=1, sides=1, cost=None, sense=1, key=None, winners=False, stream=None):

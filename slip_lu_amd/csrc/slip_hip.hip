@@ -1847,6 +1847,313 @@ static void slip_bound_body(SlipBoundArgs A)
     }
 }
 
+/* Exact pivot update (slip_hip_pivot_update, slip_hip_factor_solve_update, slip_hip_factor_step): per problem c and
+ * entry i the signed number
+ *     R_i = (P_c * V_i - T_c * A_i) / D_c
+ * from the numerators V and A of nprob problems and one P_c, T_c and (optionally) one nonzero D_c each: one IPGE step per entry,
+ * the update of a basic solution X over d to X' over A_r when position r leaves (P = A_r, T = X_r, D = d).  Without D nothing
+ * is divided.  Entry i of problem c is entry c * vstride + i of v (c * astride + i of a); what is written here is indexed by
+ * the SLOT c * n + oidx[i] (oidx NULL: i), the index the result is reported under.  place[c] (NULL: none) is a reported index
+ * whose slot receives T_c itself, -1 for no such slot, -2 for a problem that is skipped (all its slots come back empty).
+ *
+ * phase 0, classify and size, one lane per entry (a wave's 64 entries are of one problem).  With b1 = bits(P) + bits(V) and
+ *   b2 = bits(T) + bits(A) (0 for a term with a zero factor) |P V - T A| < 2^nb, nb = max(b1, b2) + 1, nd = ceil(nb / 32) its
+ *   digits; an exact quotient is below 2^(nb - bits(D) + 1).  w = the digits the slot owns in the staging slab: those of the
+ *   quotient's bound (of nd without D, of T_c in the placed slot); the widest to wmax[0], the widest two's-complement numerator
+ *   of the memory path (nd + 1) to wmax[1], one atomic each per wave.  cls = path | class << 2:
+ *     path 0: both terms are zero (or the slot is placed or skipped): nothing is computed;
+ *     path 1: both products of at most four digits by the factors' digit counts and D of at most two: a lane;
+ *     path 2: nd <= 256: a wavefront in registers, class = ceil(nd / 64) = the D of WR<D>;
+ *     path 3: above: a wavefront through its scratch in global memory.
+ *   The entries by path go to paths[0 .. 3].
+ * phase 1, the lane pass, one lane per entry: both products as 128-bit numbers, the signed sum as sign, 128-bit magnitude and
+ *   carry; the division 2-adic (slip_inv64, one Newton step to 128 bits), exact iff the low ctz(D) bits of the numerator are
+ *   zero and the 192-bit product of the quotient and D's odd part has nothing above the numerator's 128 bits but its carry.
+ * phase 2, the wave pass, one wavefront per entry, wave-uniform.  Registers: the products by slip_check_mac_reg, the
+ *   subtraction in sign and magnitude (no wrap: nd digits fit the class), then wr_div_hensel on the numerator shifted by
+ *   ctz(D), computed to W = its digits + 1 -- in WR<D + 1> when that digit is not there.  Memory: the sum modulo B^Wp in two's
+ *   complement (wb_mul_lo, wb_addsub), the inverse of D's odd part by wb_inv_extend to W digits, one wb_mul_lo.
+ *   Exactness, both ways: the numerator's trailing zero bits cover those of D, and the W-digit 2-adic quotient q has no digit
+ *   at or above W - len(D_odd): then q * D_odd < B^W is congruent to the numerator modulo B^W and below it, hence equal; an
+ *   exact quotient of a numerator below B^(W-1) by D_odd >= B^(len - 1) passes.  An inexact entry keeps length 0 and counts in
+ *   ninexact[c], one atomic per wave.
+ * phase 3, one wavefront per problem: T_c copied into the slot place[c] names, its record set.
+ * phase 4 (the fused step, before phase 0), one lane per problem: from best[c] of the selection the records of P_c = the a
+ *   numerator and T_c = the x numerator of the winner (in place in the solve's output) and place[c] = best[c]; best[c] < 0
+ *   gives empty records and place -2. */
+struct SlipPivotArgs {
+    int32_t n, nprob, phase;
+    int64_t vstride, astride;
+    const int32_t *vlen; const int64_t *voff; const uint64_t *vlimbs;              /* v: signed digit counts, limb offsets   */
+    const int32_t *alen; const int64_t *aoff; const uint64_t *alimbs;              /* a likewise                             */
+    const int32_t *plen; const int64_t *poff; const uint64_t *plimbs;              /* P_c: entry c                           */
+    const int32_t *tlen; const int64_t *toff; const uint64_t *tlimbs;              /* T_c: entry c                           */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* D_c: entry c; dlen NULL: no division   */
+    const int32_t *oidx, *pos;                                                     /* reported index of entry i; its inverse */
+    const int32_t *place;                                                          /* per problem, or NULL                   */
+    int32_t *cls, *w, *wmax;                                                       /* by slot; wmax: two widths              */
+    const int64_t *soff; uint64_t *stage; int32_t *rlen;                           /* staging slab, signed digit counts      */
+    dig_t *scratch; int32_t wcap, wscr;                                            /* per wave wscr digits: 7 * wcap, >= 328 */
+    int32_t *ninexact;                                                             /* per problem                            */
+    const int32_t *best;                                                           /* phase 4                                */
+    int32_t *wplen, *wtlen, *wplace; int64_t *wpoff, *wtoff;
+    unsigned long long *paths;
+};
+
+/* the operands of entry i of problem c */
+struct SlipPivotEnt { SlipBoundOp P, V, T, A, Dn; int s1, s2, hasd; };
+SLIP_DEV SlipPivotEnt slip_pivot_ent(const SlipPivotArgs &A, int c, int i)
+{
+    SlipPivotEnt E;
+    E.P = slip_bound_op(A.plen, A.poff, A.plimbs, c);
+    E.T = slip_bound_op(A.tlen, A.toff, A.tlimbs, c);
+    E.V = slip_bound_op(A.vlen, A.voff, A.vlimbs, (int64_t) c * A.vstride + i);
+    E.A = slip_bound_op(A.alen, A.aoff, A.alimbs, (int64_t) c * A.astride + i);
+    E.hasd = A.dlen != (const int32_t *) 0;
+    E.Dn.p = (const dig_t *) 0; E.Dn.l = 0; E.Dn.s = 1;
+    if (E.hasd) E.Dn = slip_bound_op(A.dlen, A.doff, A.dlimbs, c);
+    E.s1 = E.P.s * E.V.s; E.s2 = -E.T.s * E.A.s;                   /* the value is s1 |P||V| + s2 |T||A| */
+    return E;
+}
+
+/* lane pass: the entry's quotient into out (at most cap digits); its signed digit count, *bad set when it is not exact */
+SLIP_DEV int slip_pivot_entry_lane(const SlipPivotEnt &E, uint64_t *out, int cap, int *bad)
+{
+    const slip_u128 X = E.s1 ? slip_bound_load128(E.P) * slip_bound_load128(E.V) : 0, Y = E.s2 ? slip_bound_load128(E.T) * slip_bound_load128(E.A) : 0;
+    slip_u128 mag; uint32_t top = 0; int sg;
+    if (E.s1 == E.s2 || !E.s1 || !E.s2) { mag = X + Y; top = mag < X ? 1u : 0u; sg = E.s1 ? E.s1 : E.s2; }
+    else if (X >= Y) { mag = X - Y; sg = X == Y ? 0 : E.s1; }
+    else { mag = Y - X; sg = E.s2; }
+    *bad = 0;
+    if (sg == 0) return 0;
+    if (E.hasd) {
+        const uint64_t d = slip_bound_load128(E.Dn) & 0xFFFFFFFFFFFFFFFFull;
+        const int z = slip_ctz64(d);
+        const uint64_t dodd = d >> z;
+        if (z && ((uint64_t) mag & ((1ull << z) - 1ull))) { *bad = 1; return 0; }
+        if (z) { mag = (mag >> z) | ((slip_u128) top << (128 - z)); top = 0; }
+        if (dodd != 1) {                                           /* (a unit odd part: the shifted numerator, carry and all, is the quotient) */
+            slip_u128 inv = (slip_u128) slip_inv64(dodd);
+            inv = inv * ((slip_u128) 2 - (slip_u128) dodd * inv);
+            const slip_u128 q = mag * inv;
+            /* bits 128 .. 191 of q * dodd: the carry of the numerator and nothing else (dodd >= 3: q itself fits 128 bits) */
+            const uint64_t hi = (uint64_t)(((slip_u128)(uint64_t)(q >> 64) * dodd + (((slip_u128)(uint64_t) q * dodd) >> 64)) >> 64);
+            if (hi != top) { *bad = 1; return 0; }
+            mag = q; top = 0;
+        }
+        sg *= E.Dn.s;
+    }
+    const uint64_t l0 = (uint64_t) mag, l1 = (uint64_t)(mag >> 64);
+    const int len = top ? 5 : l1 ? (l1 >> 32 ? 4 : 3) : (l0 >> 32 ? 2 : 1);
+    if (len > cap) { *bad = 1; return 0; }
+    out[0] = l0;
+    if (len > 2) out[1] = l1;
+    if (len > 4) out[2] = top;
+    return sg < 0 ? -len : len;
+}
+
+/* wave pass, registers: the magnitude N (ln digits, ln < 64*D) over D_c into out; the quotient's digits, -1 when not exact */
+template <int D> SLIP_DEV int slip_pivot_div_reg(const WR<D> &N, const SlipBoundOp &Dv, dig_t *out, int cap, dig_t *scratch)
+{
+    const int z = wb_ctz(Dv.p, Dv.l), ldo = (wb_bits(Dv.p, Dv.l) - z + 31) >> 5;
+    int tz = 0;
+#pragma unroll
+    for (int q = D - 1; q >= 0; q--) {
+        const uint64_t nz = slip_ballot(N.d[q] != 0);
+        if (nz) { const int t = slip_ctz64(nz); tz = 32 * (64 * q + t) + slip_ctz32(slip_readlane(N.d[q], t)); }
+    }
+    if (tz < z) return -1;
+    const WR<D> Ns = wr_shr<D>(N, z, scratch);
+    const int W = wr_len<D>(Ns) + 1;
+    if (W - ldo <= 0) return -1;                                   /* D_odd exceeds the numerator */
+    const WR<D> Q = wr_div_hensel<D>(Ns, W, wr_load_shr<D>(Dv.p, Dv.l, z));
+    const int lq = wr_len<D>(Q);
+    if (lq > W - ldo || lq > cap) return -1;
+    wr_store<D>(out, Q, (lq + 1) & ~1);
+    return lq;
+}
+
+/* wave pass, registers: both products below B^(64*D) and their signed sum too; the entry's signed digit count */
+template <int D> SLIP_DEV int slip_pivot_entry_reg(const SlipPivotEnt &E, dig_t *out, int cap, dig_t *scratch, int *bad)
+{
+    const WR<D> X = E.s1 ? slip_bound_mul_reg<D>(E.P, E.V) : wr_zero<D>(), Y = E.s2 ? slip_bound_mul_reg<D>(E.T, E.A) : wr_zero<D>();
+    WR<D> N; int sg;
+    if (!E.s1 || !E.s2 || E.s1 == E.s2) { N = wr_addsub<D>(X, Y, 0); sg = E.s1 ? E.s1 : E.s2; }
+    else {
+        const int cm = slip_bound_cmp_reg<D>(X, Y);
+        sg = cm > 0 ? E.s1 : cm < 0 ? E.s2 : 0;
+        N = cm >= 0 ? wr_addsub<D>(X, Y, 1) : wr_addsub<D>(Y, X, 1);
+    }
+    *bad = 0;
+    if (sg == 0) return 0;
+    int len = wr_len<D>(N);
+    if (!E.hasd) {
+        if (len > cap) { *bad = 1; return 0; }
+        wr_store<D>(out, N, (len + 1) & ~1);
+        return sg < 0 ? -len : len;
+    }
+    if (len < 64 * D) len = slip_pivot_div_reg<D>(N, E.Dn, out, cap, scratch);
+    else {
+        WR<D + 1> Nw;
+#pragma unroll
+        for (int q = 0; q < D; q++) Nw.d[q] = N.d[q];
+        Nw.d[D] = 0u;
+        len = slip_pivot_div_reg<D + 1>(Nw, E.Dn, out, cap, scratch);
+    }
+    if (len < 0) { *bad = 1; return 0; }
+    return sg * E.Dn.s < 0 ? -len : len;
+}
+
+/* wave pass, memory: the same modulo B^Wp, Wp even and at most wcap, on seven buffers of wcap digits */
+SLIP_DEV int slip_pivot_entry_wide(const SlipPivotEnt &E, int Wp, dig_t *buf, int wcap, dig_t *out, int cap, int *bad)
+{
+    dig_t *num = buf, *prod = buf + wcap, *T = prod + wcap, *Dd = T + wcap, *inv = Dd + wcap, *e1 = inv + wcap, *e2 = e1 + wcap;
+    for (int k = slip_lane(); k < Wp; k += SLIP_WAVE) num[k] = 0u;
+    slip_wave_sync();
+    if (E.s1) { wb_mul_lo(prod, E.P.p, E.P.l, E.V.p, E.V.l, Wp); wb_addsub(num, num, Wp, prod, Wp, Wp, E.s1 < 0); }
+    if (E.s2) { wb_mul_lo(prod, E.T.p, E.T.l, E.A.p, E.A.l, Wp); wb_addsub(num, num, Wp, prod, Wp, Wp, E.s2 < 0); }
+    const int neg = (int)(num[Wp - 1] >> 31);
+    if (neg) wb_addsub(num, (const dig_t *) 0, 1, num, Wp, Wp, 1, 0u);
+    const int ln = wb_len(num, Wp);
+    *bad = 0;
+    if (ln == 0) return 0;
+    if (!E.hasd) {
+        if (ln > cap) { *bad = 1; return 0; }
+        wb_copy_pad(out, num, ln);
+        return neg ? -ln : ln;
+    }
+    const int z = wb_ctz(E.Dn.p, E.Dn.l), ldo = (wb_bits(E.Dn.p, E.Dn.l) - z + 31) >> 5;
+    if (wb_ctz(num, ln) < z) { *bad = 1; return 0; }
+    wb_copy_shr(T, num, ln, z, ln);
+    const int lt = wb_len(T, ln), W = lt + 1;                     /* W <= ln + 1 <= Wp */
+    if (W - ldo <= 0) { *bad = 1; return 0; }
+    wb_copy_shr(Dd, E.Dn.p, E.Dn.l, z, ldo);
+    wb_inv_extend(inv, 0, W, Dd, ldo, e1, e2);
+    wb_mul_lo(prod, T, lt, inv, W, W);
+    const int lq = wb_len(prod, W);
+    if (lq > W - ldo || lq > cap) { *bad = 1; return 0; }
+    wb_copy_pad(out, prod, lq);
+    return (neg ? -1 : 1) * E.Dn.s < 0 ? -lq : lq;
+}
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_pivot_kernel(SlipPivotArgs A)
+#else
+static void slip_pivot_body(SlipPivotArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    if (A.phase == 4) {
+        const int64_t rounds = ((int64_t) A.nprob + SLIP_WAVE - 1) / SLIP_WAVE;
+        for (int64_t r = wave0; r < rounds; r += nwaves) {
+            const int64_t c = r * SLIP_WAVE + lane;
+            if (c >= A.nprob) continue;
+            const int32_t b = A.best[c];
+            const int64_t p = b < 0 ? 0 : (A.pos ? A.pos[b] : b), ev = c * A.vstride + p, ea = c * A.astride + p;
+            A.wplen[c] = b < 0 ? 0 : A.alen[ea]; A.wpoff[c] = b < 0 ? 0 : A.aoff[ea];
+            A.wtlen[c] = b < 0 ? 0 : A.vlen[ev]; A.wtoff[c] = b < 0 ? 0 : A.voff[ev];
+            A.wplace[c] = b < 0 ? -2 : b;
+        }
+        return;
+    }
+    if (A.phase <= 1) {
+        const int64_t rpp = ((int64_t) A.n + SLIP_WAVE - 1) / SLIP_WAVE, rounds = rpp * A.nprob;
+        uint32_t wall = 0, wwave = 0;
+        unsigned long long cnt[4] = {0, 0, 0, 0};
+        for (int64_t r = wave0; r < rounds; r += nwaves) {
+            const int c = (int)(r / rpp);
+            const int64_t i = (r - (int64_t) c * rpp) * SLIP_WAVE + lane;
+            const int idx = i < A.n ? (A.oidx ? A.oidx[i] : (int) i) : 0;
+            const int64_t slot = (int64_t) c * A.n + idx;
+            if (A.phase == 1) {
+                const int take = i < A.n && (A.cls[slot] & 3) == 1;
+                int bad = 0;
+                if (take) {
+                    const SlipPivotEnt E = slip_pivot_ent(A, c, (int) i);
+                    A.rlen[slot] = slip_pivot_entry_lane(E, A.stage + A.soff[slot], A.w[slot], &bad);
+                }
+                const uint64_t nb = slip_ballot(bad);
+                if (nb && lane == 0) slip_atomic_add_i32(A.ninexact + c, slip_popc64(nb));
+                continue;
+            }
+            uint32_t W = 0, Ww = 0;
+            int path = -1;
+            if (i < A.n) {
+                const int pl = A.place ? A.place[c] : -1;
+                int code = 0;
+                path = 0;
+                if (pl == idx) W = (uint32_t) slip_bound_op(A.tlen, A.toff, A.tlimbs, c).l;
+                else if (pl != -2) {
+                    const SlipPivotEnt E = slip_pivot_ent(A, c, (int) i);
+                    if ((E.s1 || E.s2) && (!E.hasd || E.Dn.l)) {           /* (a zero D_c, which the host refuses: nothing) */
+                        const int b1 = E.s1 ? wb_bits(E.P.p, E.P.l) + wb_bits(E.V.p, E.V.l) : 0;
+                        const int b2 = E.s2 ? wb_bits(E.T.p, E.T.l) + wb_bits(E.A.p, E.A.l) : 0;
+                        const int w1 = E.s1 ? E.P.l + E.V.l : 0, w2 = E.s2 ? E.T.l + E.A.l : 0;
+                        const int nb = (b1 > b2 ? b1 : b2) + 1, nd = (nb + 31) >> 5;
+                        const int qb = E.hasd ? nb - wb_bits(E.Dn.p, E.Dn.l) + 1 : nb;
+                        W = qb > 0 ? (uint32_t)((qb + 31) >> 5) : 1u;
+                        path = w1 <= 4 && w2 <= 4 && E.Dn.l <= 2 ? 1 : nd <= 256 ? 2 : 3;
+                        if (path == 2) code = ((nd + 63) >> 6) << 2;
+                        if (path == 3) Ww = (uint32_t)(nd + 1);
+                        code |= path;
+                    }
+                }
+                A.cls[slot] = code; A.w[slot] = (int32_t) W; A.rlen[slot] = 0;
+            }
+            for (int k = 0; k < 4; k++) cnt[k] += (unsigned long long) slip_popc64(slip_ballot(path == k));
+            W = slip_wave_max_u32(W); Ww = slip_wave_max_u32(Ww);
+            if (W > wall) wall = W;
+            if (Ww > wwave) wwave = Ww;
+        }
+        if (A.phase == 0 && lane == 0) {
+            if (wall) slip_atomic_max_i32(A.wmax + 0, (int32_t) wall);
+            if (wwave) slip_atomic_max_i32(A.wmax + 1, (int32_t) wwave);
+            for (int k = 0; k < 4; k++) if (cnt[k]) slip_atomic_add_u64(A.paths + k, cnt[k]);
+        }
+        return;
+    }
+    if (A.phase == 2) {
+        dig_t *buf = A.scratch + wave0 * (int64_t) A.wscr;
+        const int64_t items = (int64_t) A.n * A.nprob;
+        for (int64_t e = wave0; e < items; e += nwaves) {
+            const int c = (int)(e / A.n), i = (int)(e - (int64_t) c * A.n);
+            const int64_t slot = (int64_t) c * A.n + (A.oidx ? A.oidx[i] : i);
+            const int code = A.cls[slot], path = code & 3, cls = code >> 2;
+            if (path < 2) continue;
+            const SlipPivotEnt E = slip_pivot_ent(A, c, i);
+            const int cap = A.w[slot];
+            dig_t *out = (dig_t *)(A.stage + A.soff[slot]);
+            int len, bad = 0;
+            if (path == 2 && cls == 1) len = slip_pivot_entry_reg<1>(E, out, cap, buf, &bad);
+            else if (path == 2 && cls == 2) len = slip_pivot_entry_reg<2>(E, out, cap, buf, &bad);
+            else if (path == 2 && cls == 3) len = slip_pivot_entry_reg<3>(E, out, cap, buf, &bad);
+            else if (path == 2) len = slip_pivot_entry_reg<4>(E, out, cap, buf, &bad);
+            else {
+                /* nd + 1 digits in whole limbs: at most wcap, the host sized it from wmax */
+                const int b1 = E.s1 ? wb_bits(E.P.p, E.P.l) + wb_bits(E.V.p, E.V.l) : 0, b2 = E.s2 ? wb_bits(E.T.p, E.T.l) + wb_bits(E.A.p, E.A.l) : 0;
+                const int Wp = ((((b1 > b2 ? b1 : b2) + 1 + 31) >> 5) + 2) & ~1;
+                len = slip_pivot_entry_wide(E, Wp, buf, A.wcap, out, cap, &bad);
+            }
+            if (lane == 0) {
+                A.rlen[slot] = len;
+                if (bad) slip_atomic_add_i32(A.ninexact + c, 1);
+            }
+            slip_wave_sync();
+        }
+        return;
+    }
+    for (int64_t c = wave0; c < A.nprob; c += nwaves) {
+        const int pl = A.place ? A.place[c] : -1;
+        if (pl < 0) continue;
+        const int64_t slot = c * A.n + pl;
+        const SlipBoundOp Tv = slip_bound_op(A.tlen, A.toff, A.tlimbs, c);
+        wb_copy_pad((dig_t *)(A.stage + A.soff[slot]), Tv.p, Tv.l);
+        if (lane == 0) A.rlen[slot] = Tv.s * Tv.l;
+    }
+}
+
 /* Nonbasic states and reference weights in exact pricing (slip_hip_factor_price_states, slip_hip_price_select):
  * the records slip_ratio_kernel selects on, formed from the numerators X_j (and A_j, nside 2) of nprob problems over one
  * nonzero signed d_c each, the state of every column (0 never eligible, 1 at its lower bound, 2 at its upper bound, 3 free)
@@ -2386,6 +2693,9 @@ struct slip_hip_factor {
     /* slip_hip_factor_price_states: device time of the last call (the classify, offset and square passes, the selection), the
      * eligible entries by the path that settled them and the path counts of the selection */
     double states_ms[2]; int64_t states_paths[8];
+    /* slip_hip_factor_solve_update / _step: device time of the last call (the classify, offset and form passes, the selection
+     * of a step), the entries by the path that formed them and the inexact ones */
+    double update_ms[2]; int64_t update_paths[8];
     /* slip_hip_factor_rewind / _replace_column: the host copy of q; the storage of the resident A -- annz / alimbs are its
      * LIVE entries and limbs, Acap_nz / Acap_nl what dAi, dAlen, dAoff / dAlimbs can hold, Anl_used the limbs of the slab
      * handed out (live ones and the dead ones of replaced columns: new limbs are appended there), A0_nz / A0_nl the initial
@@ -5531,6 +5841,319 @@ extern "C" int slip_hip_bound_paths(int64_t out[8])
 {
     if (!out) return SLIP_HIP_INCORRECT_INPUT;
     memcpy(out, slip_bound_paths_last, sizeof slip_bound_paths_last);
+    return SLIP_HIP_OK;
+}
+
+/* ---- exact pivot update: the numerators of the next basic solution (or of the next duals) from those the ratio test already
+ * holds, R = (P V - T A) / D per entry, with no second substitution (no counterpart in the reference; kernel:
+ * slip_pivot_kernel) ---- */
+
+/* the counts of this thread's last handle-less update */
+static thread_local int64_t slip_pivot_paths_last[8];
+
+/* the device operands of an update: v and a of problem c from entry c * stride on, P_c, T_c and D_c (d.len NULL: no division),
+ * the map from an entry to the index reported and its inverse (both NULL: the identity), place (NULL: none) */
+struct SlipPivotIn {
+    int32_t n, nprob;
+    SlipDevRecs v, a, p, t, d; int64_t vstride, astride;
+    const int32_t *oidx, *pos, *place;
+};
+
+/* one update on the device.  ninexact: nprob host integers; the result: one compact malloc'ed slab of n * nprob entries in
+ * reported order.  ms: the classify, offset and form passes; paths: [0 .. 3] the entries by path, [4] the inexact ones. */
+static int pivot_core(const SlipPivotIn &I, int32_t *ninexact, int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                      hipStream_t stream, double *ms, int64_t paths[8])
+{
+    const int32_t n = I.n, nprob = I.nprob;
+    const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE;
+    int32_t *dcls = NULL, *dw = NULL, *drl = NULL, *dwmax = NULL, *dnin = NULL; int64_t *dso = NULL;
+    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, *bsum = NULL, hpaths[4] = {0, 0, 0, 0};
+    int32_t hwmax[2] = {0, 0};
+    int32_t *hnin = (int32_t *) malloc((size_t) nprob * 4), *ol = (int32_t *) malloc((size_t) ne * 4);
+    uint64_t *out = NULL; int64_t on = 0;                  /* the result's limbs so far: every group's slab is appended */
+    int rc = !hnin || !ol ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    *ms = 0; memset(paths, 0, 8 * sizeof(int64_t));
+    A_(dev_alloc(&dcls, ne)); A_(dev_alloc(&dw, ne)); A_(dev_alloc(&drl, ne)); A_(dev_alloc(&dso, ne));
+    A_(dev_alloc(&dwmax, 2)); A_(dev_alloc(&dpaths, 4)); A_(dev_alloc(&dnin, nprob));
+    HIP_(hipMemsetAsync(dwmax, 0, 8, stream)); HIP_(hipMemsetAsync(dpaths, 0, 32, stream)); HIP_(hipMemsetAsync(dnin, 0, (size_t) nprob * 4, stream));
+    SlipPivotArgs A; memset(&A, 0, sizeof A);
+    A.n = n; A.vstride = I.vstride; A.astride = I.astride; A.oidx = I.oidx; A.pos = I.pos;
+    A.vlimbs = I.v.limbs; A.alimbs = I.a.limbs; A.plimbs = I.p.limbs; A.tlimbs = I.t.limbs; A.dlimbs = I.d.limbs;
+    A.wmax = dwmax; A.paths = dpaths;
+    /* the problems c0 .. c0 + nv of every per-problem and per-entry array */
+    auto slice = [&](int64_t c0, int64_t nv, int phase) {
+        A.nprob = (int32_t) nv; A.phase = phase;
+        A.vlen = I.v.len + c0 * I.vstride; A.voff = I.v.off + c0 * I.vstride;
+        A.alen = I.a.len + c0 * I.astride; A.aoff = I.a.off + c0 * I.astride;
+        A.plen = I.p.len + c0; A.poff = I.p.off + c0; A.tlen = I.t.len + c0; A.toff = I.t.off + c0;
+        A.dlen = I.d.len ? I.d.len + c0 : NULL; A.doff = I.d.len ? I.d.off + c0 : NULL;
+        A.place = I.place ? I.place + c0 : NULL; A.ninexact = dnin + c0;
+        A.cls = dcls + c0 * n; A.w = dw + c0 * n; A.rlen = drl + c0 * n; A.soff = dso + c0 * n;
+    };
+    if (!rc) {                                             /* the paths and widths of all entries, the widest of them */
+        SlipTimed timed;
+        slice(0, nprob, 0);
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(pivot, wave_blocks(rpp * nprob), stream, A));
+        A_(timed.end(stream, ms));
+    }
+    DOWN_(hwmax, dwmax, 8);
+    const int64_t wcap = hwmax[0] > 1 ? ((int64_t) hwmax[0] + 1) & ~(int64_t) 1 : 2, scap = ((int64_t) hwmax[1] + 1) & ~(int64_t) 1;
+    if (!rc && (wcap > (1 << 28) || scap > (1 << 27))) rc = SLIP_HIP_OUT_OF_MEMORY;
+    int64_t group = rc ? 1 : product_stage_limbs() / ((int64_t) n * (wcap / 2));       /* problems staged together */
+    if (group < 1) group = 1;
+    if (group > nprob) group = nprob;
+    /* per wave: the 64 * 5 + 2 digits a register shift goes through, or the seven buffers of the memory path */
+    const int64_t wscr = 7 * scap > 328 ? 7 * scap : 328;
+    const int64_t wblocks = fit_scratch(wave_blocks(ne), wscr), sblocks = offscan_blocks((int64_t) n * group);
+    A_(dev_alloc(&bsum, sblocks));
+    A_(dev_alloc(&dscr, wblocks * SERVICE_WAVES * wscr));
+    A.scratch = dscr; A.wcap = (int32_t) scap; A.wscr = (int32_t) wscr;
+    for (int64_t c0 = 0; c0 < nprob && !rc; c0 += group) {
+        const int64_t nv = c0 + group <= nprob ? group : nprob - c0, cnt = (int64_t) n * nv;
+        uint64_t *dstage = NULL; int64_t total = 0;
+        double t = 0;
+        {                                                  /* the staging offsets from the widths */
+            SlipTimed timed;
+            A_(timed.begin(stream));
+            A_(offscan_run(cnt, dw + c0 * n, dso + c0 * n, bsum, sblocks, stream));
+            A_(timed.end(stream, &t));
+            *ms += t;
+        }
+        A_(offscan_total(bsum, sblocks, &total, stream));
+        if (!rc && total > cnt * (wcap / 2)) rc = SLIP_HIP_DEVICE_ERROR;           /* (the widths' bound: the host's own figure) */
+        A_(dev_alloc(&dstage, total));
+        if (!rc) {                                         /* the lane pass, the wave pass, the placed entries */
+            SlipTimed timed;
+            A.stage = dstage;
+            A_(timed.begin(stream));
+            slice(c0, nv, 1); A_(SERVICE_LAUNCH(pivot, wave_blocks(rpp * nv), stream, A));
+            slice(c0, nv, 2); A_(SERVICE_LAUNCH(pivot, wave_blocks(cnt) < wblocks ? wave_blocks(cnt) : wblocks, stream, A));
+            if (I.place) { slice(c0, nv, 3); A_(SERVICE_LAUNCH(pivot, wave_blocks(nv), stream, A)); }
+            A_(timed.end(stream, &t));
+            *ms += t;
+        }
+        int32_t *gl = NULL; uint64_t *gv = NULL; int64_t gn = 0;
+        A_(pack_download(cnt, drl + c0 * n, dso + c0 * n, dstage, 0, &gl, &gv, &gn, stream));
+        if (!rc && c0 == 0 && nv == nprob) { out = gv; on = gn; gv = NULL; }       /* one group: its slab is the result */
+        else if (!rc) {
+            uint64_t *grown = (uint64_t *) realloc(out, (size_t)(on + gn > 0 ? on + gn : 1) * 8);
+            if (!grown) rc = SLIP_HIP_OUT_OF_MEMORY;
+            else { out = grown; memcpy(out + on, gv, (size_t) gn * 8); on += gn; }
+        }
+        if (!rc) memcpy(ol + c0 * n, gl, (size_t) cnt * 4);
+        free(gl); free(gv);
+        dev_free(dstage);
+    }
+    DOWN_(hpaths, dpaths, 32); DOWN_(hnin, dnin, (size_t) nprob * 4);
+    if (!rc) {
+        memcpy(ninexact, hnin, (size_t) nprob * 4);
+        for (int k = 0; k < 4; k++) paths[k] = (int64_t) hpaths[k];
+        for (int32_t c = 0; c < nprob; c++) paths[4] += hnin[c];
+        *rlen_out = ol; *rlimbs_out = out; *rnl_out = on;
+        ol = NULL; out = NULL;
+    }
+    free(hnin); free(ol); free(out);
+    dev_free(dcls); dev_free(dw); dev_free(drl); dev_free(dso); dev_free(dwmax); dev_free(dpaths); dev_free(dnin);
+    dev_free(bsum); dev_free(dscr);
+    return rc;
+}
+
+/* a slab the host has laid out (s) on the device */
+static int pivot_upload(int64_t count, const SlipSlab &s, const uint64_t *limbs, int32_t **dlen, int64_t **doff, uint64_t **dlimbs)
+{
+    int rc = 0;
+    A_(dev_alloc(dlen, count)); A_(dev_alloc(doff, count)); A_(dev_alloc(dlimbs, s.total));
+    UP_(*dlen, s.dig, (size_t) count * 4); UP_(*doff, s.off, (size_t) count * 8); UP_(*dlimbs, limbs, (size_t) s.total * 8);
+    return rc;
+}
+
+/* place: nprob indices in [-1, n), or NULL */
+static int pivot_place_ok(const int32_t *place, int32_t nprob, int32_t n)
+{
+    if (place) for (int32_t c = 0; c < nprob; c++) if (place[c] < -1 || place[c] >= n) return 0;
+    return 1;
+}
+
+extern "C" int slip_hip_pivot_update(int32_t n, int32_t nprob,
+                                     const int32_t *vlen, const uint64_t *vlimbs, int64_t v_limbs,
+                                     const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                                     const int32_t *plen, const uint64_t *plimbs, int64_t p_limbs,
+                                     const int32_t *tlen, const uint64_t *tlimbs, int64_t t_limbs,
+                                     const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                     const int32_t *place, int32_t *ninexact,
+                                     int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream_v)
+{
+    if (n <= 0 || nprob < 1 || nprob > (1 << 29) || !vlen || !vlimbs || !alen || !alimbs || !plen || !plimbs || !tlen || !tlimbs ||
+        !dlen != !dlimbs || !ninexact || !rlen_out || !rlimbs_out || !rnl_out || !pivot_place_ok(place, nprob, n))
+        return SLIP_HIP_INCORRECT_INPUT;
+    const int64_t ne = (int64_t) n * nprob;
+    SlipSlab vs, as, ps, ts, ds; memset(&vs, 0, sizeof vs); memset(&as, 0, sizeof as); memset(&ps, 0, sizeof ps); memset(&ts, 0, sizeof ts); memset(&ds, 0, sizeof ds);
+    int32_t *dvl = NULL, *dal = NULL, *dpl = NULL, *dtl = NULL, *ddl = NULL, *dplace = NULL;
+    int64_t *dvo = NULL, *dao = NULL, *dpo = NULL, *dto = NULL, *ddo = NULL; uint64_t *dvv = NULL, *dav = NULL, *dpv = NULL, *dtv = NULL, *ddv = NULL;
+    /* (every slab is checked against its capacity before a limb of it is read) */
+    int rc = slab_prepare(ne, vlen, vlimbs, v_limbs, &vs);
+    A_(slab_prepare(ne, alen, alimbs, a_limbs, &as));
+    A_(slab_prepare(nprob, plen, plimbs, p_limbs, &ps));
+    A_(slab_prepare(nprob, tlen, tlimbs, t_limbs, &ts));
+    if (dlen) {
+        A_(slab_prepare(nprob, dlen, dlimbs, d_limbs, &ds));
+        for (int32_t c = 0; c < nprob && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    }
+    A_(need_device());
+    A_(pivot_upload(ne, vs, vlimbs, &dvl, &dvo, &dvv)); A_(pivot_upload(ne, as, alimbs, &dal, &dao, &dav));
+    A_(pivot_upload(nprob, ps, plimbs, &dpl, &dpo, &dpv)); A_(pivot_upload(nprob, ts, tlimbs, &dtl, &dto, &dtv));
+    if (dlen) A_(pivot_upload(nprob, ds, dlimbs, &ddl, &ddo, &ddv));
+    if (place) { A_(dev_alloc(&dplace, nprob)); UP_(dplace, place, (size_t) nprob * 4); }
+    SlipPivotIn I; memset(&I, 0, sizeof I);
+    I.n = n; I.nprob = nprob; I.vstride = n; I.astride = n; I.place = dplace;
+    I.v.len = dvl; I.v.off = dvo; I.v.limbs = dvv; I.a.len = dal; I.a.off = dao; I.a.limbs = dav;
+    I.p.len = dpl; I.p.off = dpo; I.p.limbs = dpv; I.t.len = dtl; I.t.off = dto; I.t.limbs = dtv;
+    I.d.len = ddl; I.d.off = ddo; I.d.limbs = ddv;
+    double ms; int64_t paths[8];
+    A_(pivot_core(I, ninexact, rlen_out, rlimbs_out, rnl_out, (hipStream_t) stream_v, &ms, paths));
+    if (!rc) memcpy(slip_pivot_paths_last, paths, sizeof paths);
+    dev_free(dvl); dev_free(dvo); dev_free(dvv); dev_free(dal); dev_free(dao); dev_free(dav); dev_free(dpl); dev_free(dpo); dev_free(dpv);
+    dev_free(dtl); dev_free(dto); dev_free(dtv); dev_free(ddl); dev_free(ddo); dev_free(ddv); dev_free(dplace);
+    slab_free(&vs); slab_free(&as); slab_free(&ps); slab_free(&ts); slab_free(&ds);
+    return rc;
+}
+
+extern "C" int slip_hip_pivot_update_paths(int64_t out[8])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_pivot_paths_last, sizeof slip_pivot_paths_last);
+    return SLIP_HIP_OK;
+}
+
+/* both fused forms.  step 0 (slip_hip_factor_solve_update): P, T (host slabs ps, ts) and place from the caller.  step 1
+ * (slip_hip_factor_step): the selection of slip_hip_factor_ratio_test on the solve's output, then P, T and place from its
+ * winners (phase 4 of the kernel) and the slab of the new denominators P_c. */
+static int update_on_handle(slip_hip_factor *f, int step, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                            const SlipSlab *ps, const uint64_t *plimbs, const SlipSlab *ts, const uint64_t *tlimbs, const int32_t *place,
+                            int32_t sense, const int32_t *key, int32_t *best, int32_t *nties, int32_t *neligible, int32_t *ninexact,
+                            int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                            int32_t **dlen_out, uint64_t **dlimbs_out, int64_t *dnl_out, hipStream_t stream)
+{
+    if (!transpose && f->factors_only) return SLIP_HIP_INCORRECT_INPUT;             /* no q behind such a handle */
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
+    if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
+    const int32_t n = f->n;
+    SlipSolveOut o;
+    TRY_(solve_device(f, transpose, 2 * nprob, blen, blimbs, stream, &o));
+    int32_t *ddlen = NULL, *doidx = NULL, *dpos = NULL, *hidx = NULL, *dpl = NULL, *dtl = NULL, *dplace = NULL, *dbest = NULL;
+    int64_t *ddoff = NULL, *dpo = NULL, *dto = NULL; uint64_t *dpv = NULL, *dtv = NULL;
+    int32_t *hbest = NULL, *hties = NULL, *helig = NULL, *rl = NULL, *nl = NULL; uint64_t *rv = NULL, *nv = NULL; int64_t rn = 0, nn = 0;
+    int32_t dmaxdig = 0;
+    int rc = 0;
+    A_(det_records(f, nprob, &ddlen, &ddoff, &dmaxdig));
+    if (!rc && transpose) {                                /* position p of the transposed solve is row i, pinv[i] = p */
+        hidx = (int32_t *) malloc((size_t) n * 4);
+        if (!hidx) rc = SLIP_HIP_OUT_OF_MEMORY;
+        else for (int32_t i = 0; i < n; i++) hidx[f->tpinv[i]] = i;
+        A_(dev_alloc(&doidx, n)); UP_(doidx, hidx, (size_t) n * 4);
+        A_(dev_alloc(&dpos, n)); UP_(dpos, f->tpinv, (size_t) n * 4);
+    }
+    SlipPivotIn I; memset(&I, 0, sizeof I);
+    I.n = n; I.nprob = nprob; I.oidx = doidx; I.pos = dpos; I.vstride = I.astride = 2 * (int64_t) n;
+    I.v.len = o.olen; I.v.off = o.ooff; I.v.limbs = o.olimbs; I.a.len = o.olen + n; I.a.off = o.ooff + n; I.a.limbs = o.olimbs;
+    I.d.len = ddlen; I.d.off = ddoff; I.d.limbs = f->P.Llimbs;
+    A_(dev_alloc(&dpl, nprob)); A_(dev_alloc(&dpo, nprob)); A_(dev_alloc(&dtl, nprob)); A_(dev_alloc(&dto, nprob));
+    double sel_ms = 0;
+    if (!step) {
+        A_(dev_alloc(&dpv, ps->total)); A_(dev_alloc(&dtv, ts->total));
+        UP_(dpl, ps->dig, (size_t) nprob * 4); UP_(dpo, ps->off, (size_t) nprob * 8); UP_(dpv, plimbs, (size_t) ps->total * 8);
+        UP_(dtl, ts->dig, (size_t) nprob * 4); UP_(dto, ts->off, (size_t) nprob * 8); UP_(dtv, tlimbs, (size_t) ts->total * 8);
+        if (place) { A_(dev_alloc(&dplace, nprob)); UP_(dplace, place, (size_t) nprob * 4); }
+        I.p.limbs = dpv; I.t.limbs = dtv;
+    } else {
+        hbest = (int32_t *) malloc((size_t) nprob * 4); hties = (int32_t *) malloc((size_t) nprob * 4); helig = (int32_t *) malloc((size_t) nprob * 4);
+        if (!hbest || !hties || !helig) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
+        /* the selection, as slip_hip_factor_ratio_test makes it: the sign of det decides which sign of anum is eligible */
+        SlipPiv pr; memset(&pr, 0, sizeof pr);
+        DOWN_(&pr, f->P.piv.p_ + (n - 1), sizeof pr);
+        if (!rc && pr.len == 0) rc = SLIP_HIP_DEVICE_ERROR;
+        SlipRatioArgs R; memset(&R, 0, sizeof R);
+        R.n = n; R.nprob = nprob; R.pstride = 2 * (int64_t) n; R.oidx = doidx;
+        R.xlen = o.olen; R.xoff = o.ooff; R.xlimbs = o.olimbs; R.alen = o.olen + n; R.aoff = o.ooff + n; R.alimbs = o.olimbs;
+        R.asense = pr.len < 0 ? -sense : sense; R.xflip = pr.len < 0;
+        f->ratio_ms = 0; memset(f->ratio_paths, 0, sizeof f->ratio_paths);
+        A_(ratio_core(R, key, hbest, hties, helig, NULL, NULL, NULL, stream, &f->ratio_ms, f->ratio_paths));
+        sel_ms = f->ratio_ms;
+        /* the winners' records and places */
+        A_(dev_alloc(&dbest, nprob)); A_(dev_alloc(&dplace, nprob));
+        UP_(dbest, hbest, (size_t) nprob * 4);
+        if (!rc) {
+            SlipPivotArgs W; memset(&W, 0, sizeof W);
+            W.n = n; W.nprob = nprob; W.phase = 4; W.vstride = I.vstride; W.astride = I.astride; W.pos = dpos;
+            W.vlen = I.v.len; W.voff = I.v.off; W.alen = I.a.len; W.aoff = I.a.off;
+            W.best = dbest; W.wplen = dpl; W.wpoff = dpo; W.wtlen = dtl; W.wtoff = dto; W.wplace = dplace;
+            A_(SERVICE_LAUNCH(pivot, service_blocks(nprob), stream, W));
+        }
+        I.p.limbs = o.olimbs; I.t.limbs = o.olimbs;
+    }
+    I.p.len = dpl; I.p.off = dpo; I.t.len = dtl; I.t.off = dto; I.place = dplace;
+    double ms = 0; int64_t paths[8];
+    A_(pivot_core(I, ninexact, &rl, &rv, &rn, stream, &ms, paths));
+    if (step) A_(pack_download(nprob, dpl, dpo, o.olimbs, 0, &nl, &nv, &nn, stream));
+    if (!rc) {
+        f->update_ms[0] = ms; f->update_ms[1] = sel_ms; memcpy(f->update_paths, paths, sizeof paths);
+        *rlen_out = rl; *rlimbs_out = rv; *rnl_out = rn; rl = NULL; rv = NULL;
+        if (step) {
+            memcpy(best, hbest, (size_t) nprob * 4); memcpy(nties, hties, (size_t) nprob * 4); memcpy(neligible, helig, (size_t) nprob * 4);
+            *dlen_out = nl; *dlimbs_out = nv; *dnl_out = nn; nl = NULL; nv = NULL;
+        }
+    }
+    free(hidx); free(hbest); free(hties); free(helig); free(rl); free(rv); free(nl); free(nv);
+    dev_free(ddlen); dev_free(ddoff); dev_free(doidx); dev_free(dpos); dev_free(dpl); dev_free(dpo); dev_free(dtl); dev_free(dto);
+    dev_free(dpv); dev_free(dtv); dev_free(dplace); dev_free(dbest);
+    solve_out_free(&o);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_solve_update(slip_hip_factor *f, int32_t transpose, int32_t nprob,
+                                            const int32_t *blen, const uint64_t *blimbs,
+                                            const int32_t *plen, const uint64_t *plimbs, int64_t p_limbs,
+                                            const int32_t *tlen, const uint64_t *tlimbs, int64_t t_limbs,
+                                            const int32_t *place, int32_t *ninexact,
+                                            int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, void *stream_v)
+{
+    if (!f || nprob < 1 || nprob > (1 << 29) || !blen || !blimbs || !plen || !plimbs || !tlen || !tlimbs || !ninexact ||
+        !rlen_out || !rlimbs_out || !rnl_out || !pivot_place_ok(place, nprob, f->n))
+        return SLIP_HIP_INCORRECT_INPUT;
+    SlipSlab ps, ts; memset(&ps, 0, sizeof ps); memset(&ts, 0, sizeof ts);
+    int rc = slab_prepare(nprob, plen, plimbs, p_limbs, &ps);
+    A_(slab_prepare(nprob, tlen, tlimbs, t_limbs, &ts));
+    A_(update_on_handle(f, 0, transpose, nprob, blen, blimbs, &ps, plimbs, &ts, tlimbs, place, 1, NULL, NULL, NULL, NULL, ninexact,
+                        rlen_out, rlimbs_out, rnl_out, NULL, NULL, NULL, (hipStream_t) stream_v));
+    slab_free(&ps); slab_free(&ts);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_step(slip_hip_factor *f, int32_t transpose, int32_t nprob,
+                                    const int32_t *blen, const uint64_t *blimbs, int32_t sense, const int32_t *key,
+                                    int32_t *best, int32_t *nties, int32_t *neligible, int32_t *ninexact,
+                                    int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                                    int32_t **dlen_out, uint64_t **dlimbs_out, int64_t *dnl_out, void *stream_v)
+{
+    if (!f || nprob < 1 || nprob > (1 << 29) || (sense != 1 && sense != -1) || !blen || !blimbs || !best || !nties || !neligible ||
+        !ninexact || !rlen_out || !rlimbs_out || !rnl_out || !dlen_out || !dlimbs_out || !dnl_out)
+        return SLIP_HIP_INCORRECT_INPUT;
+    return update_on_handle(f, 1, transpose, nprob, blen, blimbs, NULL, NULL, NULL, NULL, NULL, sense, key, best, nties, neligible, ninexact,
+                            rlen_out, rlimbs_out, rnl_out, dlen_out, dlimbs_out, dnl_out, (hipStream_t) stream_v);
+}
+
+extern "C" int slip_hip_factor_update_ms(const slip_hip_factor *f, double out[2])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->update_ms, sizeof f->update_ms);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_update_paths(const slip_hip_factor *f, int64_t out[8])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->update_paths, sizeof f->update_paths);
     return SLIP_HIP_OK;
 }
 
