@@ -777,20 +777,6 @@ template <int D> SLIP_DEV int slip_history_wave_reg(const SlipParams &P, int r, 
     return slip_store_x_reg<D>(P, r, Y, sign, xr.h, xr.tag);
 }
 
-/* compare the magnitudes of two register numbers: -1, 0, +1 (all lanes call) */
-template <int D> SLIP_DEV int wr_cmp(const WR<D> &A, const WR<D> &B)
-{
-#pragma unroll
-    for (int q = D - 1; q >= 0; q--) {
-        const uint64_t df = slip_ballot(A.d[q] != B.d[q]);
-        if (df) {
-            const int t = 63 - slip_clz64(df);
-            return slip_readlane(A.d[q], t) > slip_readlane(B.d[q], t) ? 1 : -1;
-        }
-    }
-    return 0;
-}
-
 /* Is |x[r] * rho[pm] / rho[pd]| (pd >= 0: the row was last updated at column pd) on the far side of |a * rho[pm]|?  Nothing is
  * stored: the row keeps its state.  Used by the pre-pass to rule class-B candidates out BEFORE the column's turn: every
  * candidate's final value is its level-pm value times the same rho[k-1] / rho[pm], so the order at level pm is the final

@@ -1314,15 +1314,7 @@ template <int D> SLIP_DEV int slip_ratio_cmp_reg(const dig_t *x1, int lx1, const
     const WR<D> X1 = wr_load<D>(x1, lx1), A2 = wr_load<D>(a2, la2), X2 = wr_load<D>(x2, lx2), A1 = wr_load<D>(a1, la1);
     const WR<D> P = lx1 <= la2 ? wr_mul<D>(X1, lx1, A2) : wr_mul<D>(A2, la2, X1);
     const WR<D> Q = lx2 <= la1 ? wr_mul<D>(X2, lx2, A1) : wr_mul<D>(A1, la1, X2);
-#pragma unroll
-    for (int q = D - 1; q >= 0; q--) {
-        const uint64_t df = slip_ballot(P.d[q] != Q.d[q]);
-        if (df) {
-            const int t = 63 - slip_clz64(df);
-            return slip_readlane(P.d[q], t) > slip_readlane(Q.d[q], t) ? 1 : -1;
-        }
-    }
-    return 0;
+    return wr_cmp<D>(P, Q);
 }
 
 /* sign(r_i - r_j) for two eligible entries of problem c (all arguments wave-uniform); cnt[0], cnt[1]: paths 2 and 3 */
@@ -1628,20 +1620,6 @@ SLIP_DEV void slip_bound_eval_lane(const SlipBoundEnt &E, int q, int *sg, slip_u
     else { *mag = Q - P; *sg = s2; }
 }
 
-/* sign(P - Q) of two register numbers' magnitudes */
-template <int D> SLIP_DEV int slip_bound_cmp_reg(const WR<D> &P, const WR<D> &Q)
-{
-#pragma unroll
-    for (int q = D - 1; q >= 0; q--) {
-        const uint64_t df = slip_ballot(P.d[q] != Q.d[q]);
-        if (df) {
-            const int t = 63 - slip_clz64(df);
-            return slip_readlane(P.d[q], t) > slip_readlane(Q.d[q], t) ? 1 : -1;
-        }
-    }
-    return 0;
-}
-
 /* the product of two operands that fits 64*D digits, the shorter one walked */
 template <int D> SLIP_DEV WR<D> slip_bound_mul_reg(const SlipBoundOp &a, const SlipBoundOp &b)
 {
@@ -1658,11 +1636,11 @@ template <int D> SLIP_DEV WR<D> slip_bound_eval_reg(const SlipBoundEnt &E, int q
     *top = 0;
     if (!s1 || !s2 || s1 == s2) {
         const WR<D> R = wr_addsub<D>(P, Q, 0);
-        *top = slip_bound_cmp_reg<D>(R, P) < 0 ? 1u : 0u;          /* the sum wrapped */
+        *top = wr_cmp<D>(R, P) < 0 ? 1u : 0u;                      /* the sum wrapped */
         *sg = s1 ? s1 : s2;
         return R;
     }
-    const int cm = slip_bound_cmp_reg<D>(P, Q);
+    const int cm = wr_cmp<D>(P, Q);
     *sg = cm > 0 ? s1 : cm < 0 ? s2 : 0;
     return cm >= 0 ? wr_addsub<D>(P, Q, 1) : wr_addsub<D>(Q, P, 1);
 }
@@ -1676,7 +1654,7 @@ template <int D> SLIP_DEV int slip_bound_entry_reg(const SlipBoundEnt &E, dig_t 
     if (E.sides == 3) {
         int sg2; uint32_t top2;
         const WR<D> V2 = slip_bound_eval_reg<D>(E, 2, &sg2, &top2);
-        const int cm = top2 != top ? (top2 > top ? 1 : -1) : slip_bound_cmp_reg<D>(V2, V);
+        const int cm = top2 != top ? (top2 > top ? 1 : -1) : wr_cmp<D>(V2, V);
         if (slip_bound_greater(sg2, sg, cm)) { V = V2; sg = sg2; top = top2; q = 2; }
     }
     /* (a carry means a product of 64*D digits: the entry owns at least 64*D + 2 digits of the staging slab) */
@@ -1980,7 +1958,7 @@ template <int D> SLIP_DEV int slip_pivot_entry_reg(const SlipPivotEnt &E, dig_t 
     WR<D> N; int sg;
     if (!E.s1 || !E.s2 || E.s1 == E.s2) { N = wr_addsub<D>(X, Y, 0); sg = E.s1 ? E.s1 : E.s2; }
     else {
-        const int cm = slip_bound_cmp_reg<D>(X, Y);
+        const int cm = wr_cmp<D>(X, Y);
         sg = cm > 0 ? E.s1 : cm < 0 ? E.s2 : 0;
         N = cm >= 0 ? wr_addsub<D>(X, Y, 1) : wr_addsub<D>(Y, X, 1);
     }
@@ -2863,6 +2841,29 @@ static int slab_prepare(int64_t count, const int32_t *len, const uint64_t *limbs
     }
     s->total = total;
     return SLIP_HIP_OK;
+}
+
+/* operand records on the device: signed digit counts, limb offsets, the limbs */
+struct SlipDevRecs { const int32_t *len; const int64_t *off; const uint64_t *limbs; };
+
+/* a slab on the device: its three arrays and, where dev_slab_upload laid it out, the host's layout (s) */
+struct SlipDevSlab { SlipSlab s; int32_t *len; int64_t *off; uint64_t *limbs; };
+static void dev_slab_free(SlipDevSlab *d) { dev_free(d->len); dev_free(d->off); dev_free(d->limbs); slab_free(&d->s); memset(d, 0, sizeof *d); }
+static SlipDevRecs dev_slab_recs(const SlipDevSlab &d) { const SlipDevRecs r = {d.len, d.off, d.limbs}; return r; }
+/* a slab of `count` entries the host has laid out (s) into the three arrays of d (zeroed; s stays the caller's) */
+static int dev_slab_put(int64_t count, const SlipSlab &s, const uint64_t *limbs, SlipDevSlab *d)
+{
+    int rc = 0;
+    A_(dev_alloc(&d->len, count)); A_(dev_alloc(&d->off, count)); A_(dev_alloc(&d->limbs, s.total));
+    UP_(d->len, s.dig, (size_t) count * 4); UP_(d->off, s.off, (size_t) count * 8); UP_(d->limbs, limbs, (size_t) s.total * 8);
+    return rc;
+}
+/* a caller's slab of `count` entries checked, laid out (d->s) and brought to the device; d: zeroed */
+static int dev_slab_upload(int64_t count, const int32_t *len, const uint64_t *limbs, int64_t cap, SlipDevSlab *d)
+{
+    int rc = slab_prepare(count, len, limbs, cap, &d->s);
+    A_(dev_slab_put(count, d->s, limbs, d));
+    return rc;
 }
 
 extern "C" void slip_hip_free(void *p) { free(p); }
@@ -5073,8 +5074,141 @@ static int64_t product_stage_limbs(void)
     return kb > 0 ? (int64_t) kb * 128 : ((int64_t) 256 << 20) / 8;
 }
 
-/* operand records on the device: signed digit counts, limb offsets, the limbs */
-struct SlipDevRecs { const int32_t *len; const int64_t *off; const uint64_t *limbs; };
+/* The staged form of a service: nprob problems of n items each, whose widths dw (device; digits, none above the even wcap >= 2)
+ * a first pass has written, formed group by group into a staging slab no larger than product_stage_limbs() -- whole multiples
+ * of `gran` problems, at least gran (the bound groups, it never refuses).  Per group of the problems c0 .. c0 + nv: the items'
+ * staging offsets into dso (an offset scan), the slab, form(c0, nv, cnt, dstage) launching the passes that fill it (cnt = n * nv
+ * items), sink(c0, nv, dstage) for what becomes of it; both return a status.  The device ms of the scans and of the forms are
+ * added to *scan_ms and *form_ms (which may be one figure). */
+template <class Form, class Sink>
+static int staged_run(int64_t n, int64_t nprob, int64_t gran, int64_t wcap, const int32_t *dw, int64_t *dso, Form form, Sink sink,
+                      hipStream_t stream, double *scan_ms, double *form_ms)
+{
+    int64_t group = product_stage_limbs() / (n * (wcap / 2)) / gran * gran;
+    if (group < gran) group = gran;
+    if (group > nprob) group = nprob;
+    const int64_t sblocks = offscan_blocks(n * group);
+    unsigned long long *bsum = NULL;
+    int rc = dev_alloc(&bsum, sblocks);
+    for (int64_t c0 = 0; c0 < nprob && !rc; c0 += group) {
+        const int64_t nv = c0 + group <= nprob ? group : nprob - c0, cnt = n * nv;
+        uint64_t *dstage = NULL; int64_t total = 0;
+        double t = 0;
+        {                                                  /* the staging offsets from the widths */
+            SlipTimed timed;
+            A_(timed.begin(stream));
+            A_(offscan_run(cnt, dw + c0 * n, dso + c0 * n, bsum, sblocks, stream));
+            A_(timed.end(stream, &t));
+            *scan_ms += t;
+        }
+        A_(offscan_total(bsum, sblocks, &total, stream));
+        if (!rc && total > cnt * (wcap / 2)) rc = SLIP_HIP_DEVICE_ERROR;           /* (the widths' bound: the host's own figure) */
+        A_(dev_alloc(&dstage, total));
+        if (!rc) {                                         /* the passes into the staging slab */
+            SlipTimed timed;
+            A_(timed.begin(stream));
+            A_(form(c0, nv, cnt, dstage));
+            A_(timed.end(stream, &t));
+            *form_ms += t;
+        }
+        A_(sink(c0, nv, (const uint64_t *) dstage));
+        dev_free(dstage);
+    }
+    dev_free(bsum);
+    return rc;
+}
+
+/* the cnt staged records of a group packed and downloaded (pack_download) and appended to a result: their signed limb counts
+ * to ol, their limbs behind the *on that *out holds (a first group's block is taken over as it stands) */
+static int pack_append(int64_t cnt, const int32_t *drl, const int64_t *dso, const uint64_t *dstage, int32_t *ol, uint64_t **out, int64_t *on,
+                       hipStream_t stream, double *pack_ms = NULL)
+{
+    int32_t *gl = NULL; uint64_t *gv = NULL; int64_t gn = 0;
+    int rc = pack_download(cnt, drl, dso, dstage, 0, &gl, &gv, &gn, stream, pack_ms);
+    if (!rc && !*out) { *out = gv; *on = gn; gv = NULL; }
+    else if (!rc) {
+        uint64_t *grown = (uint64_t *) realloc(*out, (size_t)(*on + gn > 0 ? *on + gn : 1) * 8);
+        if (!grown) rc = SLIP_HIP_OUT_OF_MEMORY;
+        else { *out = grown; memcpy(grown + *on, gv, (size_t) gn * 8); *on += gn; }
+    }
+    if (!rc) memcpy(ol, gl, (size_t) cnt * 4);
+    free(gl); free(gv);
+    return rc;
+}
+
+/* the winners' records of a group of nv problems appended to wl / wv (signed limb counts, limbs): record c of the first stream
+ * (device: dl1, do1 into lim1), then, with lim2, record c of the second, problem by problem */
+static int winners_collect(int64_t nv, const int32_t *dl1, const int64_t *do1, const uint64_t *lim1,
+                           const int32_t *dl2, const int64_t *do2, const uint64_t *lim2,
+                           std::vector<int32_t> *wl, std::vector<uint64_t> *wv, hipStream_t stream)
+{
+    int32_t *l1 = NULL, *l2 = NULL; uint64_t *v1 = NULL, *v2 = NULL; int64_t n1 = 0, n2 = 0;
+    int rc = pack_download(nv, dl1, do1, lim1, 0, &l1, &v1, &n1, stream);
+    if (lim2) A_(pack_download(nv, dl2, do2, lim2, 0, &l2, &v2, &n2, stream));
+    if (!rc) {
+        int64_t o1 = 0, o2 = 0;
+        for (int64_t c = 0; c < nv; c++) {
+            const int64_t a1 = l1[c] < 0 ? -l1[c] : l1[c];
+            wl->push_back(l1[c]); wv->insert(wv->end(), v1 + o1, v1 + o1 + a1); o1 += a1;
+            if (lim2) {
+                const int64_t a2 = l2[c] < 0 ? -l2[c] : l2[c];
+                wl->push_back(l2[c]); wv->insert(wv->end(), v2 + o2, v2 + o2 + a2); o2 += a2;
+            }
+        }
+    }
+    free(l1); free(l2); free(v1); free(v2);
+    return rc;
+}
+
+/* the winners' records collected by winners_collect as the caller's malloc'ed slab */
+static int winners_out(const std::vector<int32_t> &wl, const std::vector<uint64_t> &wv, int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out)
+{
+    int32_t *ol = (int32_t *) malloc((wl.size() > 0 ? wl.size() : 1) * 4); uint64_t *ov = (uint64_t *) malloc((wv.size() > 0 ? wv.size() : 1) * 8);
+    if (!ol || !ov) { free(ol); free(ov); return SLIP_HIP_OUT_OF_MEMORY; }
+    if (!wl.empty()) memcpy(ol, wl.data(), wl.size() * 4);
+    if (!wv.empty()) memcpy(ov, wv.data(), wv.size() * 8);
+    *wlen_out = ol; *wlimbs_out = ov; *wnl_out = (int64_t) wv.size();
+    return SLIP_HIP_OK;
+}
+
+/* the four results of a selection, nprob each and one after the other in res, into the caller's four arrays */
+static void results_out(const int32_t *res, int32_t nprob, int32_t *r0, int32_t *r1, int32_t *r2, int32_t *r3)
+{
+    memcpy(r0, res, (size_t) nprob * 4); memcpy(r1, res + nprob, (size_t) nprob * 4);
+    memcpy(r2, res + 2 * (size_t) nprob, (size_t) nprob * 4); memcpy(r3, res + 3 * (size_t) nprob, (size_t) nprob * 4);
+}
+
+/* the winners' three outputs come all or none */
+static int winners_args_bad(int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out)
+{
+    return (wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out);
+}
+
+/* position p of a transposed solve is row i, pinv[i] = p: the map from a position to the index reported (*doidx) and, with
+ * dpos, its inverse, on the device; both stay NULL for a plain solve */
+static int transposed_maps(const slip_hip_factor *f, int transpose, int32_t **doidx, int32_t **dpos)
+{
+    const int32_t n = f->n;
+    if (!transpose) return SLIP_HIP_OK;
+    int32_t *hidx = (int32_t *) malloc((size_t) n * 4);
+    int rc = !hidx ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    if (!rc) for (int32_t i = 0; i < n; i++) hidx[f->tpinv[i]] = i;
+    A_(dev_alloc(doidx, n)); UP_(*doidx, hidx, (size_t) n * 4);
+    if (dpos) { A_(dev_alloc(dpos, n)); UP_(*dpos, f->tpinv, (size_t) n * 4); }
+    free(hidx);
+    return rc;
+}
+
+/* the sign of det = rho[n-1] of a complete handle from its pivot record: *dneg */
+static int det_negative(const slip_hip_factor *f, int *dneg)
+{
+    int rc = 0;
+    SlipPiv pr; memset(&pr, 0, sizeof pr);
+    DOWN_(&pr, f->P.piv.p_ + (f->n - 1), sizeof pr);
+    if (!rc && pr.len == 0) rc = SLIP_HIP_DEVICE_ERROR;
+    *dneg = pr.len < 0;
+    return rc;
+}
 
 /* one product on operands that are on the device already; d_c as device records (with b).  xmaxdig: the digits of the widest
  * entry of x, or negative when only the device knows the lengths (a substitution's output): the widest item is then reduced
@@ -5094,7 +5228,7 @@ static int product_device(const SlipProductView &V, int32_t nvec, const SlipDevR
     int64_t wtop = (b && dmaxdig + bmaxdig > V.amaxdig + xmaxdig ? dmaxdig + bmaxdig : V.amaxdig + xmaxdig) + 1;
     if (xmaxdig >= 0 && ((wtop + 1) & ~(int64_t) 1) > (1 << 28)) return SLIP_HIP_OUT_OF_MEMORY;
     int32_t *dw = NULL, *drl = NULL, *dwmax = NULL; int64_t *dso = NULL;
-    dig_t *dscr = NULL; unsigned long long *bsum = NULL;
+    dig_t *dscr = NULL;
     int rc = 0;
     A_(dev_alloc(&dw, ne)); A_(dev_alloc(&dso, ne)); A_(dev_alloc(&drl, ne));
     if (xmaxdig < 0) A_(dev_alloc(&dwmax, 1));
@@ -5129,42 +5263,23 @@ static int product_device(const SlipProductView &V, int32_t nvec, const SlipDevR
     }
     const int64_t wcap = (wtop + 1) & ~(int64_t) 1;
     if (!rc && (wcap > (1 << 28) || wcap < 2)) rc = wcap < 2 ? SLIP_HIP_DEVICE_ERROR : SLIP_HIP_OUT_OF_MEMORY;
-    int64_t group = rc ? gran : product_stage_limbs() / (nout * (wcap / 2)) / gran * gran;      /* vectors staged together */
-    if (group < gran) group = gran;
-    if (group > nvec) group = nvec;
-    const int64_t blocks = wtop > 256 ? fit_scratch(wave_blocks(ne), wcap) : wave_blocks(ne), sblocks = offscan_blocks(nout * group);
-    A_(dev_alloc(&bsum, sblocks));
+    const int64_t blocks = wtop > 256 ? fit_scratch(wave_blocks(ne), wcap) : wave_blocks(ne);
     if (wtop > 256) A_(dev_alloc(&dscr, blocks * SERVICE_WAVES * wcap));
     A.scratch = dscr; A.wcap = (int32_t) wcap;
-    for (int64_t c0 = 0; c0 < nvec && !rc; c0 += group) {
-        const int64_t nv = c0 + group <= nvec ? group : nvec - c0, cnt = nout * nv;
-        uint64_t *dstage = NULL; int64_t total = 0;
-        double t = 0;
+    /* pass 2, the staging offsets, is staged_run's; pass 3: the products of a group into the staging slab */
+    auto form = [&](int64_t c0, int64_t nv, int64_t, uint64_t *dstage) {
         slice(c0, nv, 1);
-        {                                                  /* pass 2: the staging offsets from the widths */
-            SlipTimed timed;
-            A_(timed.begin(stream));
-            A_(offscan_run(cnt, A.wlen, dso + c0 * nout, bsum, sblocks, stream));
-            A_(timed.end(stream, &t));
-            ms[1] += t;
-        }
-        A_(offscan_total(bsum, sblocks, &total, stream));
-        if (!rc && total > nout * nv * (wcap / 2)) rc = SLIP_HIP_DEVICE_ERROR;     /* (the widths' bound: the host's own figure) */
-        A_(dev_alloc(&dstage, total));
-        if (!rc) {                                         /* pass 3: the products into the staging slab */
-            SlipTimed timed;
-            A.stage = dstage;
-            A_(timed.begin(stream));
-            A_(SERVICE_LAUNCH(product, blocks, stream, A));
-            A_(timed.end(stream, &t));
-            ms[2] += t;
-        }
-        t = 0;
-        A_(sink(c0, nv, (const int32_t *) A.rlen, A.soff, (const uint64_t *) dstage, &t));
+        A.stage = dstage;
+        return SERVICE_LAUNCH(product, blocks, stream, A);
+    };
+    auto staged = [&](int64_t c0, int64_t nv, const uint64_t *dstage) {
+        double t = 0;
+        const int rc = sink(c0, nv, (const int32_t *) drl + c0 * nout, (const int64_t *) dso + c0 * nout, dstage, &t);
         if (!rc) ms[3] += t;
-        dev_free(dstage);
-    }
-    dev_free(dw); dev_free(dso); dev_free(drl); dev_free(dwmax); dev_free(bsum); dev_free(dscr);
+        return rc;
+    };
+    A_(staged_run(nout, nvec, gran, wcap, dw, dso, form, staged, stream, &ms[1], &ms[2]));
+    dev_free(dw); dev_free(dso); dev_free(drl); dev_free(dwmax); dev_free(dscr);
     return rc;
 }
 
@@ -5176,34 +5291,19 @@ static int product_core(const SlipProductView &V, int32_t nvec, const SlipSlab &
                         int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out, hipStream_t stream, double *ms_out)
 {
     const int64_t nout = V.nout, ne = nout * nvec, nxe = (int64_t) V.nx * nvec;
-    int32_t *dxl = NULL, *dbl = NULL; int64_t *dxo = NULL, *dbo = NULL; uint64_t *dxv = NULL, *dbv = NULL;
+    SlipDevSlab dx, db; memset(&dx, 0, sizeof dx); memset(&db, 0, sizeof db);
     int32_t *rl = (int32_t *) malloc((size_t) ne * 4); uint64_t *rv = NULL; int64_t rn = 0;
     double ms[4] = {0, 0, 0, 0};
     int rc = !rl ? SLIP_HIP_OUT_OF_MEMORY : 0;
-    A_(dev_alloc(&dxl, nxe)); A_(dev_alloc(&dxo, nxe)); A_(dev_alloc(&dxv, xs.total));
-    if (bs) { A_(dev_alloc(&dbl, ne)); A_(dev_alloc(&dbo, ne)); A_(dev_alloc(&dbv, bs->total)); }
-    UP_(dxl, xs.dig, (size_t) nxe * 4); UP_(dxo, xs.off, (size_t) nxe * 8); UP_(dxv, xlimbs, (size_t) xs.total * 8);
-    if (bs) { UP_(dbl, bs->dig, (size_t) ne * 4); UP_(dbo, bs->off, (size_t) ne * 8); UP_(dbv, blimbs, (size_t) bs->total * 8); }
-    const SlipDevRecs x = {dxl, dxo, dxv}, b = {dbl, dbo, dbv};
-    /* a group packed and downloaded (pack_download), appended to the result */
+    A_(dev_slab_put(nxe, xs, xlimbs, &dx));
+    if (bs) A_(dev_slab_put(ne, *bs, blimbs, &db));
+    const SlipDevRecs x = dev_slab_recs(dx), b = dev_slab_recs(db);
+    /* a group packed, downloaded and appended to the result */
     auto sink = [&](int64_t c0, int64_t nv, const int32_t *drl, const int64_t *dso, const uint64_t *dstage, double *t) {
-        int32_t *gl = NULL; uint64_t *gv = NULL; int64_t gn = 0;
-        int rc = pack_download(nout * nv, drl, dso, dstage, 0, &gl, &gv, &gn, stream, t);
-        if (!rc) {
-            uint64_t *grown = (uint64_t *) realloc(rv, (size_t)(rn + gn > 0 ? rn + gn : 1) * 8);
-            if (!grown) rc = SLIP_HIP_OUT_OF_MEMORY;
-            else {
-                rv = grown;
-                memcpy(rl + c0 * nout, gl, (size_t)(nout * nv) * 4);
-                if (gn > 0) memcpy(rv + rn, gv, (size_t) gn * 8);
-                rn += gn;
-            }
-        }
-        free(gl); free(gv);
-        return rc;
+        return pack_append(nout * nv, drl, dso, dstage, rl + c0 * nout, &rv, &rn, stream, t);
     };
     A_(product_device(V, nvec, x, xs.maxdig, bs ? &b : NULL, bs ? bs->maxdig : 0, ddlen, ddoff, ddlimbs, dmaxdig, 1, sink, stream, ms));
-    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dbl); dev_free(dbo); dev_free(dbv);
+    dev_slab_free(&dx); dev_slab_free(&db);
     if (rc) { free(rl); free(rv); return rc; }
     memcpy(slip_product_passes_last, ms, sizeof ms);
     if (ms_out) *ms_out = ms[0] + ms[1] + ms[2] + ms[3];
@@ -5225,18 +5325,18 @@ static int product_entry(const SlipProductView &V, slip_hip_factor *f, int32_t n
     if (!rc && blen) rc = slab_prepare((int64_t) V.nout * nvec, blen, blimbs, b_limbs, &bs);
     if (!rc && dlen) rc = slab_prepare(nvec, dlen, dlimbs, d_limbs, &ds);
     for (int32_t c = 0; c < nvec && !rc && dlen; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
-    int32_t *ddlen = NULL; int64_t *ddoff = NULL; uint64_t *ddl = NULL; const uint64_t *ddlimbs = NULL; int32_t dmaxdig = 0;
+    SlipDevSlab dd; memset(&dd, 0, sizeof dd);            /* (from det: records alone, into the L slab) */
+    const uint64_t *ddlimbs = NULL; int32_t dmaxdig = 0;
     if (blen && dlen) {
-        A_(dev_alloc(&ddlen, nvec)); A_(dev_alloc(&ddoff, nvec)); A_(dev_alloc(&ddl, ds.total));
-        UP_(ddlen, ds.dig, (size_t) nvec * 4); UP_(ddoff, ds.off, (size_t) nvec * 8); UP_(ddl, dlimbs, (size_t) ds.total * 8);
-        ddlimbs = ddl; dmaxdig = ds.maxdig;
+        A_(dev_slab_put(nvec, ds, dlimbs, &dd));
+        ddlimbs = dd.limbs; dmaxdig = ds.maxdig;
     } else if (blen) {
-        A_(det_records(f, nvec, &ddlen, &ddoff, &dmaxdig));
+        A_(det_records(f, nvec, &dd.len, &dd.off, &dmaxdig));
         ddlimbs = f->P.Llimbs;
     }
-    A_(product_core(V, nvec, xs, xlimbs, blen ? &bs : NULL, blimbs, ddlen, ddoff, ddlimbs, dmaxdig,
+    A_(product_core(V, nvec, xs, xlimbs, blen ? &bs : NULL, blimbs, dd.len, dd.off, ddlimbs, dmaxdig,
                     rlen_out, rlimbs_out, rnl_out, stream, ms_out));
-    dev_free(ddlen); dev_free(ddoff); dev_free(ddl);
+    dev_slab_free(&dd);
     slab_free(&xs); slab_free(&bs); slab_free(&ds);
     return rc;
 }
@@ -5419,16 +5519,6 @@ static int ratio_core(SlipRatioArgs A, const int32_t *key, int32_t *best, int32_
     return rc;
 }
 
-/* a caller's slab of `count` entries on the device: the host's digit counts and offsets (s), the three device arrays */
-static int ratio_upload(int64_t count, const int32_t *len, const uint64_t *limbs, int64_t cap, SlipSlab *s,
-                        int32_t **dlen, int64_t **doff, uint64_t **dlimbs)
-{
-    int rc = slab_prepare(count, len, limbs, cap, s);
-    A_(dev_alloc(dlen, count)); A_(dev_alloc(doff, count)); A_(dev_alloc(dlimbs, s->total));
-    UP_(*dlen, s->dig, (size_t) count * 4); UP_(*doff, s->off, (size_t) count * 8); UP_(*dlimbs, limbs, (size_t) s->total * 8);
-    return rc;
-}
-
 extern "C" int slip_hip_ratio_test(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
                                    const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs, int32_t sense, const int32_t *key,
                                    int32_t *best, int32_t *nties, int32_t *neligible, void *stream_v)
@@ -5437,17 +5527,15 @@ extern "C" int slip_hip_ratio_test(int32_t n, int32_t nprob, const int32_t *xlen
         return SLIP_HIP_INCORRECT_INPUT;
     TRY_(need_device());
     const int64_t ne = (int64_t) n * nprob;
-    SlipSlab xs, as; memset(&xs, 0, sizeof xs); memset(&as, 0, sizeof as);
-    int32_t *dxl = NULL, *dal = NULL; int64_t *dxo = NULL, *dao = NULL; uint64_t *dxv = NULL, *dav = NULL;
-    int rc = ratio_upload(ne, xlen, xlimbs, x_limbs, &xs, &dxl, &dxo, &dxv);
-    if (alen) A_(ratio_upload(ne, alen, alimbs, a_limbs, &as, &dal, &dao, &dav));
+    SlipDevSlab x, a; memset(&x, 0, sizeof x); memset(&a, 0, sizeof a);
+    int rc = dev_slab_upload(ne, xlen, xlimbs, x_limbs, &x);
+    if (alen) A_(dev_slab_upload(ne, alen, alimbs, a_limbs, &a));
     SlipRatioArgs A; memset(&A, 0, sizeof A);
-    A.n = n; A.nprob = nprob; A.pstride = n; A.xlen = dxl; A.xoff = dxo; A.xlimbs = dxv; A.alen = dal; A.aoff = dao; A.alimbs = dav;
+    A.n = n; A.nprob = nprob; A.pstride = n; A.xlen = x.len; A.xoff = x.off; A.xlimbs = x.limbs; A.alen = a.len; A.aoff = a.off; A.alimbs = a.limbs;
     A.asense = alen ? sense : 0; A.xflip = !alen && sense < 0;
     memset(slip_ratio_paths_last, 0, sizeof slip_ratio_paths_last);
     A_(ratio_core(A, key, best, nties, neligible, NULL, NULL, NULL, (hipStream_t) stream_v, NULL, slip_ratio_paths_last));
-    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dal); dev_free(dao); dev_free(dav);
-    slab_free(&xs); slab_free(&as);
+    dev_slab_free(&x); dev_slab_free(&a);
     return rc;
 }
 
@@ -5471,25 +5559,17 @@ extern "C" int slip_hip_factor_ratio_test(slip_hip_factor *f, int32_t transpose,
     SlipSolveOut o;
     TRY_(solve_device(f, transpose, 2 * nprob, blen, blimbs, stream, &o));
     const int32_t n = f->n;
-    int32_t *doidx = NULL, *hidx = NULL;
-    int rc = 0;
-    /* the sign of det = rho[n-1] from its pivot record: it decides which sign of anum is eligible */
-    SlipPiv pr; memset(&pr, 0, sizeof pr);
-    DOWN_(&pr, f->P.piv.p_ + (n - 1), sizeof pr);
-    if (!rc && pr.len == 0) rc = SLIP_HIP_DEVICE_ERROR;
-    if (!rc && transpose) {                                /* position p of the transposed solve is row i, pinv[i] = p */
-        hidx = (int32_t *) malloc((size_t) n * 4);
-        if (!hidx) rc = SLIP_HIP_OUT_OF_MEMORY;
-        else for (int32_t i = 0; i < n; i++) hidx[f->tpinv[i]] = i;
-        A_(dev_alloc(&doidx, n)); UP_(doidx, hidx, (size_t) n * 4);
-    }
+    int32_t *doidx = NULL;
+    int dneg = 0;
+    int rc = det_negative(f, &dneg);                       /* the sign of det decides which sign of anum is eligible */
+    A_(transposed_maps(f, transpose, &doidx, NULL));
     SlipRatioArgs A; memset(&A, 0, sizeof A);
     A.n = n; A.nprob = nprob; A.pstride = 2 * (int64_t) n; A.oidx = doidx;
     A.xlen = o.olen; A.xoff = o.ooff; A.xlimbs = o.olimbs; A.alen = o.olen + n; A.aoff = o.ooff + n; A.alimbs = o.olimbs;
-    A.asense = pr.len < 0 ? -sense : sense; A.xflip = pr.len < 0;
+    A.asense = dneg ? -sense : sense; A.xflip = dneg;
     f->ratio_ms = 0; memset(f->ratio_paths, 0, sizeof f->ratio_paths);
     A_(ratio_core(A, key, best, nties, neligible, wlen_out, wlimbs_out, wnl_out, stream, &f->ratio_ms, f->ratio_paths));
-    free(hidx); dev_free(doidx);
+    dev_free(doidx);
     solve_out_free(&o);
     return rc;
 }
@@ -5548,11 +5628,12 @@ static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const Slip
                       int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, hipStream_t stream, double ms[2], int64_t paths[8])
 {
     const int32_t n = I.n, nprob = I.nprob;
-    const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE, per = I.mode ? 1 : 2;
-    int32_t *dkind = NULL, *dlol = NULL, *dhil = NULL, *dcls = NULL, *dw = NULL, *drl = NULL, *dal2 = NULL, *dwmax = NULL, *dsel = NULL, *dwn = NULL;
-    int64_t *dloo = NULL, *dhio = NULL, *dso = NULL, *dao2 = NULL, *dwo = NULL;
-    uint64_t *dlov = NULL, *dhiv = NULL, *dbd = NULL;
-    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, *bsum = NULL, hpaths[4] = {0, 0, 0, 0};
+    const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE;
+    int32_t *dkind = NULL, *dcls = NULL, *dw = NULL, *drl = NULL, *dal2 = NULL, *dwmax = NULL, *dsel = NULL, *dwn = NULL;
+    int64_t *dso = NULL, *dao2 = NULL, *dwo = NULL;
+    uint64_t *dbd = NULL;
+    SlipDevSlab lo, hi; memset(&lo, 0, sizeof lo); memset(&hi, 0, sizeof hi);
+    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
     int32_t *hres = (int32_t *) malloc((size_t) nprob * 16), hwmax[2] = {0, 0};
     std::vector<int32_t> wl; std::vector<uint64_t> wv;
     int rc = !hres ? SLIP_HIP_OUT_OF_MEMORY : 0;
@@ -5561,14 +5642,8 @@ static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const Slip
     const int64_t bdn = ((int64_t) hb.bddig + 1) >> 1;
     A_(dev_alloc(&dkind, n)); UP_(dkind, B->kind, (size_t) n * 4);
     A_(dev_alloc(&dbd, bdn + 1)); UP_(dbd, B->bdlimbs ? B->bdlimbs : &hb.one, (size_t) bdn * 8); UP_(dbd + bdn, &hb.one, 8);
-    if (hb.has_lo) {
-        A_(dev_alloc(&dlol, n)); A_(dev_alloc(&dloo, n)); A_(dev_alloc(&dlov, hb.lo.total));
-        UP_(dlol, hb.lo.dig, (size_t) n * 4); UP_(dloo, hb.lo.off, (size_t) n * 8); UP_(dlov, B->lolimbs, (size_t) hb.lo.total * 8);
-    }
-    if (hb.has_hi) {
-        A_(dev_alloc(&dhil, n)); A_(dev_alloc(&dhio, n)); A_(dev_alloc(&dhiv, hb.hi.total));
-        UP_(dhil, hb.hi.dig, (size_t) n * 4); UP_(dhio, hb.hi.off, (size_t) n * 8); UP_(dhiv, B->hilimbs, (size_t) hb.hi.total * 8);
-    }
+    if (hb.has_lo) A_(dev_slab_put(n, hb.lo, B->lolimbs, &lo));
+    if (hb.has_hi) A_(dev_slab_put(n, hb.hi, B->hilimbs, &hi));
     A_(dev_alloc(&dcls, ne)); A_(dev_alloc(&dw, ne)); A_(dev_alloc(&drl, ne)); A_(dev_alloc(&dso, ne));
     A_(dev_alloc(&dal2, ne)); A_(dev_alloc(&dao2, ne)); A_(dev_alloc(&dwmax, 2)); A_(dev_alloc(&dpaths, 4));
     A_(dev_alloc(&dsel, 2 * (int64_t) nprob));
@@ -5577,7 +5652,7 @@ static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const Slip
     SlipBoundArgs A; memset(&A, 0, sizeof A);
     A.n = n; A.mode = I.mode; A.sense = I.sense; A.xstride = I.xstride; A.astride = I.astride;
     A.xlimbs = I.x.limbs; A.alimbs = I.a.limbs; A.dlimbs = I.d.limbs; A.oidx = I.oidx; A.pos = I.pos;
-    A.kind = dkind; A.lolen = dlol; A.looff = dloo; A.lolimbs = dlov; A.hilen = dhil; A.hioff = dhio; A.hilimbs = dhiv;
+    A.kind = dkind; A.lolen = lo.len; A.looff = lo.off; A.lolimbs = lo.limbs; A.hilen = hi.len; A.hioff = hi.off; A.hilimbs = hi.limbs;
     A.bddig = hb.bddig; A.bdlimbs = dbd; A.bdunit = hb.bddig == 1 && (B->bdlimbs ? B->bdlimbs[0] : 1) == 1;
     A.wmax = dwmax; A.paths = dpaths;
     /* the problems c0 .. c0 + nv of every per-problem and per-entry array */
@@ -5599,44 +5674,26 @@ static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const Slip
     DOWN_(hwmax, dwmax, 8);
     const int64_t wcap = hwmax[0] > 1 ? ((int64_t) hwmax[0] + 1) & ~(int64_t) 1 : 2, scap = ((int64_t) hwmax[1] + 1) & ~(int64_t) 1;
     if (!rc && wcap > (1 << 28)) rc = SLIP_HIP_OUT_OF_MEMORY;
-    int64_t group = rc ? 1 : product_stage_limbs() / ((int64_t) n * (wcap / 2));       /* problems staged together */
-    if (group < 1) group = 1;
-    if (group > nprob) group = nprob;
-    const int64_t wblocks = hwmax[1] > 256 ? fit_scratch(wave_blocks(ne), 2 * scap) : wave_blocks(ne), sblocks = offscan_blocks((int64_t) n * group);
-    A_(dev_alloc(&bsum, sblocks));
+    const int64_t wblocks = hwmax[1] > 256 ? fit_scratch(wave_blocks(ne), 2 * scap) : wave_blocks(ne);
     if (hwmax[1] > 256) { A_(dev_alloc(&dscr, wblocks * SERVICE_WAVES * 2 * scap)); A.scratch = dscr; A.wcap = (int32_t) scap; }
-    for (int64_t c0 = 0; c0 < nprob && !rc; c0 += group) {
-        const int64_t nv = c0 + group <= nprob ? group : nprob - c0, cnt = (int64_t) n * nv;
-        uint64_t *dstage = NULL; int64_t total = 0;
-        double t = 0;
-        {                                                  /* the staging offsets from the widths */
-            SlipTimed timed;
-            A_(timed.begin(stream));
-            A_(offscan_run(cnt, dw + c0 * n, dso + c0 * n, bsum, sblocks, stream));
-            A_(timed.end(stream, &t));
-            ms[0] += t;
-        }
-        A_(offscan_total(bsum, sblocks, &total, stream));
-        if (!rc && total > cnt * (wcap / 2)) rc = SLIP_HIP_DEVICE_ERROR;           /* (the widths' bound: the host's own figure) */
-        A_(dev_alloc(&dstage, total));
-        if (!rc) {                                         /* the numerators into the staging slab: the lane pass, the wave pass */
-            SlipTimed timed;
-            A.stage = dstage;
-            A_(timed.begin(stream));
-            slice(c0, nv, 1); A_(SERVICE_LAUNCH(bound, wave_blocks(rpp * nv), stream, A));
-            slice(c0, nv, 2); A_(SERVICE_LAUNCH(bound, wave_blocks(cnt) < wblocks ? wave_blocks(cnt) : wblocks, stream, A));
-            A_(timed.end(stream, &t));
-            ms[0] += t;
-        }
+    /* the numerators of a group of whole problems into the staging slab: the lane pass, the wave pass */
+    auto form = [&](int64_t c0, int64_t nv, int64_t cnt, uint64_t *dstage) {
+        int rc = 0;
+        A.stage = dstage;
+        slice(c0, nv, 1); A_(SERVICE_LAUNCH(bound, wave_blocks(rpp * nv), stream, A));
+        slice(c0, nv, 2); A_(SERVICE_LAUNCH(bound, wave_blocks(cnt) < wblocks ? wave_blocks(cnt) : wblocks, stream, A));
+        return rc;
+    };
+    auto select = [&](int64_t c0, int64_t nv, const uint64_t *dstage) {
         /* the selection on the group's (N, a') records */
         int64_t gp[4] = {0, 0, 0, 0};
+        double t = 0;
         SlipRatioArgs R; memset(&R, 0, sizeof R);
         R.n = n; R.nprob = (int32_t) nv; R.pstride = n; R.oidx = I.oidx;
         R.xlen = drl + c0 * n; R.xoff = dso + c0 * n; R.xlimbs = dstage;
         R.alen = dal2 + c0 * n; R.aoff = dao2 + c0 * n; R.alimbs = I.mode ? dbd + bdn : I.a.limbs;
         R.asense = I.mode ? 1 : I.sense; R.xflip = I.mode;
-        t = 0;
-        A_(ratio_core(R, key, hres + c0, hres + nprob + c0, hres + 2 * (int64_t) nprob + c0, NULL, NULL, NULL, stream, &t, gp));
+        int rc = ratio_core(R, key, hres + c0, hres + nprob + c0, hres + 2 * (int64_t) nprob + c0, NULL, NULL, NULL, stream, &t, gp);
         if (!rc) { ms[1] += t; for (int k = 0; k < 4; k++) paths[4 + k] += gp[k]; }
         /* the winners' sides and, on request, their records */
         UP_(dsel, hres + c0, (size_t) nv * 4);
@@ -5648,52 +5705,21 @@ static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const Slip
             HIP_(hipStreamSynchronize(stream));
         }
         DOWN_(hres + 3 * (int64_t) nprob + c0, dsel + nprob, (size_t) nv * 4);
-        if (wlen_out) {
-            int32_t *nl = NULL, *al = NULL; uint64_t *nvl = NULL, *avl = NULL; int64_t nn = 0, an = 0;
-            A_(pack_download(nv, dwn, dwo, dstage, 0, &nl, &nvl, &nn, stream));
-            if (!I.mode) A_(pack_download(nv, dwn + nprob, dwo + nprob, I.a.limbs, 0, &al, &avl, &an, stream));
-            if (!rc) {
-                int64_t on = 0, oa = 0;
-                for (int64_t c = 0; c < nv; c++) {
-                    const int64_t ln = nl[c] < 0 ? -nl[c] : nl[c];
-                    wl.push_back(nl[c]); wv.insert(wv.end(), nvl + on, nvl + on + ln); on += ln;
-                    if (!I.mode) {
-                        const int64_t la = al[c] < 0 ? -al[c] : al[c];
-                        wl.push_back(al[c]); wv.insert(wv.end(), avl + oa, avl + oa + la); oa += la;
-                    }
-                }
-            }
-            free(nl); free(al); free(nvl); free(avl);
-        }
-        dev_free(dstage);
-    }
+        if (wlen_out) A_(winners_collect(nv, dwn, dwo, dstage, dwn + nprob, dwo + nprob, I.mode ? NULL : I.a.limbs, &wl, &wv, stream));
+        return rc;
+    };
+    A_(staged_run(n, nprob, 1, wcap, dw, dso, form, select, stream, &ms[0], &ms[0]));
     DOWN_(hpaths, dpaths, 32);
-    int32_t *ol = NULL; uint64_t *ov = NULL;
-    if (!rc && wlen_out) {
-        ol = (int32_t *) malloc((size_t)(per * nprob) * 4); ov = (uint64_t *) malloc((wv.size() > 0 ? wv.size() : 1) * 8);
-        if (!ol || !ov) { free(ol); free(ov); rc = SLIP_HIP_OUT_OF_MEMORY; }
-        else {
-            memcpy(ol, wl.data(), (size_t)(per * nprob) * 4);
-            if (!wv.empty()) memcpy(ov, wv.data(), wv.size() * 8);
-        }
-    }
+    if (!rc && wlen_out) rc = winners_out(wl, wv, wlen_out, wlimbs_out, wnl_out);
     if (!rc) {
         memcpy(res, hres, (size_t) nprob * 16);
         for (int k = 0; k < 4; k++) paths[k] = (int64_t) hpaths[k];
-        if (wlen_out) { *wlen_out = ol; *wlimbs_out = ov; *wnl_out = (int64_t) wv.size(); }
     }
     free(hres);
-    dev_free(dkind); dev_free(dlol); dev_free(dhil); dev_free(dloo); dev_free(dhio); dev_free(dlov); dev_free(dhiv); dev_free(dbd);
-    dev_free(dcls); dev_free(dw); dev_free(drl); dev_free(dso); dev_free(dal2); dev_free(dao2); dev_free(dwmax); dev_free(dpaths);
-    dev_free(dsel); dev_free(dwn); dev_free(dwo); dev_free(bsum); dev_free(dscr);
+    dev_slab_free(&lo); dev_slab_free(&hi);
+    dev_free(dkind); dev_free(dbd); dev_free(dcls); dev_free(dw); dev_free(drl); dev_free(dso); dev_free(dal2); dev_free(dao2);
+    dev_free(dwmax); dev_free(dpaths); dev_free(dsel); dev_free(dwn); dev_free(dwo); dev_free(dscr);
     return rc;
-}
-
-/* the 4 * nprob results of bound_core into the caller's four arrays */
-static void bound_results(const int32_t *res, int32_t nprob, int32_t *r0, int32_t *r1, int32_t *r2, int32_t *r3)
-{
-    memcpy(r0, res, (size_t) nprob * 4); memcpy(r1, res + nprob, (size_t) nprob * 4);
-    memcpy(r2, res + 2 * (size_t) nprob, (size_t) nprob * 4); memcpy(r3, res + 3 * (size_t) nprob, (size_t) nprob * 4);
 }
 
 /* both fused forms: mode 0 the bounded ratio test on 2 * nprob right-hand sides, mode 1 the bound test on nprob */
@@ -5705,7 +5731,7 @@ static int bound_on_handle(slip_hip_factor *f, int mode, int32_t transpose, int3
     if (!f || nprob < 1 || nprob > (1 << 29) || (sense != 1 && sense != -1) || !blen || !blimbs || !r0 || !r1 || !r2 || !r3 ||
         !bounds || !bounds->kind)
         return SLIP_HIP_INCORRECT_INPUT;
-    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (winners_args_bad(wlen_out, wlimbs_out, wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
     if (!transpose && f->factors_only) return SLIP_HIP_INCORRECT_INPUT;             /* no q behind such a handle */
     if (f->broken) return SLIP_HIP_DEVICE_ERROR;
     if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
@@ -5717,17 +5743,11 @@ static int bound_on_handle(slip_hip_factor *f, int mode, int32_t transpose, int3
     int rc = solve_device(f, transpose, per * nprob, blen, blimbs, stream, &o);
     if (rc) { host_bounds_free(&hb); return rc; }
     if (wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
-    int32_t *ddlen = NULL, *doidx = NULL, *dpos = NULL, *hidx = NULL, *res = (int32_t *) malloc((size_t) nprob * 16); int64_t *ddoff = NULL;
+    int32_t *ddlen = NULL, *doidx = NULL, *dpos = NULL, *res = (int32_t *) malloc((size_t) nprob * 16); int64_t *ddoff = NULL;
     int32_t dmaxdig = 0;
     if (!res) rc = SLIP_HIP_OUT_OF_MEMORY;
     A_(det_records(f, nprob, &ddlen, &ddoff, &dmaxdig));
-    if (!rc && transpose) {                                /* position p of the transposed solve is row i, pinv[i] = p */
-        hidx = (int32_t *) malloc((size_t) n * 4);
-        if (!hidx) rc = SLIP_HIP_OUT_OF_MEMORY;
-        else for (int32_t i = 0; i < n; i++) hidx[f->tpinv[i]] = i;
-        A_(dev_alloc(&doidx, n)); UP_(doidx, hidx, (size_t) n * 4);
-        A_(dev_alloc(&dpos, n)); UP_(dpos, f->tpinv, (size_t) n * 4);
-    }
+    A_(transposed_maps(f, transpose, &doidx, &dpos));
     SlipBoundIn I; memset(&I, 0, sizeof I);
     I.n = n; I.nprob = nprob; I.mode = mode; I.sense = sense; I.oidx = doidx; I.pos = dpos;
     I.x.len = o.olen; I.x.off = o.ooff; I.x.limbs = o.olimbs; I.xstride = (int64_t) per * n;
@@ -5736,10 +5756,10 @@ static int bound_on_handle(slip_hip_factor *f, int mode, int32_t transpose, int3
     double ms[2]; int64_t paths[8];
     A_(bound_core(I, bounds, hb, key, res, wlen_out, wlimbs_out, wnl_out, stream, ms, paths));
     if (!rc) {
-        bound_results(res, nprob, r0, r1, r2, r3);
+        results_out(res, nprob, r0, r1, r2, r3);
         memcpy(f->bound_ms, ms, sizeof ms); memcpy(f->bound_paths, paths, sizeof paths);
     }
-    free(hidx); free(res); dev_free(doidx); dev_free(dpos); dev_free(ddlen); dev_free(ddoff);
+    free(res); dev_free(doidx); dev_free(dpos); dev_free(ddlen); dev_free(ddoff);
     solve_out_free(&o);
     host_bounds_free(&hb);
     return rc;
@@ -5772,32 +5792,31 @@ static int bound_on_slabs(int mode, int32_t n, int32_t nprob, const int32_t *xle
     if (n <= 0 || nprob < 1 || nprob > (1 << 29) || (sense != 1 && sense != -1) || !xlen || !xlimbs || (!mode && (!alen || !alimbs)) ||
         !dlen || !dlimbs || !r0 || !r1 || !r2 || !r3 || !bounds || !bounds->kind)
         return SLIP_HIP_INCORRECT_INPUT;
-    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (winners_args_bad(wlen_out, wlimbs_out, wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
     TRY_(need_device());
     const int64_t ne = (int64_t) n * nprob;
     SlipHostBounds hb;
     TRY_(host_bounds(n, bounds, &hb));
-    SlipSlab xs, as, ds; memset(&xs, 0, sizeof xs); memset(&as, 0, sizeof as); memset(&ds, 0, sizeof ds);
-    int32_t *dxl = NULL, *dal = NULL, *ddl = NULL, *res = NULL; int64_t *dxo = NULL, *dao = NULL, *ddo = NULL; uint64_t *dxv = NULL, *dav = NULL, *ddv = NULL;
+    SlipDevSlab x, a, d; memset(&x, 0, sizeof x); memset(&a, 0, sizeof a); memset(&d, 0, sizeof d);
+    int32_t *res = NULL;
     /* (every slab is checked against its capacity before a limb of it is read) */
-    int rc = ratio_upload(nprob, dlen, dlimbs, d_limbs, &ds, &ddl, &ddo, &ddv);
-    for (int32_t c = 0; c < nprob && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
-    A_(ratio_upload(ne, xlen, xlimbs, x_limbs, &xs, &dxl, &dxo, &dxv));
-    if (!mode) A_(ratio_upload(ne, alen, alimbs, a_limbs, &as, &dal, &dao, &dav));
+    int rc = dev_slab_upload(nprob, dlen, dlimbs, d_limbs, &d);
+    for (int32_t c = 0; c < nprob && !rc; c++) if (d.s.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    A_(dev_slab_upload(ne, xlen, xlimbs, x_limbs, &x));
+    if (!mode) A_(dev_slab_upload(ne, alen, alimbs, a_limbs, &a));
     if (!rc && !(res = (int32_t *) malloc((size_t) nprob * 16))) rc = SLIP_HIP_OUT_OF_MEMORY;
     if (!rc && wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
     SlipBoundIn I; memset(&I, 0, sizeof I);
     I.n = n; I.nprob = nprob; I.mode = mode; I.sense = sense; I.xstride = n; I.astride = n;
-    I.x.len = dxl; I.x.off = dxo; I.x.limbs = dxv; I.a.len = dal; I.a.off = dao; I.a.limbs = dav; I.d.len = ddl; I.d.off = ddo; I.d.limbs = ddv;
+    I.x = dev_slab_recs(x); I.a = dev_slab_recs(a); I.d = dev_slab_recs(d);
     double ms[2]; int64_t paths[8];
     A_(bound_core(I, bounds, hb, key, res, wlen_out, wlimbs_out, wnl_out, (hipStream_t) stream_v, ms, paths));
     if (!rc) {
-        bound_results(res, nprob, r0, r1, r2, r3);
+        results_out(res, nprob, r0, r1, r2, r3);
         memcpy(slip_bound_paths_last, paths, sizeof paths);
     }
     free(res);
-    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dal); dev_free(dao); dev_free(dav); dev_free(ddl); dev_free(ddo); dev_free(ddv);
-    slab_free(&xs); slab_free(&as); slab_free(&ds);
+    dev_slab_free(&x); dev_slab_free(&a); dev_slab_free(&d);
     host_bounds_free(&hb);
     return rc;
 }
@@ -5867,7 +5886,7 @@ static int pivot_core(const SlipPivotIn &I, int32_t *ninexact, int32_t **rlen_ou
     const int32_t n = I.n, nprob = I.nprob;
     const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE;
     int32_t *dcls = NULL, *dw = NULL, *drl = NULL, *dwmax = NULL, *dnin = NULL; int64_t *dso = NULL;
-    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, *bsum = NULL, hpaths[4] = {0, 0, 0, 0};
+    dig_t *dscr = NULL; unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
     int32_t hwmax[2] = {0, 0};
     int32_t *hnin = (int32_t *) malloc((size_t) nprob * 4), *ol = (int32_t *) malloc((size_t) ne * 4);
     uint64_t *out = NULL; int64_t on = 0;                  /* the result's limbs so far: every group's slab is appended */
@@ -5900,51 +5919,25 @@ static int pivot_core(const SlipPivotIn &I, int32_t *ninexact, int32_t **rlen_ou
     DOWN_(hwmax, dwmax, 8);
     const int64_t wcap = hwmax[0] > 1 ? ((int64_t) hwmax[0] + 1) & ~(int64_t) 1 : 2, scap = ((int64_t) hwmax[1] + 1) & ~(int64_t) 1;
     if (!rc && (wcap > (1 << 28) || scap > (1 << 27))) rc = SLIP_HIP_OUT_OF_MEMORY;
-    int64_t group = rc ? 1 : product_stage_limbs() / ((int64_t) n * (wcap / 2));       /* problems staged together */
-    if (group < 1) group = 1;
-    if (group > nprob) group = nprob;
     /* per wave: the 64 * 5 + 2 digits a register shift goes through, or the seven buffers of the memory path */
     const int64_t wscr = 7 * scap > 328 ? 7 * scap : 328;
-    const int64_t wblocks = fit_scratch(wave_blocks(ne), wscr), sblocks = offscan_blocks((int64_t) n * group);
-    A_(dev_alloc(&bsum, sblocks));
+    const int64_t wblocks = fit_scratch(wave_blocks(ne), wscr);
     A_(dev_alloc(&dscr, wblocks * SERVICE_WAVES * wscr));
     A.scratch = dscr; A.wcap = (int32_t) scap; A.wscr = (int32_t) wscr;
-    for (int64_t c0 = 0; c0 < nprob && !rc; c0 += group) {
-        const int64_t nv = c0 + group <= nprob ? group : nprob - c0, cnt = (int64_t) n * nv;
-        uint64_t *dstage = NULL; int64_t total = 0;
-        double t = 0;
-        {                                                  /* the staging offsets from the widths */
-            SlipTimed timed;
-            A_(timed.begin(stream));
-            A_(offscan_run(cnt, dw + c0 * n, dso + c0 * n, bsum, sblocks, stream));
-            A_(timed.end(stream, &t));
-            *ms += t;
-        }
-        A_(offscan_total(bsum, sblocks, &total, stream));
-        if (!rc && total > cnt * (wcap / 2)) rc = SLIP_HIP_DEVICE_ERROR;           /* (the widths' bound: the host's own figure) */
-        A_(dev_alloc(&dstage, total));
-        if (!rc) {                                         /* the lane pass, the wave pass, the placed entries */
-            SlipTimed timed;
-            A.stage = dstage;
-            A_(timed.begin(stream));
-            slice(c0, nv, 1); A_(SERVICE_LAUNCH(pivot, wave_blocks(rpp * nv), stream, A));
-            slice(c0, nv, 2); A_(SERVICE_LAUNCH(pivot, wave_blocks(cnt) < wblocks ? wave_blocks(cnt) : wblocks, stream, A));
-            if (I.place) { slice(c0, nv, 3); A_(SERVICE_LAUNCH(pivot, wave_blocks(nv), stream, A)); }
-            A_(timed.end(stream, &t));
-            *ms += t;
-        }
-        int32_t *gl = NULL; uint64_t *gv = NULL; int64_t gn = 0;
-        A_(pack_download(cnt, drl + c0 * n, dso + c0 * n, dstage, 0, &gl, &gv, &gn, stream));
-        if (!rc && c0 == 0 && nv == nprob) { out = gv; on = gn; gv = NULL; }       /* one group: its slab is the result */
-        else if (!rc) {
-            uint64_t *grown = (uint64_t *) realloc(out, (size_t)(on + gn > 0 ? on + gn : 1) * 8);
-            if (!grown) rc = SLIP_HIP_OUT_OF_MEMORY;
-            else { out = grown; memcpy(out + on, gv, (size_t) gn * 8); on += gn; }
-        }
-        if (!rc) memcpy(ol + c0 * n, gl, (size_t) cnt * 4);
-        free(gl); free(gv);
-        dev_free(dstage);
-    }
+    /* a group of whole problems into the staging slab: the lane pass, the wave pass, the placed entries */
+    auto form = [&](int64_t c0, int64_t nv, int64_t cnt, uint64_t *dstage) {
+        int rc = 0;
+        A.stage = dstage;
+        slice(c0, nv, 1); A_(SERVICE_LAUNCH(pivot, wave_blocks(rpp * nv), stream, A));
+        slice(c0, nv, 2); A_(SERVICE_LAUNCH(pivot, wave_blocks(cnt) < wblocks ? wave_blocks(cnt) : wblocks, stream, A));
+        if (I.place) { slice(c0, nv, 3); A_(SERVICE_LAUNCH(pivot, wave_blocks(nv), stream, A)); }
+        return rc;
+    };
+    /* (the block of a call that fits one group is the result as pack_download made it) */
+    auto sink = [&](int64_t c0, int64_t nv, const uint64_t *dstage) {
+        return pack_append(n * nv, drl + c0 * n, dso + c0 * n, dstage, ol + c0 * n, &out, &on, stream);
+    };
+    A_(staged_run(n, nprob, 1, wcap, dw, dso, form, sink, stream, ms, ms));
     DOWN_(hpaths, dpaths, 32); DOWN_(hnin, dnin, (size_t) nprob * 4);
     if (!rc) {
         memcpy(ninexact, hnin, (size_t) nprob * 4);
@@ -5954,17 +5947,7 @@ static int pivot_core(const SlipPivotIn &I, int32_t *ninexact, int32_t **rlen_ou
         ol = NULL; out = NULL;
     }
     free(hnin); free(ol); free(out);
-    dev_free(dcls); dev_free(dw); dev_free(drl); dev_free(dso); dev_free(dwmax); dev_free(dpaths); dev_free(dnin);
-    dev_free(bsum); dev_free(dscr);
-    return rc;
-}
-
-/* a slab the host has laid out (s) on the device */
-static int pivot_upload(int64_t count, const SlipSlab &s, const uint64_t *limbs, int32_t **dlen, int64_t **doff, uint64_t **dlimbs)
-{
-    int rc = 0;
-    A_(dev_alloc(dlen, count)); A_(dev_alloc(doff, count)); A_(dev_alloc(dlimbs, s.total));
-    UP_(*dlen, s.dig, (size_t) count * 4); UP_(*doff, s.off, (size_t) count * 8); UP_(*dlimbs, limbs, (size_t) s.total * 8);
+    dev_free(dcls); dev_free(dw); dev_free(drl); dev_free(dso); dev_free(dwmax); dev_free(dpaths); dev_free(dnin); dev_free(dscr);
     return rc;
 }
 
@@ -5988,34 +5971,30 @@ extern "C" int slip_hip_pivot_update(int32_t n, int32_t nprob,
         !dlen != !dlimbs || !ninexact || !rlen_out || !rlimbs_out || !rnl_out || !pivot_place_ok(place, nprob, n))
         return SLIP_HIP_INCORRECT_INPUT;
     const int64_t ne = (int64_t) n * nprob;
-    SlipSlab vs, as, ps, ts, ds; memset(&vs, 0, sizeof vs); memset(&as, 0, sizeof as); memset(&ps, 0, sizeof ps); memset(&ts, 0, sizeof ts); memset(&ds, 0, sizeof ds);
-    int32_t *dvl = NULL, *dal = NULL, *dpl = NULL, *dtl = NULL, *ddl = NULL, *dplace = NULL;
-    int64_t *dvo = NULL, *dao = NULL, *dpo = NULL, *dto = NULL, *ddo = NULL; uint64_t *dvv = NULL, *dav = NULL, *dpv = NULL, *dtv = NULL, *ddv = NULL;
-    /* (every slab is checked against its capacity before a limb of it is read) */
-    int rc = slab_prepare(ne, vlen, vlimbs, v_limbs, &vs);
-    A_(slab_prepare(ne, alen, alimbs, a_limbs, &as));
-    A_(slab_prepare(nprob, plen, plimbs, p_limbs, &ps));
-    A_(slab_prepare(nprob, tlen, tlimbs, t_limbs, &ts));
+    SlipDevSlab v, a, p, t, d; memset(&v, 0, sizeof v); memset(&a, 0, sizeof a); memset(&p, 0, sizeof p); memset(&t, 0, sizeof t); memset(&d, 0, sizeof d);
+    int32_t *dplace = NULL;
+    /* (every slab is checked against its capacity before a limb of it is read, and all of them before the device is asked for) */
+    int rc = slab_prepare(ne, vlen, vlimbs, v_limbs, &v.s);
+    A_(slab_prepare(ne, alen, alimbs, a_limbs, &a.s));
+    A_(slab_prepare(nprob, plen, plimbs, p_limbs, &p.s));
+    A_(slab_prepare(nprob, tlen, tlimbs, t_limbs, &t.s));
     if (dlen) {
-        A_(slab_prepare(nprob, dlen, dlimbs, d_limbs, &ds));
-        for (int32_t c = 0; c < nprob && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+        A_(slab_prepare(nprob, dlen, dlimbs, d_limbs, &d.s));
+        for (int32_t c = 0; c < nprob && !rc; c++) if (d.s.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
     }
     A_(need_device());
-    A_(pivot_upload(ne, vs, vlimbs, &dvl, &dvo, &dvv)); A_(pivot_upload(ne, as, alimbs, &dal, &dao, &dav));
-    A_(pivot_upload(nprob, ps, plimbs, &dpl, &dpo, &dpv)); A_(pivot_upload(nprob, ts, tlimbs, &dtl, &dto, &dtv));
-    if (dlen) A_(pivot_upload(nprob, ds, dlimbs, &ddl, &ddo, &ddv));
+    A_(dev_slab_put(ne, v.s, vlimbs, &v)); A_(dev_slab_put(ne, a.s, alimbs, &a));
+    A_(dev_slab_put(nprob, p.s, plimbs, &p)); A_(dev_slab_put(nprob, t.s, tlimbs, &t));
+    if (dlen) A_(dev_slab_put(nprob, d.s, dlimbs, &d));
     if (place) { A_(dev_alloc(&dplace, nprob)); UP_(dplace, place, (size_t) nprob * 4); }
     SlipPivotIn I; memset(&I, 0, sizeof I);
     I.n = n; I.nprob = nprob; I.vstride = n; I.astride = n; I.place = dplace;
-    I.v.len = dvl; I.v.off = dvo; I.v.limbs = dvv; I.a.len = dal; I.a.off = dao; I.a.limbs = dav;
-    I.p.len = dpl; I.p.off = dpo; I.p.limbs = dpv; I.t.len = dtl; I.t.off = dto; I.t.limbs = dtv;
-    I.d.len = ddl; I.d.off = ddo; I.d.limbs = ddv;
+    I.v = dev_slab_recs(v); I.a = dev_slab_recs(a); I.p = dev_slab_recs(p); I.t = dev_slab_recs(t); I.d = dev_slab_recs(d);
     double ms; int64_t paths[8];
     A_(pivot_core(I, ninexact, rlen_out, rlimbs_out, rnl_out, (hipStream_t) stream_v, &ms, paths));
     if (!rc) memcpy(slip_pivot_paths_last, paths, sizeof paths);
-    dev_free(dvl); dev_free(dvo); dev_free(dvv); dev_free(dal); dev_free(dao); dev_free(dav); dev_free(dpl); dev_free(dpo); dev_free(dpv);
-    dev_free(dtl); dev_free(dto); dev_free(dtv); dev_free(ddl); dev_free(ddo); dev_free(ddv); dev_free(dplace);
-    slab_free(&vs); slab_free(&as); slab_free(&ps); slab_free(&ts); slab_free(&ds);
+    dev_slab_free(&v); dev_slab_free(&a); dev_slab_free(&p); dev_slab_free(&t); dev_slab_free(&d);
+    dev_free(dplace);
     return rc;
 }
 
@@ -6041,42 +6020,32 @@ static int update_on_handle(slip_hip_factor *f, int step, int32_t transpose, int
     const int32_t n = f->n;
     SlipSolveOut o;
     TRY_(solve_device(f, transpose, 2 * nprob, blen, blimbs, stream, &o));
-    int32_t *ddlen = NULL, *doidx = NULL, *dpos = NULL, *hidx = NULL, *dpl = NULL, *dtl = NULL, *dplace = NULL, *dbest = NULL;
-    int64_t *ddoff = NULL, *dpo = NULL, *dto = NULL; uint64_t *dpv = NULL, *dtv = NULL;
+    int32_t *ddlen = NULL, *doidx = NULL, *dpos = NULL, *dplace = NULL, *dbest = NULL; int64_t *ddoff = NULL;
+    SlipDevSlab dp, dt; memset(&dp, 0, sizeof dp); memset(&dt, 0, sizeof dt);      /* (step 1: records alone, into the solve's output) */
     int32_t *hbest = NULL, *hties = NULL, *helig = NULL, *rl = NULL, *nl = NULL; uint64_t *rv = NULL, *nv = NULL; int64_t rn = 0, nn = 0;
     int32_t dmaxdig = 0;
     int rc = 0;
     A_(det_records(f, nprob, &ddlen, &ddoff, &dmaxdig));
-    if (!rc && transpose) {                                /* position p of the transposed solve is row i, pinv[i] = p */
-        hidx = (int32_t *) malloc((size_t) n * 4);
-        if (!hidx) rc = SLIP_HIP_OUT_OF_MEMORY;
-        else for (int32_t i = 0; i < n; i++) hidx[f->tpinv[i]] = i;
-        A_(dev_alloc(&doidx, n)); UP_(doidx, hidx, (size_t) n * 4);
-        A_(dev_alloc(&dpos, n)); UP_(dpos, f->tpinv, (size_t) n * 4);
-    }
+    A_(transposed_maps(f, transpose, &doidx, &dpos));
     SlipPivotIn I; memset(&I, 0, sizeof I);
     I.n = n; I.nprob = nprob; I.oidx = doidx; I.pos = dpos; I.vstride = I.astride = 2 * (int64_t) n;
     I.v.len = o.olen; I.v.off = o.ooff; I.v.limbs = o.olimbs; I.a.len = o.olen + n; I.a.off = o.ooff + n; I.a.limbs = o.olimbs;
     I.d.len = ddlen; I.d.off = ddoff; I.d.limbs = f->P.Llimbs;
-    A_(dev_alloc(&dpl, nprob)); A_(dev_alloc(&dpo, nprob)); A_(dev_alloc(&dtl, nprob)); A_(dev_alloc(&dto, nprob));
     double sel_ms = 0;
     if (!step) {
-        A_(dev_alloc(&dpv, ps->total)); A_(dev_alloc(&dtv, ts->total));
-        UP_(dpl, ps->dig, (size_t) nprob * 4); UP_(dpo, ps->off, (size_t) nprob * 8); UP_(dpv, plimbs, (size_t) ps->total * 8);
-        UP_(dtl, ts->dig, (size_t) nprob * 4); UP_(dto, ts->off, (size_t) nprob * 8); UP_(dtv, tlimbs, (size_t) ts->total * 8);
+        A_(dev_slab_put(nprob, *ps, plimbs, &dp)); A_(dev_slab_put(nprob, *ts, tlimbs, &dt));
         if (place) { A_(dev_alloc(&dplace, nprob)); UP_(dplace, place, (size_t) nprob * 4); }
-        I.p.limbs = dpv; I.t.limbs = dtv;
     } else {
+        A_(dev_alloc(&dp.len, nprob)); A_(dev_alloc(&dp.off, nprob)); A_(dev_alloc(&dt.len, nprob)); A_(dev_alloc(&dt.off, nprob));
         hbest = (int32_t *) malloc((size_t) nprob * 4); hties = (int32_t *) malloc((size_t) nprob * 4); helig = (int32_t *) malloc((size_t) nprob * 4);
         if (!hbest || !hties || !helig) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
         /* the selection, as slip_hip_factor_ratio_test makes it: the sign of det decides which sign of anum is eligible */
-        SlipPiv pr; memset(&pr, 0, sizeof pr);
-        DOWN_(&pr, f->P.piv.p_ + (n - 1), sizeof pr);
-        if (!rc && pr.len == 0) rc = SLIP_HIP_DEVICE_ERROR;
+        int dneg = 0;
+        A_(det_negative(f, &dneg));
         SlipRatioArgs R; memset(&R, 0, sizeof R);
         R.n = n; R.nprob = nprob; R.pstride = 2 * (int64_t) n; R.oidx = doidx;
         R.xlen = o.olen; R.xoff = o.ooff; R.xlimbs = o.olimbs; R.alen = o.olen + n; R.aoff = o.ooff + n; R.alimbs = o.olimbs;
-        R.asense = pr.len < 0 ? -sense : sense; R.xflip = pr.len < 0;
+        R.asense = dneg ? -sense : sense; R.xflip = dneg;
         f->ratio_ms = 0; memset(f->ratio_paths, 0, sizeof f->ratio_paths);
         A_(ratio_core(R, key, hbest, hties, helig, NULL, NULL, NULL, stream, &f->ratio_ms, f->ratio_paths));
         sel_ms = f->ratio_ms;
@@ -6087,15 +6056,15 @@ static int update_on_handle(slip_hip_factor *f, int step, int32_t transpose, int
             SlipPivotArgs W; memset(&W, 0, sizeof W);
             W.n = n; W.nprob = nprob; W.phase = 4; W.vstride = I.vstride; W.astride = I.astride; W.pos = dpos;
             W.vlen = I.v.len; W.voff = I.v.off; W.alen = I.a.len; W.aoff = I.a.off;
-            W.best = dbest; W.wplen = dpl; W.wpoff = dpo; W.wtlen = dtl; W.wtoff = dto; W.wplace = dplace;
+            W.best = dbest; W.wplen = dp.len; W.wpoff = dp.off; W.wtlen = dt.len; W.wtoff = dt.off; W.wplace = dplace;
             A_(SERVICE_LAUNCH(pivot, service_blocks(nprob), stream, W));
         }
-        I.p.limbs = o.olimbs; I.t.limbs = o.olimbs;
     }
-    I.p.len = dpl; I.p.off = dpo; I.t.len = dtl; I.t.off = dto; I.place = dplace;
+    I.p = dev_slab_recs(dp); I.t = dev_slab_recs(dt); I.place = dplace;
+    if (step) I.p.limbs = I.t.limbs = o.olimbs;
     double ms = 0; int64_t paths[8];
     A_(pivot_core(I, ninexact, &rl, &rv, &rn, stream, &ms, paths));
-    if (step) A_(pack_download(nprob, dpl, dpo, o.olimbs, 0, &nl, &nv, &nn, stream));
+    if (step) A_(pack_download(nprob, dp.len, dp.off, o.olimbs, 0, &nl, &nv, &nn, stream));
     if (!rc) {
         f->update_ms[0] = ms; f->update_ms[1] = sel_ms; memcpy(f->update_paths, paths, sizeof paths);
         *rlen_out = rl; *rlimbs_out = rv; *rnl_out = rn; rl = NULL; rv = NULL;
@@ -6104,9 +6073,9 @@ static int update_on_handle(slip_hip_factor *f, int step, int32_t transpose, int
             *dlen_out = nl; *dlimbs_out = nv; *dnl_out = nn; nl = NULL; nv = NULL;
         }
     }
-    free(hidx); free(hbest); free(hties); free(helig); free(rl); free(rv); free(nl); free(nv);
-    dev_free(ddlen); dev_free(ddoff); dev_free(doidx); dev_free(dpos); dev_free(dpl); dev_free(dpo); dev_free(dtl); dev_free(dto);
-    dev_free(dpv); dev_free(dtv); dev_free(dplace); dev_free(dbest);
+    free(hbest); free(hties); free(helig); free(rl); free(rv); free(nl); free(nv);
+    dev_free(ddlen); dev_free(ddoff); dev_free(doidx); dev_free(dpos); dev_free(dplace); dev_free(dbest);
+    dev_slab_free(&dp); dev_slab_free(&dt);
     solve_out_free(&o);
     return rc;
 }
@@ -6161,6 +6130,24 @@ extern "C" int slip_hip_factor_update_paths(const slip_hip_factor *f, int64_t ou
  * substitution (slip_solve_kernel on the view), the products with a resident matrix (slip_product_kernel) and the selection
  * (slip_ratio_kernel), joined by slip_price_kernel's records; no numerator leaves the device (no counterpart in the reference;
  * DESIGN 3k) ---- */
+
+/* det * g of a pricing call: the cost vectors' records (gs: nprob * ncols, laid out by the host) on the x side of every problem,
+ * empty records on its a side (nside 2), and the limbs as they came, into dg (zeroed) */
+static int price_costs_put(int32_t nside, int32_t nprob, int32_t ncols, const SlipSlab &gs, const uint64_t *glimbs, SlipDevSlab *dg)
+{
+    const int64_t ne = (int64_t) ncols * nside * nprob;
+    int32_t *hl = (int32_t *) calloc((size_t) ne, 4); int64_t *ho = (int64_t *) calloc((size_t) ne, 8);
+    int rc = !hl || !ho ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    if (!rc) for (int32_t c = 0; c < nprob; c++) {
+        memcpy(hl + (int64_t) nside * c * ncols, gs.dig + (int64_t) c * ncols, (size_t) ncols * 4);
+        memcpy(ho + (int64_t) nside * c * ncols, gs.off + (int64_t) c * ncols, (size_t) ncols * 8);
+    }
+    A_(dev_alloc(&dg->len, ne)); A_(dev_alloc(&dg->off, ne)); A_(dev_alloc(&dg->limbs, gs.total));
+    UP_(dg->len, hl, (size_t) ne * 4); UP_(dg->off, ho, (size_t) ne * 8); UP_(dg->limbs, glimbs, (size_t) gs.total * 8);
+    free(hl); free(ho);
+    return rc;
+}
+
 extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int32_t nside, int32_t nprob,
                                      const int32_t *blen, const uint64_t *blimbs,
                                      const int32_t *glen, const uint64_t *glimbs, int64_t g_limbs,
@@ -6171,12 +6158,12 @@ extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int
     if (!f || !M || !blen || !blimbs || !best || !nties || !neligible || !vsign || (nside != 1 && nside != 2) || nprob < 1 ||
         nprob > (1 << 29) || (sense != 1 && sense != -1) || !glen != !glimbs)
         return SLIP_HIP_INCORRECT_INPUT;
-    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (winners_args_bad(wlen_out, wlimbs_out, wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
     if (M->m != f->n) return SLIP_HIP_INCORRECT_INPUT;
     if (f->broken) return SLIP_HIP_DEVICE_ERROR;
     if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
     const int32_t n = f->n, ncols = M->ncols, nvec = nside * nprob;
-    const int64_t nxe = (int64_t) n * nvec, ne = (int64_t) ncols * nvec;
+    const int64_t nxe = (int64_t) n * nvec;
     hipStream_t stream = (hipStream_t) stream_v;
     SlipSlab gs; memset(&gs, 0, sizeof gs);
     if (glen) TRY_(slab_prepare((int64_t) nprob * ncols, glen, glimbs, g_limbs, &gs));
@@ -6184,8 +6171,8 @@ extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int
     SlipSolveOut o;
     int rc = solve_device(f, 1, nvec, blen, blimbs, stream, &o);
     if (rc) { slab_free(&gs); return rc; }
-    int32_t *dxl = NULL, *dgl = NULL, *ddlen = NULL, *dsel = NULL, *dwl = NULL; int64_t *dxo = NULL, *dgo = NULL, *ddoff = NULL, *dwo = NULL;
-    uint64_t *dgv = NULL;
+    int32_t *dxl = NULL, *ddlen = NULL, *dsel = NULL, *dwl = NULL; int64_t *dxo = NULL, *ddoff = NULL, *dwo = NULL;
+    SlipDevSlab dg; memset(&dg, 0, sizeof dg);
     int32_t dmaxdig = 0;
     /* the result on the host until all of it stands: best, nties, neligible, vsign, nprob each */
     int32_t *hres = (int32_t *) malloc((size_t) nprob * 16), *wl = wlen_out ? (int32_t *) malloc((size_t) nprob * 8) : NULL;
@@ -6193,11 +6180,9 @@ extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int
     double gather_ms = 0, ms[4] = {0, 0, 0, 0};
     int64_t paths[4] = {0, 0, 0, 0};
     if (!hres || (wlen_out && !wl)) rc = SLIP_HIP_OUT_OF_MEMORY;
-    /* the sign of det = rho[n-1] from its pivot record: it decides the eligible sign of A, the direction of X and vsign */
-    SlipPiv pr; memset(&pr, 0, sizeof pr);
-    DOWN_(&pr, f->P.piv.p_ + (n - 1), sizeof pr);
-    if (!rc && pr.len == 0) rc = SLIP_HIP_DEVICE_ERROR;
-    const int dneg = pr.len < 0;
+    /* the sign of det: it decides the eligible sign of A, the direction of X and vsign */
+    int dneg = 0;
+    A_(det_negative(f, &dneg));
     /* y by row id: the records of the substitution's output gathered through pinv, its limbs where they are */
     A_(dev_alloc(&dxl, nxe)); A_(dev_alloc(&dxo, nxe));
     if (!rc) {
@@ -6210,15 +6195,7 @@ extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int
     }
     /* det * g: the cost vector's records on the x side of every problem, empty records on its a side */
     if (glen) {
-        int32_t *hl = (int32_t *) calloc((size_t) ne, 4); int64_t *ho = (int64_t *) calloc((size_t) ne, 8);
-        if (!hl || !ho) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
-        else for (int32_t c = 0; c < nprob; c++) {
-            memcpy(hl + (int64_t) nside * c * ncols, gs.dig + (int64_t) c * ncols, (size_t) ncols * 4);
-            memcpy(ho + (int64_t) nside * c * ncols, gs.off + (int64_t) c * ncols, (size_t) ncols * 8);
-        }
-        A_(dev_alloc(&dgl, ne)); A_(dev_alloc(&dgo, ne)); A_(dev_alloc(&dgv, gs.total));
-        UP_(dgl, hl, (size_t) ne * 4); UP_(dgo, ho, (size_t) ne * 8); UP_(dgv, glimbs, (size_t) gs.total * 8);
-        free(hl); free(ho);
+        A_(price_costs_put(nside, nprob, ncols, gs, glimbs, &dg));
         A_(det_records(f, nvec, &ddlen, &ddoff, &dmaxdig));
     }
     /* per group: best (up), vsign (down), and without denominators the winners' records */
@@ -6227,7 +6204,7 @@ extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int
     SlipProductView V;
     V.nout = ncols; V.nx = n; V.alen = M->dAlen; V.aoff = M->dAoff; V.alimbs = M->dAlimbs; V.amaxdig = M->amaxdig;
     V.rp = M->col_rp; V.re = M->col_re; V.rx = M->col_rx;
-    const SlipDevRecs x = {dxl, dxo, o.olimbs}, g = {dgl, dgo, dgv};
+    const SlipDevRecs x = {dxl, dxo, o.olimbs}, g = dev_slab_recs(dg);
     /* the selection on a group of whole problems, on the staged records: X of problem c at c * pstride, A (nside 2) ncols on */
     auto select = [&](int64_t c0, int64_t nv, const int32_t *rlen, const int64_t *soff, const uint64_t *stage, double *t) {
         const int64_t p0 = c0 / nside;
@@ -6267,13 +6244,12 @@ extern "C" int slip_hip_factor_price(slip_hip_factor *f, slip_hip_matrix *M, int
         return rc;
     };
     A_(product_device(V, nvec, x, -1, glen ? &g : NULL, gs.maxdig, ddlen, ddoff, f->P.Llimbs, dmaxdig, nside, select, stream, ms));
-    dev_free(dxl); dev_free(dxo); dev_free(dgl); dev_free(dgo); dev_free(dgv); dev_free(ddlen); dev_free(ddoff);
-    dev_free(dsel); dev_free(dwl); dev_free(dwo);
+    dev_free(dxl); dev_free(dxo); dev_free(ddlen); dev_free(ddoff); dev_free(dsel); dev_free(dwl); dev_free(dwo);
+    dev_slab_free(&dg);
     slab_free(&gs);
     solve_out_free(&o);
     if (!rc) {
-        memcpy(best, hres, (size_t) nprob * 4); memcpy(nties, hres + nprob, (size_t) nprob * 4);
-        memcpy(neligible, hres + 2 * (size_t) nprob, (size_t) nprob * 4); memcpy(vsign, hres + 3 * (size_t) nprob, (size_t) nprob * 4);
+        results_out(hres, nprob, best, nties, neligible, vsign);
         if (wlen_out) { *wlen_out = wl; *wlimbs_out = wv; *wnl_out = wn; wl = NULL; wv = NULL; }
         ms[0] += gather_ms;
         memcpy(f->price_ms, ms, sizeof ms); memcpy(f->price_paths, paths, sizeof paths);
@@ -6318,10 +6294,10 @@ static int states_check(int32_t ncols, int32_t nside, const int32_t *state, cons
 }
 
 /* the same on the device: the states, the weights' records and limbs (NULL without weights), one limb holding 1 */
-struct SlipStatesOps { int32_t *state, *wtlen; int64_t *wtoff; uint64_t *wtlimbs, *one; };
+struct SlipStatesOps { int32_t *state; SlipDevSlab wt; uint64_t *one; };
 static void states_ops_free(SlipStatesOps *o)
 {
-    dev_free(o->state); dev_free(o->wtlen); dev_free(o->wtoff); dev_free(o->wtlimbs); dev_free(o->one);
+    dev_free(o->state); dev_slab_free(&o->wt); dev_free(o->one);
     memset(o, 0, sizeof *o);
 }
 static int states_upload(int32_t ncols, const int32_t *state, const SlipSlab *ws, const uint64_t *wlimbs, SlipStatesOps *o)
@@ -6331,10 +6307,7 @@ static int states_upload(int32_t ncols, const int32_t *state, const SlipSlab *ws
     memset(o, 0, sizeof *o);
     A_(dev_alloc(&o->state, ncols)); UP_(o->state, state, (size_t) ncols * 4);
     A_(dev_alloc(&o->one, 1)); UP_(o->one, &one, 8);
-    if (ws->dig) {
-        A_(dev_alloc(&o->wtlen, ncols)); A_(dev_alloc(&o->wtoff, ncols)); A_(dev_alloc(&o->wtlimbs, ws->total));
-        UP_(o->wtlen, ws->dig, (size_t) ncols * 4); UP_(o->wtoff, ws->off, (size_t) ncols * 8); UP_(o->wtlimbs, wlimbs, (size_t) ws->total * 8);
-    }
+    if (ws->dig) A_(dev_slab_put(ncols, *ws, wlimbs, &o->wt));
     if (rc) states_ops_free(o);
     return rc;
 }
@@ -6354,11 +6327,11 @@ static int states_core(const SlipStatesIn &I, const SlipStatesOps &O, const int3
                        std::vector<int32_t> *wl, std::vector<uint64_t> *wv, hipStream_t stream, double ms[2], int64_t paths[8])
 {
     const int32_t n = I.n, nprob = I.nprob;
-    const int weighted = O.wtlen != NULL;
+    const int weighted = O.wt.len != NULL;
     const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE;
     int32_t *dxl2 = NULL, *dal2 = NULL, *dcls = NULL, *dw = NULL, *dwmax = NULL, *dsel = NULL, *dwn = NULL;
     int64_t *dxo2 = NULL, *dao2 = NULL, *dso = NULL, *dwo = NULL;
-    unsigned long long *dpaths = NULL, *bsum = NULL, hpaths[4] = {0, 0, 0, 0};
+    unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
     int32_t hwmax = 0;
     int rc = 0;
     A_(dev_alloc(&dxl2, ne)); A_(dev_alloc(&dxo2, ne)); A_(dev_alloc(&dal2, ne)); A_(dev_alloc(&dao2, ne));
@@ -6369,7 +6342,7 @@ static int states_core(const SlipStatesIn &I, const SlipStatesOps &O, const int3
     if (weighted) HIP_(hipMemsetAsync(dwmax, 0, 4, stream));
     SlipStatesArgs A; memset(&A, 0, sizeof A);
     A.n = n; A.nside = I.nside; A.sense = I.sense; A.weighted = weighted; A.xstride = I.xstride; A.astride = I.astride;
-    A.xlimbs = I.x.limbs; A.alimbs = I.a.limbs; A.state = O.state; A.wtlen = O.wtlen; A.wtoff = O.wtoff;
+    A.xlimbs = I.x.limbs; A.alimbs = I.a.limbs; A.state = O.state; A.wtlen = O.wt.len; A.wtoff = O.wt.off;
     A.wmax = dwmax; A.paths = dpaths;
     /* the problems c0 .. c0 + nv of every per-problem and per-entry array */
     auto slice = [&](int64_t c0, int64_t nv, int phase) {
@@ -6389,52 +6362,24 @@ static int states_core(const SlipStatesIn &I, const SlipStatesOps &O, const int3
         A_(timed.end(stream, &t));
         ms[0] += t;
     }
-    /* the squares are staged in groups of whole problems (at least one: the bound never refuses) */
-    int64_t group = nprob, sblocks = 0;
-    if (weighted) {
-        DOWN_(&hwmax, dwmax, 4);
-        const int64_t wcap = hwmax > 2 ? hwmax : 2;        /* (even: twice an operand's digits) */
-        if (!rc && wcap > (1 << 28)) rc = SLIP_HIP_OUT_OF_MEMORY;
-        group = rc ? 1 : product_stage_limbs() / ((int64_t) n * (wcap / 2));
-        if (group < 1) group = 1;
-        if (group > nprob) group = nprob;
-        sblocks = offscan_blocks((int64_t) n * group);
-        A_(dev_alloc(&bsum, sblocks));
-    }
-    for (int64_t c0 = 0; c0 < nprob && !rc; c0 += group) {
-        const int64_t nv = c0 + group <= nprob ? group : nprob - c0, cnt = (int64_t) n * nv;
-        uint64_t *dstage = NULL; int64_t total = 0;
-        double t = 0;
-        if (weighted) {
-            {                                              /* the staging offsets from the widths */
-                SlipTimed timed;
-                A_(timed.begin(stream));
-                A_(offscan_run(cnt, dw + c0 * n, dso + c0 * n, bsum, sblocks, stream));
-                A_(timed.end(stream, &t));
-                ms[0] += t;
-            }
-            A_(offscan_total(bsum, sblocks, &total, stream));
-            if (!rc && total > cnt * (int64_t)(hwmax / 2)) rc = SLIP_HIP_DEVICE_ERROR;   /* (the widths' bound: the host's own figure) */
-            A_(dev_alloc(&dstage, total));
-            if (!rc) {                                     /* the squares into the slab: the lane pass, the wave pass */
-                SlipTimed timed;
-                A.stage = dstage;
-                A_(timed.begin(stream));
-                slice(c0, nv, 1); A_(SERVICE_LAUNCH(states, wave_blocks(rpp * nv), stream, A));
-                if (hwmax > 4) { slice(c0, nv, 2); A_(SERVICE_LAUNCH(states, wave_blocks(cnt), stream, A)); }
-                A_(timed.end(stream, &t));
-                ms[0] += t;
-            }
-        }
+    /* the squares of a group of whole problems into the staging slab: the lane pass, the wave pass */
+    auto form = [&](int64_t c0, int64_t nv, int64_t cnt, uint64_t *dstage) {
+        int rc = 0;
+        A.stage = dstage;
+        slice(c0, nv, 1); A_(SERVICE_LAUNCH(states, wave_blocks(rpp * nv), stream, A));
+        if (hwmax > 4) { slice(c0, nv, 2); A_(SERVICE_LAUNCH(states, wave_blocks(cnt), stream, A)); }
+        return rc;
+    };
+    auto select = [&](int64_t c0, int64_t nv, const uint64_t *dstage) {
         /* the selection on the group's records: the largest |X_j| or X_j^2 / w_j, or the smallest X_j / (sense * A_j) */
         int64_t gp[4] = {0, 0, 0, 0};
+        double t = 0;
         SlipRatioArgs R; memset(&R, 0, sizeof R);
         R.n = n; R.nprob = (int32_t) nv; R.pstride = n;
         R.xlen = dxl2 + c0 * n; R.xoff = weighted ? dso + c0 * n : dxo2 + c0 * n; R.xlimbs = weighted ? dstage : I.x.limbs;
-        R.alen = dal2 + c0 * n; R.aoff = dao2 + c0 * n; R.alimbs = I.nside == 2 ? I.a.limbs : weighted ? O.wtlimbs : O.one;
+        R.alen = dal2 + c0 * n; R.aoff = dao2 + c0 * n; R.alimbs = I.nside == 2 ? I.a.limbs : weighted ? O.wt.limbs : O.one;
         R.asense = I.nside == 2 ? I.sense : 1; R.xflip = I.nside == 1;
-        t = 0;
-        A_(ratio_core(R, key, r0 + c0, r1 + c0, r2 + c0, NULL, NULL, NULL, stream, &t, gp));
+        int rc = ratio_core(R, key, r0 + c0, r1 + c0, r2 + c0, NULL, NULL, NULL, stream, &t, gp);
         if (!rc) { ms[1] += t; for (int k = 0; k < 4; k++) paths[4 + k] += gp[k]; }
         /* the winners' direction and, on request, their records as they came in */
         UP_(dsel, r0 + c0, (size_t) nv * 4);
@@ -6446,38 +6391,21 @@ static int states_core(const SlipStatesIn &I, const SlipStatesOps &O, const int3
             HIP_(hipStreamSynchronize(stream));
         }
         DOWN_(r3 + c0, dsel + nprob, (size_t) nv * 4);
-        if (wl) {
-            int32_t *xl = NULL, *al = NULL; uint64_t *xv = NULL, *av = NULL; int64_t xn = 0, an = 0;
-            A_(pack_download(nv, dwn, dwo, I.x.limbs, 0, &xl, &xv, &xn, stream));
-            A_(pack_download(nv, dwn + nprob, dwo + nprob, I.nside == 2 ? I.a.limbs : I.x.limbs, 0, &al, &av, &an, stream));
-            if (!rc) {
-                int64_t ox = 0, oa = 0;
-                for (int64_t c = 0; c < nv; c++) {
-                    const int64_t lx = xl[c] < 0 ? -xl[c] : xl[c], la = al[c] < 0 ? -al[c] : al[c];
-                    wl->push_back(xl[c]); wv->insert(wv->end(), xv + ox, xv + ox + lx); ox += lx;
-                    wl->push_back(al[c]); wv->insert(wv->end(), av + oa, av + oa + la); oa += la;
-                }
-            }
-            free(xl); free(al); free(xv); free(av);
-        }
-        dev_free(dstage);
-    }
+        if (wl) A_(winners_collect(nv, dwn, dwo, I.x.limbs, dwn + nprob, dwo + nprob, I.nside == 2 ? I.a.limbs : I.x.limbs, wl, wv, stream));
+        return rc;
+    };
+    /* with weights the squares are staged in groups of whole problems; without, nothing is staged: one pass over all problems */
+    if (weighted) {
+        DOWN_(&hwmax, dwmax, 4);
+        const int64_t wcap = hwmax > 2 ? hwmax : 2;        /* (even: twice an operand's digits) */
+        if (!rc && wcap > (1 << 28)) rc = SLIP_HIP_OUT_OF_MEMORY;
+        A_(staged_run(n, nprob, 1, wcap, dw, dso, form, select, stream, &ms[0], &ms[0]));
+    } else A_(select(0, nprob, NULL));
     DOWN_(hpaths, dpaths, 32);
     if (!rc) for (int k = 0; k < 4; k++) paths[k] += (int64_t) hpaths[k];
     dev_free(dxl2); dev_free(dxo2); dev_free(dal2); dev_free(dao2); dev_free(dcls); dev_free(dw); dev_free(dso); dev_free(dwmax);
-    dev_free(dpaths); dev_free(dsel); dev_free(dwn); dev_free(dwo); dev_free(bsum);
+    dev_free(dpaths); dev_free(dsel); dev_free(dwn); dev_free(dwo);
     return rc;
-}
-
-/* the winners' records collected by states_core as the caller's malloc'ed slab */
-static int states_winners(const std::vector<int32_t> &wl, const std::vector<uint64_t> &wv, int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out)
-{
-    int32_t *ol = (int32_t *) malloc((wl.size() > 0 ? wl.size() : 1) * 4); uint64_t *ov = (uint64_t *) malloc((wv.size() > 0 ? wv.size() : 1) * 8);
-    if (!ol || !ov) { free(ol); free(ov); return SLIP_HIP_OUT_OF_MEMORY; }
-    if (!wl.empty()) memcpy(ol, wl.data(), wl.size() * 4);
-    if (!wv.empty()) memcpy(ov, wv.data(), wv.size() * 8);
-    *wlen_out = ol; *wlimbs_out = ov; *wnl_out = (int64_t) wv.size();
-    return SLIP_HIP_OK;
 }
 
 extern "C" int slip_hip_factor_price_states(slip_hip_factor *f, slip_hip_matrix *M, int32_t nside, int32_t nprob,
@@ -6491,12 +6419,12 @@ extern "C" int slip_hip_factor_price_states(slip_hip_factor *f, slip_hip_matrix 
     if (!f || !M || !blen || !blimbs || !best || !nties || !neligible || !vsign || (nside != 1 && nside != 2) || nprob < 1 ||
         nprob > (1 << 29) || (sense != 1 && sense != -1) || !glen != !glimbs)
         return SLIP_HIP_INCORRECT_INPUT;
-    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (winners_args_bad(wlen_out, wlimbs_out, wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
     if (M->m != f->n) return SLIP_HIP_INCORRECT_INPUT;
     if (f->broken) return SLIP_HIP_DEVICE_ERROR;
     if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
     const int32_t n = f->n, ncols = M->ncols, nvec = nside * nprob;
-    const int64_t nxe = (int64_t) n * nvec, ne = (int64_t) ncols * nvec;
+    const int64_t nxe = (int64_t) n * nvec;
     hipStream_t stream = (hipStream_t) stream_v;
     SlipSlab gs, ws; memset(&gs, 0, sizeof gs);
     TRY_(states_check(ncols, nside, state, wlen, wlimbs, w_limbs, &ws));
@@ -6505,7 +6433,8 @@ extern "C" int slip_hip_factor_price_states(slip_hip_factor *f, slip_hip_matrix 
     int rc = solve_device(f, 1, nvec, blen, blimbs, stream, &o);
     if (rc) { slab_free(&gs); slab_free(&ws); return rc; }
     if (wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
-    int32_t *dxl = NULL, *dgl = NULL, *ddlen = NULL; int64_t *dxo = NULL, *dgo = NULL, *ddoff = NULL; uint64_t *dgv = NULL;
+    int32_t *dxl = NULL, *ddlen = NULL; int64_t *dxo = NULL, *ddoff = NULL;
+    SlipDevSlab dg; memset(&dg, 0, sizeof dg);
     int32_t dmaxdig = 0;
     /* the result on the host until all of it stands: best, nties, neligible, vsign, nprob each */
     int32_t *hres = (int32_t *) malloc((size_t) nprob * 16);
@@ -6523,23 +6452,13 @@ extern "C" int slip_hip_factor_price_states(slip_hip_factor *f, slip_hip_matrix 
         A_(SERVICE_LAUNCH(price, service_blocks(nxe), stream, G));
     }
     /* det * g: the cost vector's records on the x side of every problem, empty records on its a side */
-    if (glen) {
-        int32_t *hl = (int32_t *) calloc((size_t) ne, 4); int64_t *ho = (int64_t *) calloc((size_t) ne, 8);
-        if (!hl || !ho) rc = rc ? rc : SLIP_HIP_OUT_OF_MEMORY;
-        else for (int32_t c = 0; c < nprob; c++) {
-            memcpy(hl + (int64_t) nside * c * ncols, gs.dig + (int64_t) c * ncols, (size_t) ncols * 4);
-            memcpy(ho + (int64_t) nside * c * ncols, gs.off + (int64_t) c * ncols, (size_t) ncols * 8);
-        }
-        A_(dev_alloc(&dgl, ne)); A_(dev_alloc(&dgo, ne)); A_(dev_alloc(&dgv, gs.total));
-        UP_(dgl, hl, (size_t) ne * 4); UP_(dgo, ho, (size_t) ne * 8); UP_(dgv, glimbs, (size_t) gs.total * 8);
-        free(hl); free(ho);
-    }
+    if (glen) A_(price_costs_put(nside, nprob, ncols, gs, glimbs, &dg));
     /* det's record once per vector: the products' d and, its sign alone, the d_c of every problem */
     A_(det_records(f, nvec, &ddlen, &ddoff, &dmaxdig));
     SlipProductView V;
     V.nout = ncols; V.nx = n; V.alen = M->dAlen; V.aoff = M->dAoff; V.alimbs = M->dAlimbs; V.amaxdig = M->amaxdig;
     V.rp = M->col_rp; V.re = M->col_re; V.rx = M->col_rx;
-    const SlipDevRecs x = {dxl, dxo, o.olimbs}, g = {dgl, dgo, dgv};
+    const SlipDevRecs x = {dxl, dxo, o.olimbs}, g = dev_slab_recs(dg);
     /* the selection on a group of whole problems, on the staged records: X of problem c at c * nside * ncols, A ncols on */
     auto select = [&](int64_t c0, int64_t nv, const int32_t *rlen, const int64_t *soff, const uint64_t *stage, double *t) {
         const int64_t p0 = c0 / nside;
@@ -6555,14 +6474,14 @@ extern "C" int slip_hip_factor_price_states(slip_hip_factor *f, slip_hip_matrix 
         return rc;
     };
     A_(product_device(V, nvec, x, -1, glen ? &g : NULL, gs.maxdig, ddlen, ddoff, f->P.Llimbs, dmaxdig, nside, select, stream, pms));
-    dev_free(dxl); dev_free(dxo); dev_free(dgl); dev_free(dgo); dev_free(dgv); dev_free(ddlen); dev_free(ddoff);
+    dev_free(dxl); dev_free(dxo); dev_free(ddlen); dev_free(ddoff);
+    dev_slab_free(&dg);
     states_ops_free(&O);
     slab_free(&gs); slab_free(&ws);
     solve_out_free(&o);
-    if (!rc && wlen_out) rc = states_winners(wl, wv, wlen_out, wlimbs_out, wnl_out);
+    if (!rc && wlen_out) rc = winners_out(wl, wv, wlen_out, wlimbs_out, wnl_out);
     if (!rc) {
-        memcpy(best, hres, (size_t) nprob * 4); memcpy(nties, hres + nprob, (size_t) nprob * 4);
-        memcpy(neligible, hres + 2 * (size_t) nprob, (size_t) nprob * 4); memcpy(vsign, hres + 3 * (size_t) nprob, (size_t) nprob * 4);
+        results_out(hres, nprob, best, nties, neligible, vsign);
         memcpy(f->states_ms, ms, sizeof ms); memcpy(f->states_paths, paths, sizeof paths);
     }
     free(hres);
@@ -6582,39 +6501,40 @@ extern "C" int slip_hip_price_select(int32_t ncols, int32_t nprob, int32_t nside
         !dlen || !dlimbs || !best || !nties || !neligible || !vsign)
         return SLIP_HIP_INCORRECT_INPUT;
     if (nside == 2 ? (!alen || !alimbs) : (alen || alimbs)) return SLIP_HIP_INCORRECT_INPUT;
-    if ((wlen_out || wlimbs_out || wnl_out) && (!wlen_out || !wlimbs_out || !wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
+    if (winners_args_bad(wlen_out, wlimbs_out, wnl_out)) return SLIP_HIP_INCORRECT_INPUT;
     TRY_(need_device());
     const int64_t ne = (int64_t) ncols * nprob;
     hipStream_t stream = (hipStream_t) stream_v;
-    SlipSlab xs, as, ds, ws; memset(&xs, 0, sizeof xs); memset(&as, 0, sizeof as); memset(&ds, 0, sizeof ds);
+    SlipSlab ws;
     TRY_(states_check(ncols, nside, state, wlen, wlimbs, w_limbs, &ws));
-    int32_t *dxl = NULL, *dal = NULL, *ddl = NULL, *res = NULL; int64_t *dxo = NULL, *dao = NULL, *ddo = NULL; uint64_t *dxv = NULL, *dav = NULL, *ddv = NULL;
+    SlipDevSlab x, a, d; memset(&x, 0, sizeof x); memset(&a, 0, sizeof a); memset(&d, 0, sizeof d);
+    int32_t *res = NULL;
     std::vector<int32_t> wl; std::vector<uint64_t> wv;
     double ms[2] = {0, 0};
     int64_t paths[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     SlipStatesOps O; memset(&O, 0, sizeof O);
     /* (every slab is checked against its capacity before a limb of it is read) */
-    int rc = ratio_upload(nprob, dlen, dlimbs, d_limbs, &ds, &ddl, &ddo, &ddv);
-    for (int32_t c = 0; c < nprob && !rc; c++) if (ds.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
-    A_(ratio_upload(ne, xlen, xlimbs, x_limbs, &xs, &dxl, &dxo, &dxv));
-    if (nside == 2) A_(ratio_upload(ne, alen, alimbs, a_limbs, &as, &dal, &dao, &dav));
+    int rc = dev_slab_upload(nprob, dlen, dlimbs, d_limbs, &d);
+    for (int32_t c = 0; c < nprob && !rc; c++) if (d.s.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    A_(dev_slab_upload(ne, xlen, xlimbs, x_limbs, &x));
+    if (nside == 2) A_(dev_slab_upload(ne, alen, alimbs, a_limbs, &a));
     A_(states_upload(ncols, state, &ws, wlimbs, &O));
     if (!rc && !(res = (int32_t *) malloc((size_t) nprob * 16))) rc = SLIP_HIP_OUT_OF_MEMORY;
     if (!rc && wlen_out) { *wlen_out = NULL; *wlimbs_out = NULL; *wnl_out = 0; }
     SlipStatesIn I; memset(&I, 0, sizeof I);
     I.n = ncols; I.nprob = nprob; I.nside = nside; I.sense = sense; I.xstride = ncols; I.astride = ncols;
-    I.x.len = dxl; I.x.off = dxo; I.x.limbs = dxv; I.a.len = dal; I.a.off = dao; I.a.limbs = dav; I.dlen = ddl;
+    I.x = dev_slab_recs(x); I.a = dev_slab_recs(a); I.dlen = d.len;
     A_(states_core(I, O, key, res, res + nprob, res + 2 * (int64_t) nprob, res + 3 * (int64_t) nprob,
                    wlen_out ? &wl : NULL, wlen_out ? &wv : NULL, stream, ms, paths));
-    if (!rc && wlen_out) rc = states_winners(wl, wv, wlen_out, wlimbs_out, wnl_out);
+    if (!rc && wlen_out) rc = winners_out(wl, wv, wlen_out, wlimbs_out, wnl_out);
     if (!rc) {
-        bound_results(res, nprob, best, nties, neligible, vsign);
+        results_out(res, nprob, best, nties, neligible, vsign);
         memcpy(slip_states_paths_last, paths, sizeof paths);
     }
     free(res);
-    dev_free(dxl); dev_free(dxo); dev_free(dxv); dev_free(dal); dev_free(dao); dev_free(dav); dev_free(ddl); dev_free(ddo); dev_free(ddv);
+    dev_slab_free(&x); dev_slab_free(&a); dev_slab_free(&d);
     states_ops_free(&O);
-    slab_free(&xs); slab_free(&as); slab_free(&ds); slab_free(&ws);
+    slab_free(&ws);
     return rc;
 }
 

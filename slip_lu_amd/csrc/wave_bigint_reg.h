@@ -68,6 +68,20 @@ template <int D> SLIP_DEV int wr_len(const WR<D> &x)
     return 0;
 }
 
+/* compare the magnitudes of two register numbers: -1, 0, +1 (all lanes call) */
+template <int D> SLIP_DEV int wr_cmp(const WR<D> &A, const WR<D> &B)
+{
+#pragma unroll
+    for (int q = D - 1; q >= 0; q--) {
+        const uint64_t df = slip_ballot(A.d[q] != B.d[q]);
+        if (df) {
+            const int t = 63 - slip_clz64(df);
+            return slip_readlane(A.d[q], t) > slip_readlane(B.d[q], t) ? 1 : -1;
+        }
+    }
+    return 0;
+}
+
 /* digit c of x as a wave-uniform value */
 template <int D> SLIP_DEV uint32_t wr_digit(const WR<D> &x, int c)
 {
