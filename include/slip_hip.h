@@ -718,6 +718,69 @@ int slip_hip_factor_update_ms(const slip_hip_factor *f, double out[2]);
 int slip_hip_factor_update_paths(const slip_hip_factor *f, int64_t out[8]);
 int slip_hip_pivot_update_paths(int64_t out[8]);
 
+/* Bounded exact simplex step: the bounded ratio test above, the comparison of the winning step with the entering variable's
+ * own range, and the update of all n numerators -- a pivot or a bound flip -- in one call; between the selection and the
+ * update no numerator leaves the device.
+ *
+ * The entering variable of problem c over the bounds' denominator bd: its current value ev_c / bd (evlen NULL: 0) and, with
+ * finite[c] = 1, a range er_c / bd >= 0, the distance to its opposite bound (finite NULL: no range is finite).  er and ev
+ * are limb slabs of nprob entries; er is required iff some finite[c] is set, and the entry of a problem whose flag is 0 is
+ * never read.  A NULL slip_hip_entering: no range is finite and every value is 0. */
+typedef struct slip_hip_entering {
+    const int32_t *finite;                                 /* nprob flags 0 / 1, or NULL */
+    const int32_t *erlen; const uint64_t *erlimbs; int64_t er_limbs;   /* nprob entries >= 0 */
+    const int32_t *evlen; const uint64_t *evlimbs; int64_t ev_limbs;   /* nprob entries, optional */
+} slip_hip_entering;
+
+/* Problem c: xnum, anum over one nonzero signed d (on a handle d = det), s = sign(d).  The selection is
+ * slip_hip_factor_ratio_test_bounded's: best, nties, neligible, side; r = best[c], N_r and a'_r as defined there, the step
+ * theta = N_r / (bd * sense * a'_r).  Then move[c]:
+ *   2, a flip, iff finite[c] and (best = -1 or er_c * |a'_r| <= s * N_r) -- an exact tie flips, it needs no basis change:
+ *        R_i = bd * xnum_i - sense * er_c * anum_i for all n entries, Dn = bd * d, E = (ev_c + sense * er_c) * d;
+ *   1, a pivot, iff best >= 0 and no flip:
+ *        R_i = (bd * a'_r * xnum_i - N_r * anum_i) / d for i != r, R_r = E = ev_c * a'_r + N_r, Dn = bd * a'_r;
+ *   0, unbounded, otherwise: the n entries of R, Dn and E of that problem have length 0.
+ * The new basic values are R_i / Dn, the entering variable's new value E / Dn; after a pivot the leaving variable sits on
+ * the bound side[c] names.  On a handle every division is exact; on caller slabs an entry d does not divide comes back with
+ * length 0 and is counted in ninexact[c].  With kind = 1, lonum = 0, bd = 1 and no entering data R, Dn, best, nties and
+ * neligible are slip_hip_factor_step's.
+ *
+ * slip_hip_factor_step_bounded: b holds 2 * nprob right-hand sides as slip_hip_factor_ratio_test takes them; indices are
+ * those of the matching solve (pivot position for transpose 0, original row id for transpose 1).  slip_hip_step_bounded: the
+ * same on caller slabs of nprob * n entries and one d_c per problem.  r (nprob * n entries), dn and e (nprob entries each)
+ * are normalised malloc'ed slabs (slip_hip_free).  Results are written only when every staging group has succeeded.
+ *
+ * SLIP_HIP_INCORRECT_INPUT, with nothing written and before any array is read past its end: everything
+ * slip_hip_factor_ratio_test_bounded and slip_hip_factor_step refuse; a finite[c] outside {0, 1}; a finite range with a NULL
+ * er slab; exactly one of evlen / evlimbs NULL; a negative er_c with finite[c] set; a slab whose sum |len| exceeds its
+ * capacity; any NULL output.  A broken handle or no device: SLIP_HIP_DEVICE_ERROR.
+ *
+ * _ms (of the handle's last call; of this thread's last handle-less call): device ms of out[0] the selection's classify,
+ * offset and form passes, out[1] the selection, out[2] slip_bstep_kernel (capture, classify, form), out[3] the update.
+ * _paths: out[0..7] slip_hip_factor_bound_paths' counts, out[8..12] the first five of slip_hip_factor_update_paths (the slot
+ * of a pivot's leaving entry is computed like any other before E replaces it), out[13..15] the problems that were
+ * unbounded, pivoted, flipped, out[16..19] the scalars slip_bstep_kernel formed [16] without arithmetic (both terms zero),
+ * [17] in a lane, [18] in registers, [19] through memory: per problem the comparison (finite[c] and best >= 0), then the
+ * two of its move (P and E of a pivot, Dn and E of a flip). */
+int slip_hip_factor_step_bounded(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                                 const slip_hip_bounds *bounds, const slip_hip_entering *entering, int32_t sense, const int32_t *key,
+                                 int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side, int32_t *move, int32_t *ninexact,
+                                 int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                                 int32_t **dnlen_out, uint64_t **dnlimbs_out, int64_t *dnnl_out,
+                                 int32_t **elen_out, uint64_t **elimbs_out, int64_t *enl_out, void *stream);
+int slip_hip_step_bounded(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                          const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                          const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                          const slip_hip_bounds *bounds, const slip_hip_entering *entering, int32_t sense, const int32_t *key,
+                          int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side, int32_t *move, int32_t *ninexact,
+                          int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                          int32_t **dnlen_out, uint64_t **dnlimbs_out, int64_t *dnnl_out,
+                          int32_t **elen_out, uint64_t **elimbs_out, int64_t *enl_out, void *stream);
+int slip_hip_factor_step_bounded_ms(const slip_hip_factor *f, double out[4]);
+int slip_hip_factor_step_bounded_paths(const slip_hip_factor *f, int64_t out[20]);
+int slip_hip_step_bounded_ms(double out[4]);
+int slip_hip_step_bounded_paths(int64_t out[20]);
+
 void slip_hip_factor_destroy(slip_hip_factor *f);
 /* Device buffers of destroyed handles are kept in a process-level pool for the next handle (the drop-in SLIP_LU_factorize
  * creates and destroys one per call): at most SLIP_HIP_POOL_MB megabytes (environment, default 32768; 0 = no pool).  This

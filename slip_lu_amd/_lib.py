@@ -25,6 +25,12 @@ class BoundsRec(C.Structure):
                 ("bdlen", C.c_int32), ("bdlimbs", C.c_void_p)]
 
 
+class EnteringRec(C.Structure):
+    """slip_hip_entering"""
+    _fields_ = [("finite", C.c_void_p), ("erlen", C.c_void_p), ("erlimbs", C.c_void_p), ("er_limbs", C.c_int64),
+                ("evlen", C.c_void_p), ("evlimbs", C.c_void_p), ("ev_limbs", C.c_int64)]
+
+
 class Info(C.Structure):
     _fields_ = [("n", C.c_int32), ("K", C.c_int32), ("status", C.c_int32), ("window_end", C.c_int32),
                 ("lnz", C.c_int64), ("unz", C.c_int64), ("l_limbs", C.c_int64), ("u_limbs", C.c_int64),
@@ -62,7 +68,9 @@ EXPORTS = ("slip_hip_default_options", "slip_hip_device_count", "slip_hip_factor
            "slip_hip_factor_price_states", "slip_hip_price_select", "slip_hip_factor_price_states_ms",
            "slip_hip_factor_price_states_paths", "slip_hip_price_select_paths",
            "slip_hip_pivot_update", "slip_hip_factor_solve_update", "slip_hip_factor_step", "slip_hip_factor_update_ms",
-           "slip_hip_factor_update_paths", "slip_hip_pivot_update_paths")
+           "slip_hip_factor_update_paths", "slip_hip_pivot_update_paths",
+           "slip_hip_factor_step_bounded", "slip_hip_step_bounded", "slip_hip_factor_step_bounded_ms",
+           "slip_hip_factor_step_bounded_paths", "slip_hip_step_bounded_ms", "slip_hip_step_bounded_paths")
 
 _libs = {}
 
@@ -232,5 +240,19 @@ def load(path=None):
     lib.slip_hip_factor_update_paths.restype = C.c_int
     lib.slip_hip_pivot_update_paths.argtypes = [vp]
     lib.slip_hip_pivot_update_paths.restype = C.c_int
+    ep = C.POINTER(EnteringRec)
+    stepb = [bp, ep, C.c_int32, vp] + [vp] * 6 + win * 3 + [vp]     # bounds, entering, sense, key, six results, R, Dn, E, stream
+    lib.slip_hip_factor_step_bounded.argtypes = [vp, C.c_int32, C.c_int32, vp, vp] + stepb
+    lib.slip_hip_factor_step_bounded.restype = C.c_int
+    lib.slip_hip_step_bounded.argtypes = [C.c_int32, C.c_int32] + [vp, vp, i64] * 3 + stepb
+    lib.slip_hip_step_bounded.restype = C.c_int
+    lib.slip_hip_factor_step_bounded_ms.argtypes = [vp, vp]
+    lib.slip_hip_factor_step_bounded_ms.restype = C.c_int
+    lib.slip_hip_factor_step_bounded_paths.argtypes = [vp, vp]
+    lib.slip_hip_factor_step_bounded_paths.restype = C.c_int
+    lib.slip_hip_step_bounded_ms.argtypes = [vp]
+    lib.slip_hip_step_bounded_ms.restype = C.c_int
+    lib.slip_hip_step_bounded_paths.argtypes = [vp]
+    lib.slip_hip_step_bounded_paths.restype = C.c_int
     _libs[path] = lib
     return lib

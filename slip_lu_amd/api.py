@@ -434,6 +434,89 @@ class StepResult:
         self.best, self.nties, self.neligible, self.ninexact, self.x, self.d = best, nties, neligible, ninexact, x, d
 
 
+class Entering:
+    """The entering variables of a bounded step (slip_hip_entering), one per problem, over the bounds' denominator: finite[c]
+    = 1 switches on a finite range er_c / den >= 0, the distance to the variable's opposite bound; value is its current value
+    ev_c / den (None: 0).  er and value are Python ints (one, or one per problem) or (signed limb counts, limbs) slabs."""
+
+    def __init__(self, nprob, finite=None, er=None, value=None):
+        self.nprob = int(nprob)
+        self.rec = _lib.EnteringRec()
+        self.finite = None if finite is None else np.ascontiguousarray(finite, dtype=np.int32)
+        if self.finite is not None:
+            if self.finite.size != self.nprob:
+                raise ValueError("Entering: finite must hold one flag per problem")
+            self.rec.finite = self.finite.ctypes.data
+        self.er = None if er is None else _scalar_slab(er, self.nprob, "er")
+        self.ev = None if value is None else _scalar_slab(value, self.nprob, "value")
+        if self.er is not None:
+            self.rec.erlen, self.rec.erlimbs, self.rec.er_limbs = self.er[0].ctypes.data, self.er[1].ctypes.data, self.er[2]
+        if self.ev is not None:
+            self.rec.evlen, self.rec.evlimbs, self.rec.ev_limbs = self.ev[0].ctypes.data, self.ev[1].ctypes.data, self.ev[2]
+
+    def ref(self, nprob):
+        if self.nprob != nprob:
+            raise ValueError("Entering: made for another nprob")
+        return C.byref(self.rec)
+
+
+class BoundedStepResult:
+    """What step_bounded returns: best, nties, neligible, side, move (0 unbounded, 1 pivot, 2 flip), ninexact (int32[nprob]
+    each), x = (rlen, rlimbs) the new numerators (nprob * n entries), d = (dlen, dlimbs) the new denominators and e = (elen,
+    elimbs) the entering variables' new numerators (nprob entries each)."""
+
+    def __init__(self, best, nties, neligible, side, move, ninexact, x, d, e):
+        self.best, self.nties, self.neligible, self.side, self.move, self.ninexact = best, nties, neligible, side, move, ninexact
+        self.x, self.d, self.e = x, d, e
+
+
+def _step_bounded_call(lib, fn, where, head, n, nprob, bounds, entering, sense, key, stream):
+    res = [np.zeros(max(nprob, 1), np.int32) for _ in range(6)]
+    outs = [(C.c_void_p(), C.c_void_p(), C.c_int64()) for _ in range(3)]
+    rc = fn(*head, bounds.ref(n), None if entering is None else entering.ref(nprob), int(sense),
+            None if key is None else key.ctypes.data, *[r.ctypes.data for r in res],
+            *[C.byref(v) for o in outs for v in o], C.c_void_p(stream or 0))
+    if rc:
+        raise SlipError(rc, where)
+    x, d, e = (_take_slab(lib, *o, cnt) for o, cnt in zip(outs, (n * nprob, nprob, nprob)))
+    return BoundedStepResult(*(r[:nprob] for r in res), x, d, e)
+
+
+def step_bounded(n, xlen, xlimbs, alen, alimbs, dlen, dlimbs, bounds, entering=None, nprob=1, sense=1, key=None, lib_path=None):
+    """One bounded exact simplex step on caller slabs (slip_hip_step_bounded): the selection of `ratio_test_bounded`, the
+    comparison of the winning step with the entering variable's own range (`Entering`), then the new numerators of a pivot
+    (move 1: R_i = (den * a'_r * x_i - N_r * a_i) / d, entry best the entering variable's E = ev * a'_r + N_r, over den *
+    a'_r) or of a bound flip (move 2: R_i = den * x_i - sense * er * a_i over den * d, E = (ev + sense * er) * d; an exact tie
+    flips); move 0 leaves the problem's outputs empty.  Returns a BoundedStepResult."""
+    lib = _lib.load(lib_path)
+    n, nprob = int(n), int(nprob)
+    args, keep = [], []
+    for t, (lens, limbs) in enumerate(((xlen, xlimbs), (alen, alimbs), (dlen, dlimbs))):
+        lens, limbs, cap = _limb_arrays(lens, limbs)
+        if n >= 1 and nprob >= 1 and lens.size != (nprob if t == 2 else n * nprob):
+            raise ValueError("step_bounded: x and a must hold n*nprob entries, d nprob")
+        keep.append((lens, limbs))
+        args += [lens.ctypes.data, limbs.ctypes.data, cap]
+    key = _ratio_key(n, key) if n >= 1 else None
+    return _step_bounded_call(lib, lib.slip_hip_step_bounded, "slip_hip_step_bounded", [n, nprob] + args, n, nprob, bounds, entering,
+                              sense, key, None)
+
+
+def step_bounded_paths(lib_path=None):
+    """this thread's last handle-less step_bounded: the eight counts of `bound_paths`, the first five of `pivot_update_paths`,
+    the problems [unbounded, pivoted, flipped], the scalars formed [without arithmetic, in a lane, in registers, through memory]"""
+    out = np.zeros(20, np.int64)
+    _lib.load(lib_path).slip_hip_step_bounded_paths(out.ctypes.data)
+    return [int(v) for v in out]
+
+
+def step_bounded_ms(lib_path=None):
+    """device ms of this thread's last handle-less step_bounded: [the selection's form passes, the selection, the scalars, the update]"""
+    out = np.zeros(4, np.float64)
+    _lib.load(lib_path).slip_hip_step_bounded_ms(out.ctypes.data)
+    return [float(v) for v in out]
+
+
 def _states_args(ncols, state, weights, where):
     """the states and optional weights of a pricing with states as the arguments of the C ABI (and the arrays behind them)"""
     state = np.ascontiguousarray(state, dtype=np.int32)
@@ -986,6 +1069,29 @@ class Factorization:
         x = _take_slab(self.lib, pl, px, nl, self.n * nprob)
         d = _take_slab(self.lib, ql, qx, qn, nprob)
         return StepResult(*(r[:nprob] for r in res), x, d)
+
+    def step_bounded(self, blen, blimbs, bounds, entering=None, nprob=1, transpose=False, sense=1, key=None, stream=None):
+        """One bounded exact simplex step on the device (slip_hip_factor_step_bounded): the right-hand sides and index
+        conventions of `ratio_test_bounded`, the definition of the module's `step_bounded` with d = det; no numerator crosses
+        the host between the selection and the update.  Returns a BoundedStepResult."""
+        nprob = int(nprob)
+        blen, blimbs, _ = _rhs(self.n, blen, blimbs, 2 * nprob if nprob >= 1 else nprob)
+        key = _ratio_key(self.n, key)
+        head = [self.h, int(bool(transpose)), nprob, blen.ctypes.data, blimbs.ctypes.data]
+        return _step_bounded_call(self.lib, self.lib.slip_hip_factor_step_bounded, "slip_hip_factor_step_bounded", head, self.n, nprob,
+                                  bounds, entering, sense, key, stream)
+
+    def step_bounded_ms(self):
+        """device ms of the last step_bounded: [the selection's form passes, the selection, the scalars, the update]"""
+        out = np.zeros(4, np.float64)
+        self.lib.slip_hip_factor_step_bounded_ms(self.h, out.ctypes.data)
+        return [float(v) for v in out]
+
+    def step_bounded_paths(self):
+        """the last step_bounded, as the module's `step_bounded_paths`"""
+        out = np.zeros(20, np.int64)
+        self.lib.slip_hip_factor_step_bounded_paths(self.h, out.ctypes.data)
+        return [int(v) for v in out]
 
     def update_ms(self):
         """device ms of the last solve_update or step: [the classify, offset and form passes, the selection of a step]"""

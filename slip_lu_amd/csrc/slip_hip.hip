@@ -25,6 +25,7 @@
 #include <string.h>
 #include <math.h>
 #include <vector>
+#include <functional>
 
 #define SLIP_LDS_MAX_WORDS 40000          /* of the 40960 words (160 KiB) per CU */
 #define SLIP_BITMAP_LDS_MAX_WORDS 16384   /* n <= 524288 keeps the pattern bitmap in LDS */
@@ -2132,6 +2133,253 @@ static void slip_pivot_body(SlipPivotArgs A)
     }
 }
 
+/* The scalars of a bounded step (slip_hip_factor_step_bounded, slip_hip_step_bounded): between the bounded
+ * selection (slip_bound_kernel, slip_ratio_kernel) and the update of all n numerators (slip_pivot_kernel), per problem c the
+ * move and the records the update takes, formed on the device from the winner r = best[c] of the selection (N_r and a'_r as
+ * DESIGN 3l defines them), d_c (s its sign), bd and the entering variable's value ev_c / bd and range er_c / bd >= 0
+ * (finite[c]):
+ *   flip  (2) iff finite[c] and (best < 0 or er_c |a'_r| <= s N_r):
+ *               P = bd, T = sense er_c, D = 1, Dn = bd d_c, E = (ev_c + sense er_c) d_c;
+ *   pivot (1) iff best >= 0 and no flip:  P = Dn = bd a'_r, T = N_r, D = d_c, E = ev_c a'_r + N_r;
+ *   none  (0) otherwise: empty records, place -2 (slip_pivot_kernel skips the problem).
+ * Every scalar is of the form s1 |X||Y| + s2 |Z||W| (SlipBstepJob).  One wavefront per problem in every phase, wave-uniform.
+ *
+ * phase 0, capture (inside the selection's sink, the group's staging slab alive): the winner's numerator, which phase 3 of
+ *   slip_bound_kernel has given a record with the sign of d_c taken out again, copied into the problem's nstride limbs of a
+ *   slab that outlives the group; the record of a'_r (into the a slab, which stays) copied.
+ * phase 1, classify and size: from the operands' bit lengths, as phase 0 of slip_pivot_kernel, the digits nd no scalar of
+ *   either move exceeds, and those of what is copied; the widest to wmax[0], the widest two's-complement sum of the memory
+ *   path (nd + 1) to wmax[1].  The host reads 8 bytes back and sizes the five regions (P, T, D, E, Dn) of a problem.
+ * phase 2, form: the comparison (into the E region, overwritten afterwards), the move, then the two products of the move
+ *   and the copies.  A scalar whose terms are both zero takes no arithmetic (path 0); both products of at most four digits
+ *   by the factors' digit counts finish in lane 0 as 128-bit numbers (path 1); nd <= 256 in registers, class ceil(nd / 64)
+ *   (path 2); above through the wave's scratch, modulo B^Wp in two's complement (path 3).  Every value leaves as whole limbs
+ *   with a trimmed signed digit count.  paths[0 .. 3]: the scalars formed by path; err: a value that did not fit (never, by
+ *   phase 1's sizes). */
+struct SlipBstepArgs {
+    int32_t nprob, phase, sense;
+    const int32_t *wnlen, *walen; const int64_t *wnoff, *waoff; const uint64_t *stage;    /* phase 0: the group's winners        */
+    int32_t *nlen; uint64_t *nslab; int64_t nstride;                               /* N_r: nstride limbs a problem           */
+    int32_t *arlen; int64_t *aroff; const uint64_t *alimbs;                        /* a'_r: records into the a slab          */
+    const int32_t *dlen; const int64_t *doff; const uint64_t *dlimbs;              /* d_c: entry c                           */
+    int32_t bddig; const uint64_t *bdlimbs, *one;                                  /* bd > 0, trimmed; a limb holding 1      */
+    const int32_t *best, *finite;                                                  /* finite NULL: no range is finite        */
+    const int32_t *erlen; const int64_t *eroff; const uint64_t *erlimbs;           /* er_c (finite set)                      */
+    const int32_t *evlen; const int64_t *evoff; const uint64_t *evlimbs;           /* ev_c, or NULL: 0                       */
+    int32_t *wmax;
+    uint64_t *slab; int64_t stride;                                                /* region k of problem c: (5 c + k) stride */
+    int32_t *rlen; int64_t *roff; int64_t rstride;                                 /* record k of problem c: k * rstride + c */
+    int32_t *place, *move, *err;
+    dig_t *scratch; int32_t wcap;                                                  /* path 3: 2 * wcap digits per wave       */
+    unsigned long long *paths;
+};
+
+/* s1 |X||Y| + s2 |Z||W| */
+struct SlipBstepJob { SlipBoundOp X, Y, Z, W; int s1, s2; };
+SLIP_DEV SlipBstepJob slip_bstep_job(const SlipBoundOp &X, const SlipBoundOp &Y, int s1, const SlipBoundOp &Z, const SlipBoundOp &W, int s2)
+{
+    SlipBstepJob J;
+    J.X = X; J.Y = Y; J.Z = Z; J.W = W; J.s1 = s1; J.s2 = s2;
+    return J;
+}
+
+/* the digits the scalar does not exceed, from its factors' bit lengths; *path as slip_pivot_kernel's phase 0 chooses it */
+SLIP_DEV int slip_bstep_digits(const SlipBstepJob &J, int *path)
+{
+    const int b1 = J.s1 ? wb_bits(J.X.p, J.X.l) + wb_bits(J.Y.p, J.Y.l) : 0, b2 = J.s2 ? wb_bits(J.Z.p, J.Z.l) + wb_bits(J.W.p, J.W.l) : 0;
+    const int w1 = J.s1 ? J.X.l + J.Y.l : 0, w2 = J.s2 ? J.Z.l + J.W.l : 0;
+    const int nd = ((b1 > b2 ? b1 : b2) + 1 + 31) >> 5;
+    *path = !J.s1 && !J.s2 ? 0 : w1 <= 4 && w2 <= 4 ? 1 : nd <= 256 ? 2 : 3;
+    return *path ? nd : 0;
+}
+
+/* lane arithmetic: both products as 128-bit numbers, the signed sum into out (at most five digits); its signed digit count */
+SLIP_DEV int slip_bstep_lane(const SlipBstepJob &J, uint64_t *out)
+{
+    const slip_u128 P = J.s1 ? slip_bound_load128(J.X) * slip_bound_load128(J.Y) : 0, Q = J.s2 ? slip_bound_load128(J.Z) * slip_bound_load128(J.W) : 0;
+    slip_u128 mag; uint32_t top = 0; int sg;
+    if (J.s1 == J.s2 || !J.s1 || !J.s2) { mag = P + Q; top = mag < P ? 1u : 0u; sg = J.s1 ? J.s1 : J.s2; }
+    else if (P >= Q) { mag = P - Q; sg = P == Q ? 0 : J.s1; }
+    else { mag = Q - P; sg = J.s2; }
+    if (sg == 0 || (!top && mag == 0)) return 0;
+    const uint64_t l0 = (uint64_t) mag, l1 = (uint64_t)(mag >> 64);
+    const int len = top ? 5 : l1 ? (l1 >> 32 ? 4 : 3) : (l0 >> 32 ? 2 : 1);
+    out[0] = l0;
+    if (len > 2) out[1] = l1;
+    if (len > 4) out[2] = top;
+    return sg < 0 ? -len : len;
+}
+
+/* registers: both products below B^(64*D) and their signed sum too; whole limbs into out, the signed digit count */
+template <int D> SLIP_DEV int slip_bstep_reg(const SlipBstepJob &J, dig_t *out)
+{
+    const WR<D> P = J.s1 ? slip_bound_mul_reg<D>(J.X, J.Y) : wr_zero<D>(), Q = J.s2 ? slip_bound_mul_reg<D>(J.Z, J.W) : wr_zero<D>();
+    WR<D> N; int sg;
+    if (!J.s1 || !J.s2 || J.s1 == J.s2) { N = wr_addsub<D>(P, Q, 0); sg = J.s1 ? J.s1 : J.s2; }
+    else {
+        const int cm = wr_cmp<D>(P, Q);
+        sg = cm > 0 ? J.s1 : cm < 0 ? J.s2 : 0;
+        N = cm >= 0 ? wr_addsub<D>(P, Q, 1) : wr_addsub<D>(Q, P, 1);
+    }
+    const int len = wr_len<D>(N);
+    if (sg == 0 || len == 0) return 0;
+    wr_store<D>(out, N, (len + 1) & ~1);
+    return sg < 0 ? -len : len;
+}
+
+/* memory: the sum modulo B^Wp, Wp even, in two's complement on two buffers of Wp digits; whole limbs into out */
+SLIP_DEV int slip_bstep_wide(const SlipBstepJob &J, int Wp, dig_t *num, dig_t *prod, dig_t *out)
+{
+    for (int k = slip_lane(); k < Wp; k += SLIP_WAVE) num[k] = 0u;
+    slip_wave_sync();
+    if (J.s1) { wb_mul_lo(prod, J.X.p, J.X.l, J.Y.p, J.Y.l, Wp); wb_addsub(num, num, Wp, prod, Wp, Wp, J.s1 < 0); }
+    if (J.s2) { wb_mul_lo(prod, J.Z.p, J.Z.l, J.W.p, J.W.l, Wp); wb_addsub(num, num, Wp, prod, Wp, Wp, J.s2 < 0); }
+    const int neg = (int)(num[Wp - 1] >> 31);
+    if (neg) wb_addsub(num, (const dig_t *) 0, 1, num, Wp, Wp, 1, 0u);
+    const int ln = wb_len(num, Wp);
+    wb_copy_pad(out, num, ln);
+    return neg ? -ln : ln;
+}
+
+/* one scalar into its region of cap digits (buf: the wave's scratch, 2 * wcap digits, or NULL); its signed digit count,
+ * *path the path that formed it, *bad set when it does not fit */
+SLIP_DEV int slip_bstep_form(const SlipBstepJob &J, dig_t *out, int cap, dig_t *buf, int wcap, int *path, int *bad)
+{
+    const int nd = slip_bstep_digits(J, path);
+    if (*path == 0) return 0;
+    if (nd > cap || (*path == 3 && (!buf || ((nd + 2) & ~1) > wcap))) { *bad = 1; return 0; }
+    int len = 0;
+    if (*path == 1) {
+        if (slip_lane() == 0) len = slip_bstep_lane(J, (uint64_t *) out);
+        len = (int) slip_shfl_u32((uint32_t) len, 0);
+        slip_wave_sync();
+    } else if (*path == 2) {
+        const int cls = (nd + 63) >> 6;
+        if (cls == 1) len = slip_bstep_reg<1>(J, out);
+        else if (cls == 2) len = slip_bstep_reg<2>(J, out);
+        else if (cls == 3) len = slip_bstep_reg<3>(J, out);
+        else len = slip_bstep_reg<4>(J, out);
+        slip_wave_sync();
+    } else len = slip_bstep_wide(J, (nd + 2) & ~1, buf, buf + wcap, out);
+    return len;
+}
+
+/* phase 1: a scalar's digits into the widths of its problem */
+SLIP_DEV void slip_bstep_size(const SlipBstepJob &J, uint32_t *W, uint32_t *Ww)
+{
+    int path;
+    const uint32_t nd = (uint32_t) slip_bstep_digits(J, &path);
+    if (nd > *W) *W = nd;
+    if (path == 3 && nd + 1 > *Ww) *Ww = nd + 1;
+}
+
+/* phase 2: a scalar formed, counted by its path */
+#define SLIP_BSTEP_FORM(J, out) slip_bstep_form(J, out, cap, buf, A.wcap, &path, &bad); \
+    for (int k_ = 0; k_ < 4; k_++) cnt[k_] += path == k_ ? 1u : 0u
+
+#ifndef SLIP_EMULATE
+__global__ void __launch_bounds__(256)
+slip_bstep_kernel(SlipBstepArgs A)
+#else
+static void slip_bstep_body(SlipBstepArgs A)
+#endif
+{
+    const int lane = slip_lane();
+    const int64_t wave0 = (int64_t) slip_block() * slip_nwaves() + slip_wave(), nwaves = (int64_t) slip_nblocks() * slip_nwaves();
+    if (A.phase == 0) {
+        for (int64_t c = wave0; c < A.nprob; c += nwaves) {
+            int32_t nl = A.wnlen[c];
+            const int l = slip_abs(nl);
+            if ((int64_t) l > 2 * A.nstride) { nl = 0; if (lane == 0) slip_atomic_add_i32(A.err, 1); }
+            else wb_copy_pad((dig_t *)(A.nslab + c * A.nstride), (const dig_t *)(A.stage + A.wnoff[c]), l);
+            if (lane == 0) { A.nlen[c] = nl; A.arlen[c] = A.walen[c]; A.aroff[c] = A.waoff[c]; }
+        }
+        return;
+    }
+    const int cap = (int)(2 * A.stride);
+    dig_t *buf = A.scratch ? A.scratch + wave0 * 2 * (int64_t) A.wcap : (dig_t *) 0;
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    uint32_t wall = 0, wwave = 0;
+    int nbad = 0;
+    for (int64_t c = wave0; c < A.nprob; c += nwaves) {
+        const int32_t b = A.best[c];
+        const int fin = A.finite ? A.finite[c] != 0 : 0;
+        SlipBoundOp Z, Ar, N, BD, ONE, ER, EV;
+        Z.p = (const dig_t *) 0; Z.l = 0; Z.s = 0;
+        Ar = Z; N = Z; ER = Z; EV = Z;
+        if (b >= 0) {
+            Ar = slip_bound_op(A.arlen, A.aroff, A.alimbs, c);
+            const int32_t nl = A.nlen[c];
+            N.p = (const dig_t *)(A.nslab + c * A.nstride);
+            N.l = slip_trim_digits(N.p, slip_abs(nl));
+            N.s = N.l == 0 ? 0 : (nl < 0 ? -1 : 1);
+        }
+        const SlipBoundOp Dd = slip_bound_op(A.dlen, A.doff, A.dlimbs, c);
+        BD.p = (const dig_t *) A.bdlimbs; BD.l = A.bddig; BD.s = 1;
+        ONE.p = (const dig_t *) A.one; ONE.l = 1; ONE.s = 1;
+        if (fin) ER = slip_bound_op(A.erlen, A.eroff, A.erlimbs, c);
+        if (A.evlen) EV = slip_bound_op(A.evlen, A.evoff, A.evlimbs, c);
+        /* the comparison er |a'| - s N; the two products of a pivot; those of a flip */
+        const SlipBstepJob Jc = slip_bstep_job(ER, Ar, ER.s, N, ONE, -Dd.s * N.s);
+        const SlipBstepJob Jp1 = slip_bstep_job(BD, Ar, Ar.s, Z, Z, 0), Jp2 = slip_bstep_job(EV, Ar, EV.s * Ar.s, N, ONE, N.s);
+        const SlipBstepJob Jf1 = slip_bstep_job(BD, Dd, Dd.s, Z, Z, 0), Jf2 = slip_bstep_job(EV, Dd, EV.s * Dd.s, ER, Dd, A.sense * ER.s * Dd.s);
+        if (A.phase == 1) {
+            uint32_t W = (uint32_t)(Dd.l > BD.l ? Dd.l : BD.l), Ww = 0;
+            if ((uint32_t) N.l > W) W = (uint32_t) N.l;
+            if ((uint32_t) ER.l > W) W = (uint32_t) ER.l;
+            if (fin && b >= 0) slip_bstep_size(Jc, &W, &Ww);
+            if (b >= 0) { slip_bstep_size(Jp1, &W, &Ww); slip_bstep_size(Jp2, &W, &Ww); }
+            if (fin) { slip_bstep_size(Jf1, &W, &Ww); slip_bstep_size(Jf2, &W, &Ww); }
+            if (W > wall) wall = W;
+            if (Ww > wwave) wwave = Ww;
+            continue;
+        }
+        dig_t *rP = (dig_t *)(A.slab + (5 * c + 0) * A.stride), *rT = (dig_t *)(A.slab + (5 * c + 1) * A.stride);
+        dig_t *rD = (dig_t *)(A.slab + (5 * c + 2) * A.stride), *rE = (dig_t *)(A.slab + (5 * c + 3) * A.stride);
+        dig_t *rN = (dig_t *)(A.slab + (5 * c + 4) * A.stride);
+        int path, bad = 0, move;
+        if (fin && b >= 0) {
+            const int lc = SLIP_BSTEP_FORM(Jc, rE);
+            move = lc <= 0 ? 2 : 1;                                /* (a tie: the flip) */
+        } else move = fin ? 2 : b >= 0 ? 1 : 0;
+        int lP = 0, lT = 0, lD = 1, lE = 0, lN = 0;
+        int64_t oN = (5 * c + 4) * A.stride;
+        if (move == 1) {
+            lP = SLIP_BSTEP_FORM(Jp1, rP);
+            lE = SLIP_BSTEP_FORM(Jp2, rE);
+            wb_copy_pad(rT, N.p, N.l); lT = N.s * N.l;
+            wb_copy_pad(rD, Dd.p, Dd.l); lD = Dd.s * Dd.l;
+            lN = lP; oN = (5 * c + 0) * A.stride;                  /* Dn = P */
+        } else {
+            if (move == 2) {
+                lN = SLIP_BSTEP_FORM(Jf1, rN);
+                lE = SLIP_BSTEP_FORM(Jf2, rE);
+                wb_copy_pad(rP, BD.p, BD.l); lP = BD.l;
+                wb_copy_pad(rT, ER.p, ER.l); lT = A.sense * ER.s * ER.l;
+            }
+            wb_copy_pad(rD, ONE.p, 1);
+        }
+        if (lane == 0) {
+            A.rlen[c] = lP; A.roff[c] = (5 * c + 0) * A.stride;
+            A.rlen[A.rstride + c] = lT; A.roff[A.rstride + c] = (5 * c + 1) * A.stride;
+            A.rlen[2 * A.rstride + c] = lD; A.roff[2 * A.rstride + c] = (5 * c + 2) * A.stride;
+            A.rlen[3 * A.rstride + c] = lE; A.roff[3 * A.rstride + c] = (5 * c + 3) * A.stride;
+            A.rlen[4 * A.rstride + c] = lN; A.roff[4 * A.rstride + c] = oN;
+            A.place[c] = move ? -1 : -2; A.move[c] = move;
+        }
+        nbad += bad;
+    }
+    if (lane == 0) {
+        if (A.phase == 1) {
+            if (wall) slip_atomic_max_i32(A.wmax + 0, (int32_t) wall);
+            if (wwave) slip_atomic_max_i32(A.wmax + 1, (int32_t) wwave);
+        } else {
+            for (int k = 0; k < 4; k++) if (cnt[k]) slip_atomic_add_u64(A.paths + k, cnt[k]);
+            if (nbad) slip_atomic_add_i32(A.err, nbad);
+        }
+    }
+}
+
 /* Nonbasic states and reference weights in exact pricing (slip_hip_factor_price_states, slip_hip_price_select):
  * the records slip_ratio_kernel selects on, formed from the numerators X_j (and A_j, nside 2) of nprob problems over one
  * nonzero signed d_c each, the state of every column (0 never eligible, 1 at its lower bound, 2 at its upper bound, 3 free)
@@ -2674,6 +2922,7 @@ struct slip_hip_factor {
     /* slip_hip_factor_solve_update / _step: device time of the last call (the classify, offset and form passes, the selection
      * of a step), the entries by the path that formed them and the inexact ones */
     double update_ms[2]; int64_t update_paths[8];
+    double bstep_ms[4]; int64_t bstep_paths[20];          /* the last bounded step */
     /* slip_hip_factor_rewind / _replace_column: the host copy of q; the storage of the resident A -- annz / alimbs are its
      * LIVE entries and limbs, Acap_nz / Acap_nl what dAi, dAlen, dAoff / dAlimbs can hold, Anl_used the limbs of the slab
      * handed out (live ones and the dead ones of replaced columns: new limbs are appended there), A0_nz / A0_nl the initial
@@ -5622,10 +5871,16 @@ struct SlipBoundIn {
     const int32_t *oidx, *pos;
 };
 
+/* what a fused caller does with the winners of a group while its staging slab is alive: (c0, nv, wcap, the nv records of N
+ * into dstage, dstage, the nv records of a' into I.a.limbs), all on the device; its status */
+typedef std::function<int(int64_t, int64_t, int64_t, const int32_t *, const int64_t *, const uint64_t *, const int32_t *, const int64_t *)> SlipBoundCapture;
+
 /* one bounded selection on the device.  res: 4 * nprob host integers (best, nties, the count, side); with wlen_out the
- * winners' slab (mode 0: N and a' of every problem, a' read from I.a.limbs; mode 1: v).  ms: the form passes, the selection. */
+ * winners' slab (mode 0: N and a' of every problem, a' read from I.a.limbs; mode 1: v).  ms: the form passes, the selection.
+ * capture (mode 0; NULL: none): handed the winners' records of every group after its selection. */
 static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const SlipHostBounds &hb, const int32_t *key, int32_t *res,
-                      int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, hipStream_t stream, double ms[2], int64_t paths[8])
+                      int32_t **wlen_out, uint64_t **wlimbs_out, int64_t *wnl_out, hipStream_t stream, double ms[2], int64_t paths[8],
+                      const SlipBoundCapture *capture = NULL)
 {
     const int32_t n = I.n, nprob = I.nprob;
     const int64_t ne = (int64_t) n * nprob, rpp = ((int64_t) n + SLIP_WAVE - 1) / SLIP_WAVE;
@@ -5647,7 +5902,7 @@ static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const Slip
     A_(dev_alloc(&dcls, ne)); A_(dev_alloc(&dw, ne)); A_(dev_alloc(&drl, ne)); A_(dev_alloc(&dso, ne));
     A_(dev_alloc(&dal2, ne)); A_(dev_alloc(&dao2, ne)); A_(dev_alloc(&dwmax, 2)); A_(dev_alloc(&dpaths, 4));
     A_(dev_alloc(&dsel, 2 * (int64_t) nprob));
-    if (wlen_out) { A_(dev_alloc(&dwn, 2 * (int64_t) nprob)); A_(dev_alloc(&dwo, 2 * (int64_t) nprob)); }
+    if (wlen_out || capture) { A_(dev_alloc(&dwn, 2 * (int64_t) nprob)); A_(dev_alloc(&dwo, 2 * (int64_t) nprob)); }
     HIP_(hipMemsetAsync(dwmax, 0, 8, stream)); HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
     SlipBoundArgs A; memset(&A, 0, sizeof A);
     A.n = n; A.mode = I.mode; A.sense = I.sense; A.xstride = I.xstride; A.astride = I.astride;
@@ -5700,12 +5955,13 @@ static int bound_core(const SlipBoundIn &I, const slip_hip_bounds *B, const Slip
         if (!rc) {
             slice(c0, nv, 3);
             A.best = dsel; A.side = dsel + nprob;
-            if (wlen_out) { A.wnlen = dwn; A.wnoff = dwo; A.walen = I.mode ? NULL : dwn + nprob; A.waoff = I.mode ? NULL : dwo + nprob; }
+            if (wlen_out || capture) { A.wnlen = dwn; A.wnoff = dwo; A.walen = I.mode ? NULL : dwn + nprob; A.waoff = I.mode ? NULL : dwo + nprob; }
             A_(SERVICE_LAUNCH(bound, service_blocks(nv), stream, A));
             HIP_(hipStreamSynchronize(stream));
         }
         DOWN_(hres + 3 * (int64_t) nprob + c0, dsel + nprob, (size_t) nv * 4);
         if (wlen_out) A_(winners_collect(nv, dwn, dwo, dstage, dwn + nprob, dwo + nprob, I.mode ? NULL : I.a.limbs, &wl, &wv, stream));
+        if (capture) A_((*capture)(c0, nv, wcap, dwn, dwo, dstage, dwn + nprob, dwo + nprob));
         return rc;
     };
     A_(staged_run(n, nprob, 1, wcap, dw, dso, form, select, stream, &ms[0], &ms[0]));
@@ -6123,6 +6379,303 @@ extern "C" int slip_hip_factor_update_paths(const slip_hip_factor *f, int64_t ou
 {
     if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
     memcpy(out, f->update_paths, sizeof f->update_paths);
+    return SLIP_HIP_OK;
+}
+
+/* ---- the bounded step: the bounded ratio test, the comparison of the winning step with the entering variable's own range,
+ * and the update of all n numerators -- a pivot or a bound flip -- with no numerator crossing the host in between (no
+ * counterpart in the reference; kernels: slip_bound_kernel, slip_ratio_kernel, slip_bstep_kernel, slip_pivot_kernel;
+ * DESIGN 3o) ---- */
+
+/* the counts and passes of this thread's last handle-less bounded step */
+static thread_local int64_t slip_bstep_paths_last[20];
+static thread_local double slip_bstep_ms_last[4];
+
+/* the entering variables' data checked and laid out on the host */
+struct SlipHostEntering { SlipSlab er, ev; int any_finite, has_ev; };
+static void host_entering_free(SlipHostEntering *h) { slab_free(&h->er); slab_free(&h->ev); }
+static int host_entering(int32_t nprob, const slip_hip_entering *En, SlipHostEntering *h)
+{
+    memset(h, 0, sizeof *h);
+    if (!En) return SLIP_HIP_OK;
+    if (En->finite) for (int32_t c = 0; c < nprob; c++) {
+        if (En->finite[c] != 0 && En->finite[c] != 1) return SLIP_HIP_INCORRECT_INPUT;
+        h->any_finite |= En->finite[c];
+    }
+    if ((h->any_finite && (!En->erlen || !En->erlimbs)) || !En->evlen != !En->evlimbs) return SLIP_HIP_INCORRECT_INPUT;
+    int rc = h->any_finite ? slab_prepare(nprob, En->erlen, En->erlimbs, En->er_limbs, &h->er) : 0;
+    for (int32_t c = 0; c < nprob && !rc && h->any_finite; c++) if (En->finite[c] && h->er.dig[c] < 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    if (!rc && En->evlen) { rc = slab_prepare(nprob, En->evlen, En->evlimbs, En->ev_limbs, &h->ev); h->has_ev = !rc; }
+    if (rc) host_entering_free(h);
+    return rc;
+}
+
+/* E_c into the slot best[c] of every problem that pivots: the result slab (signed limb counts rl, limbs *rv of *rn) rebuilt */
+static int bstep_place(int32_t n, int32_t nprob, const int32_t *best, const int32_t *move, const int32_t *el, const uint64_t *ev,
+                       int32_t *rl, uint64_t **rv, int64_t *rn)
+{
+    auto mag = [](int32_t l) { return (int64_t)(l < 0 ? -l : l); };
+    int64_t total = *rn;
+    for (int32_t c = 0; c < nprob; c++) if (move[c] == 1) total += mag(el[c]) - mag(rl[(int64_t) c * n + best[c]]);
+    uint64_t *out = (uint64_t *) malloc((size_t)(total > 0 ? total : 1) * 8);
+    if (!out) return SLIP_HIP_OUT_OF_MEMORY;
+    int64_t so = 0, dn = 0, eo = 0;
+    for (int32_t c = 0; c < nprob; c++) {
+        const int32_t r = move[c] == 1 ? best[c] : -1;
+        for (int32_t i = 0; i < n; i++) {
+            int32_t *l = rl + (int64_t) c * n + i;
+            if (i == r) {
+                so += mag(*l);
+                memcpy(out + dn, ev + eo, (size_t) mag(el[c]) * 8); dn += mag(el[c]);
+                *l = el[c];
+            } else { memcpy(out + dn, *rv + so, (size_t) mag(*l) * 8); so += mag(*l); dn += mag(*l); }
+        }
+        eo += mag(el[c]);
+    }
+    free(*rv);
+    *rv = out; *rn = total;
+    return SLIP_HIP_OK;
+}
+
+/* one bounded step on the device: the operands as bound_core takes them (mode 0), the entering data as host_entering left
+ * them.  res: 4 * nprob host integers (best, nties, neligible, side); move, ninexact: nprob each; R: n * nprob entries in
+ * reported order, Dn and E: nprob entries each, compact malloc'ed slabs.  ms: the selection's form passes, the selection,
+ * slip_bstep_kernel, the update; paths: bound_core's eight counts, pivot_core's five, the problems by move (0, 1, 2), the
+ * scalars slip_bstep_kernel formed by path (4). */
+static int bstep_core(const SlipBoundIn &I, const slip_hip_bounds *B, const SlipHostBounds &hb,
+                      const slip_hip_entering *En, const SlipHostEntering &he, const int32_t *key,
+                      int32_t *res, int32_t *move, int32_t *ninexact,
+                      int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                      int32_t **nlen_out, uint64_t **nlimbs_out, int64_t *nnl_out,
+                      int32_t **elen_out, uint64_t **elimbs_out, int64_t *enl_out,
+                      hipStream_t stream, double ms[4], int64_t paths[20])
+{
+    const int32_t n = I.n, nprob = I.nprob;
+    int32_t *dnlen = NULL, *darlen = NULL, *derr = NULL, *dwmax = NULL, *dbest = NULL, *dfin = NULL, *drlen = NULL, *dplace = NULL, *dmove = NULL;
+    int64_t *daroff = NULL, *droff = NULL; uint64_t *dnslab = NULL, *dbd = NULL, *dslab = NULL;
+    unsigned long long *dpaths = NULL, hpaths[4] = {0, 0, 0, 0};
+    dig_t *dscr = NULL;
+    SlipDevSlab er, ev; memset(&er, 0, sizeof er); memset(&ev, 0, sizeof ev);
+    int32_t hwmax[2] = {0, 0}, herr = 0;
+    int32_t *hmove = (int32_t *) malloc((size_t) nprob * 4), *hres = (int32_t *) malloc((size_t) nprob * 16), *hnin = (int32_t *) malloc((size_t) nprob * 4);
+    int32_t *rl = NULL, *nl = NULL, *el = NULL; uint64_t *rv = NULL, *nv = NULL, *evv = NULL; int64_t rn = 0, nn = 0, en = 0;
+    int64_t nstride = 0;
+    double bms[2] = {0, 0}, pms = 0, sms = 0; int64_t bpaths[8], ppaths[8];
+    int rc = !hmove || !hres || !hnin ? SLIP_HIP_OUT_OF_MEMORY : 0;
+    const int64_t bdn = ((int64_t) hb.bddig + 1) >> 1;
+    A_(dev_alloc(&dnlen, nprob)); A_(dev_alloc(&darlen, nprob)); A_(dev_alloc(&daroff, nprob)); A_(dev_alloc(&derr, 1)); A_(dev_alloc(&dwmax, 2));
+    A_(dev_alloc(&dpaths, 4)); A_(dev_alloc(&dbest, nprob)); A_(dev_alloc(&drlen, 5 * (int64_t) nprob)); A_(dev_alloc(&droff, 5 * (int64_t) nprob));
+    A_(dev_alloc(&dplace, nprob)); A_(dev_alloc(&dmove, nprob));
+    A_(dev_alloc(&dbd, bdn + 1)); UP_(dbd, B->bdlimbs ? B->bdlimbs : &hb.one, (size_t) bdn * 8); UP_(dbd + bdn, &hb.one, 8);
+    if (he.any_finite) {
+        A_(dev_alloc(&dfin, nprob)); UP_(dfin, En->finite, (size_t) nprob * 4);
+        A_(dev_slab_put(nprob, he.er, En->erlimbs, &er));
+    }
+    if (he.has_ev) A_(dev_slab_put(nprob, he.ev, En->evlimbs, &ev));
+    HIP_(hipMemsetAsync(derr, 0, 4, stream)); HIP_(hipMemsetAsync(dwmax, 0, 8, stream)); HIP_(hipMemsetAsync(dpaths, 0, 32, stream));
+    SlipBstepArgs S; memset(&S, 0, sizeof S);
+    S.sense = I.sense; S.alimbs = I.a.limbs; S.dlimbs = I.d.limbs; S.bddig = hb.bddig; S.bdlimbs = dbd; S.one = dbd + bdn;
+    S.erlimbs = er.limbs; S.evlimbs = ev.limbs; S.wmax = dwmax; S.err = derr; S.paths = dpaths;
+    /* the winners of a group into slabs that outlive its staging slab */
+    const SlipBoundCapture capture = [&](int64_t c0, int64_t nv, int64_t wcap, const int32_t *wnl, const int64_t *wno, const uint64_t *dstage,
+                                         const int32_t *wal, const int64_t *wao) {
+        int rc = 0;
+        double t = 0;
+        if (!dnslab) { nstride = wcap / 2; A_(dev_alloc(&dnslab, nprob * nstride)); }
+        SlipBstepArgs C = S;
+        C.nprob = (int32_t) nv; C.phase = 0; C.wnlen = wnl; C.wnoff = wno; C.walen = wal; C.waoff = wao; C.stage = dstage;
+        C.nlen = dnlen + c0; C.nslab = dnslab + c0 * nstride; C.nstride = nstride; C.arlen = darlen + c0; C.aroff = daroff + c0;
+        SlipTimed timed;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(bstep, wave_blocks(nv), stream, C));
+        A_(timed.end(stream, &t));
+        sms += t;
+        return rc;
+    };
+    A_(bound_core(I, B, hb, key, hres, NULL, NULL, NULL, stream, bms, bpaths, &capture));
+    UP_(dbest, hres, (size_t) nprob * 4);
+    S.nprob = nprob; S.nlen = dnlen; S.nslab = dnslab; S.nstride = nstride; S.arlen = darlen; S.aroff = daroff;
+    S.dlen = I.d.len; S.doff = I.d.off; S.best = dbest; S.finite = dfin;
+    S.erlen = er.len; S.eroff = er.off; S.evlen = ev.len; S.evoff = ev.off;
+    S.rlen = drlen; S.roff = droff; S.rstride = nprob; S.place = dplace; S.move = dmove;
+    if (!rc) {                                             /* the widths of every scalar either move may need */
+        SlipTimed timed;
+        double t = 0;
+        S.phase = 1;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(bstep, wave_blocks(nprob), stream, S));
+        A_(timed.end(stream, &t));
+        sms += t;
+    }
+    DOWN_(hwmax, dwmax, 8);
+    const int64_t stride = hwmax[0] > 1 ? ((int64_t) hwmax[0] + 1) >> 1 : 1, scap = ((int64_t) hwmax[1] + 1) & ~(int64_t) 1;
+    if (!rc && (stride > (1 << 27) || scap > (1 << 27))) rc = SLIP_HIP_OUT_OF_MEMORY;
+    const int64_t sblocks = hwmax[1] > 0 ? fit_scratch(wave_blocks(nprob), 2 * scap) : wave_blocks(nprob);
+    if (hwmax[1] > 0) { A_(dev_alloc(&dscr, sblocks * SERVICE_WAVES * 2 * scap)); S.scratch = dscr; S.wcap = (int32_t) scap; }
+    A_(dev_alloc(&dslab, 5 * (int64_t) nprob * stride));
+    S.slab = dslab; S.stride = stride;
+    if (!rc) {                                             /* the move and its records */
+        SlipTimed timed;
+        double t = 0;
+        S.phase = 2;
+        A_(timed.begin(stream));
+        A_(SERVICE_LAUNCH(bstep, sblocks, stream, S));
+        A_(timed.end(stream, &t));
+        sms += t;
+    }
+    DOWN_(&herr, derr, 4); DOWN_(hmove, dmove, (size_t) nprob * 4); DOWN_(hpaths, dpaths, 32);
+    if (!rc && herr) rc = SLIP_HIP_DEVICE_ERROR;                                    /* a scalar wider than phase 1 sized it */
+    SlipPivotIn U; memset(&U, 0, sizeof U);
+    U.n = n; U.nprob = nprob; U.oidx = I.oidx; U.pos = I.pos; U.place = dplace;
+    U.v = I.x; U.vstride = I.xstride; U.a = I.a; U.astride = I.astride;
+    U.p.len = drlen; U.p.off = droff; U.t.len = drlen + nprob; U.t.off = droff + nprob; U.d.len = drlen + 2 * (int64_t) nprob; U.d.off = droff + 2 * (int64_t) nprob;
+    U.p.limbs = U.t.limbs = U.d.limbs = dslab;
+    A_(pivot_core(U, hnin, &rl, &rv, &rn, stream, &pms, ppaths));
+    A_(pack_download(nprob, drlen + 4 * (int64_t) nprob, droff + 4 * (int64_t) nprob, dslab, 0, &nl, &nv, &nn, stream));
+    A_(pack_download(nprob, drlen + 3 * (int64_t) nprob, droff + 3 * (int64_t) nprob, dslab, 0, &el, &evv, &en, stream));
+    A_(bstep_place(n, nprob, hres, hmove, el, evv, rl, &rv, &rn));
+    if (!rc) {
+        memcpy(res, hres, (size_t) nprob * 16); memcpy(move, hmove, (size_t) nprob * 4); memcpy(ninexact, hnin, (size_t) nprob * 4);
+        *rlen_out = rl; *rlimbs_out = rv; *rnl_out = rn; *nlen_out = nl; *nlimbs_out = nv; *nnl_out = nn; *elen_out = el; *elimbs_out = evv; *enl_out = en;
+        rl = nl = el = NULL; rv = nv = evv = NULL;
+        ms[0] = bms[0]; ms[1] = bms[1]; ms[2] = sms; ms[3] = pms;
+        memset(paths, 0, 20 * sizeof(int64_t));
+        memcpy(paths, bpaths, sizeof bpaths); memcpy(paths + 8, ppaths, 5 * sizeof(int64_t));
+        for (int32_t c = 0; c < nprob; c++) paths[13 + hmove[c]]++;
+        for (int k = 0; k < 4; k++) paths[16 + k] = (int64_t) hpaths[k];
+    }
+    free(hmove); free(hres); free(hnin); free(rl); free(rv); free(nl); free(nv); free(el); free(evv);
+    dev_slab_free(&er); dev_slab_free(&ev);
+    dev_free(dnlen); dev_free(darlen); dev_free(daroff); dev_free(derr); dev_free(dwmax); dev_free(dpaths); dev_free(dbest); dev_free(dfin);
+    dev_free(drlen); dev_free(droff); dev_free(dplace); dev_free(dmove); dev_free(dnslab); dev_free(dbd); dev_free(dslab); dev_free(dscr);
+    return rc;
+}
+
+/* the outputs of a bounded step: all required */
+static int bstep_outputs_bad(const int32_t *best, const int32_t *nties, const int32_t *neligible, const int32_t *side, const int32_t *move,
+                             const int32_t *ninexact, int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                             int32_t **nlen_out, uint64_t **nlimbs_out, int64_t *nnl_out, int32_t **elen_out, uint64_t **elimbs_out, int64_t *enl_out)
+{
+    return !best || !nties || !neligible || !side || !move || !ninexact || !rlen_out || !rlimbs_out || !rnl_out ||
+           !nlen_out || !nlimbs_out || !nnl_out || !elen_out || !elimbs_out || !enl_out;
+}
+
+extern "C" int slip_hip_factor_step_bounded(slip_hip_factor *f, int32_t transpose, int32_t nprob, const int32_t *blen, const uint64_t *blimbs,
+                                            const slip_hip_bounds *bounds, const slip_hip_entering *entering, int32_t sense, const int32_t *key,
+                                            int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side, int32_t *move, int32_t *ninexact,
+                                            int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                                            int32_t **dnlen_out, uint64_t **dnlimbs_out, int64_t *dnnl_out,
+                                            int32_t **elen_out, uint64_t **elimbs_out, int64_t *enl_out, void *stream_v)
+{
+    if (!f || nprob < 1 || nprob > (1 << 27) || (sense != 1 && sense != -1) || !blen || !blimbs || !bounds || !bounds->kind ||
+        bstep_outputs_bad(best, nties, neligible, side, move, ninexact, rlen_out, rlimbs_out, rnl_out, dnlen_out, dnlimbs_out, dnnl_out,
+                          elen_out, elimbs_out, enl_out))
+        return SLIP_HIP_INCORRECT_INPUT;
+    if (!transpose && f->factors_only) return SLIP_HIP_INCORRECT_INPUT;             /* no q behind such a handle */
+    if (f->broken) return SLIP_HIP_DEVICE_ERROR;
+    if (f->hs.F != f->n) return SLIP_HIP_INCORRECT_INPUT;       /* needs the complete factorisation */
+    const int32_t n = f->n;
+    hipStream_t stream = (hipStream_t) stream_v;
+    SlipHostBounds hb; SlipHostEntering he;
+    TRY_(host_bounds(n, bounds, &hb));
+    int rc = host_entering(nprob, entering, &he);
+    if (rc) { host_bounds_free(&hb); return rc; }
+    SlipSolveOut o;
+    rc = solve_device(f, transpose, 2 * nprob, blen, blimbs, stream, &o);
+    if (rc) { host_bounds_free(&hb); host_entering_free(&he); return rc; }
+    int32_t *ddlen = NULL, *doidx = NULL, *dpos = NULL, *res = (int32_t *) malloc((size_t) nprob * 16); int64_t *ddoff = NULL;
+    int32_t dmaxdig = 0;
+    if (!res) rc = SLIP_HIP_OUT_OF_MEMORY;
+    A_(det_records(f, nprob, &ddlen, &ddoff, &dmaxdig));
+    A_(transposed_maps(f, transpose, &doidx, &dpos));
+    SlipBoundIn I; memset(&I, 0, sizeof I);
+    I.n = n; I.nprob = nprob; I.mode = 0; I.sense = sense; I.oidx = doidx; I.pos = dpos;
+    I.x.len = o.olen; I.x.off = o.ooff; I.x.limbs = o.olimbs; I.xstride = 2 * (int64_t) n;
+    I.a.len = o.olen + n; I.a.off = o.ooff + n; I.a.limbs = o.olimbs; I.astride = 2 * (int64_t) n;
+    I.d.len = ddlen; I.d.off = ddoff; I.d.limbs = f->P.Llimbs;
+    double ms[4]; int64_t paths[20];
+    A_(bstep_core(I, bounds, hb, entering, he, key, res, move, ninexact, rlen_out, rlimbs_out, rnl_out, dnlen_out, dnlimbs_out, dnnl_out,
+                  elen_out, elimbs_out, enl_out, stream, ms, paths));
+    if (!rc) {
+        results_out(res, nprob, best, nties, neligible, side);
+        memcpy(f->bstep_ms, ms, sizeof ms); memcpy(f->bstep_paths, paths, sizeof paths);
+    }
+    free(res); dev_free(doidx); dev_free(dpos); dev_free(ddlen); dev_free(ddoff);
+    solve_out_free(&o);
+    host_bounds_free(&hb); host_entering_free(&he);
+    return rc;
+}
+
+extern "C" int slip_hip_step_bounded(int32_t n, int32_t nprob, const int32_t *xlen, const uint64_t *xlimbs, int64_t x_limbs,
+                                     const int32_t *alen, const uint64_t *alimbs, int64_t a_limbs,
+                                     const int32_t *dlen, const uint64_t *dlimbs, int64_t d_limbs,
+                                     const slip_hip_bounds *bounds, const slip_hip_entering *entering, int32_t sense, const int32_t *key,
+                                     int32_t *best, int32_t *nties, int32_t *neligible, int32_t *side, int32_t *move, int32_t *ninexact,
+                                     int32_t **rlen_out, uint64_t **rlimbs_out, int64_t *rnl_out,
+                                     int32_t **dnlen_out, uint64_t **dnlimbs_out, int64_t *dnnl_out,
+                                     int32_t **elen_out, uint64_t **elimbs_out, int64_t *enl_out, void *stream_v)
+{
+    if (n <= 0 || nprob < 1 || nprob > (1 << 27) || (sense != 1 && sense != -1) || !xlen || !xlimbs || !alen || !alimbs || !dlen || !dlimbs ||
+        !bounds || !bounds->kind ||
+        bstep_outputs_bad(best, nties, neligible, side, move, ninexact, rlen_out, rlimbs_out, rnl_out, dnlen_out, dnlimbs_out, dnnl_out,
+                          elen_out, elimbs_out, enl_out))
+        return SLIP_HIP_INCORRECT_INPUT;
+    const int64_t ne = (int64_t) n * nprob;
+    SlipHostBounds hb; SlipHostEntering he;
+    TRY_(host_bounds(n, bounds, &hb));
+    int rc = host_entering(nprob, entering, &he);
+    if (rc) { host_bounds_free(&hb); return rc; }
+    SlipDevSlab x, a, d; memset(&x, 0, sizeof x); memset(&a, 0, sizeof a); memset(&d, 0, sizeof d);
+    int32_t *res = NULL;
+    /* (every slab is checked against its capacity before a limb of it is read, and all of them before the device is asked for) */
+    A_(slab_prepare(nprob, dlen, dlimbs, d_limbs, &d.s));
+    for (int32_t c = 0; c < nprob && !rc; c++) if (d.s.dig[c] == 0) rc = SLIP_HIP_INCORRECT_INPUT;
+    A_(slab_prepare(ne, xlen, xlimbs, x_limbs, &x.s));
+    A_(slab_prepare(ne, alen, alimbs, a_limbs, &a.s));
+    A_(need_device());
+    A_(dev_slab_put(nprob, d.s, dlimbs, &d)); A_(dev_slab_put(ne, x.s, xlimbs, &x)); A_(dev_slab_put(ne, a.s, alimbs, &a));
+    if (!rc && !(res = (int32_t *) malloc((size_t) nprob * 16))) rc = SLIP_HIP_OUT_OF_MEMORY;
+    SlipBoundIn I; memset(&I, 0, sizeof I);
+    I.n = n; I.nprob = nprob; I.mode = 0; I.sense = sense; I.xstride = n; I.astride = n;
+    I.x = dev_slab_recs(x); I.a = dev_slab_recs(a); I.d = dev_slab_recs(d);
+    double ms[4]; int64_t paths[20];
+    A_(bstep_core(I, bounds, hb, entering, he, key, res, move, ninexact, rlen_out, rlimbs_out, rnl_out, dnlen_out, dnlimbs_out, dnnl_out,
+                  elen_out, elimbs_out, enl_out, (hipStream_t) stream_v, ms, paths));
+    if (!rc) {
+        results_out(res, nprob, best, nties, neligible, side);
+        memcpy(slip_bstep_ms_last, ms, sizeof ms); memcpy(slip_bstep_paths_last, paths, sizeof paths);
+    }
+    free(res);
+    dev_slab_free(&x); dev_slab_free(&a); dev_slab_free(&d);
+    host_bounds_free(&hb); host_entering_free(&he);
+    return rc;
+}
+
+extern "C" int slip_hip_factor_step_bounded_ms(const slip_hip_factor *f, double out[4])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->bstep_ms, sizeof f->bstep_ms);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_factor_step_bounded_paths(const slip_hip_factor *f, int64_t out[20])
+{
+    if (!f || !out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, f->bstep_paths, sizeof f->bstep_paths);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_step_bounded_paths(int64_t out[20])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_bstep_paths_last, sizeof slip_bstep_paths_last);
+    return SLIP_HIP_OK;
+}
+
+extern "C" int slip_hip_step_bounded_ms(double out[4])
+{
+    if (!out) return SLIP_HIP_INCORRECT_INPUT;
+    memcpy(out, slip_bstep_ms_last, sizeof slip_bstep_ms_last);
     return SLIP_HIP_OK;
 }
 
